@@ -2,13 +2,17 @@
 """Headline benchmark: aligned reads/s through `coverm contig` (BAM -> pileup -> per-contig) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full   (also every leg beyond the headline figure, below)
+    python bench.py ... --dump-outputs DIR                 (what the last timed step computed, as DIR/<name>.npy)
 
 Workload (BASELINE.json configs[1] at N = 1; configs[3] shape — one BAM per GPU — at N > 1):
 50 M synthetic 150 bp reads over 5 000 contigs (1.0 Gbp), coordinate sorted, methods
-`mean trimmed_mean covered_fraction variance` (SURVEY.md §8d profile, coverm_amd/synth.py).
+`mean trimmed_mean covered_fraction variance` (SURVEY.md §8d profile, coverm_amd/synth.py).  The inputs depend only on the arguments.
 
-`value` is measured on basis (i) below, as the bench contract prescribes (inputs resident in HBM when the clock starts); the same
-JSON line carries the two wider bases, each beside a CPU figure taken on the SAME basis (`bases`):
+`value` is measured on basis (i) below, as the bench contract prescribes (inputs resident in HBM when the clock starts).  A plain run
+sets up, warms up, times the steps and prints the line.  With --full the same JSON line also carries the two wider bases, each beside
+a CPU figure taken on the SAME basis (`bases`), the parity check and configs 2 / 3 through the binary (N = 1), or the product's
+--devices legs (N > 1):
 
   (i)   device_resident  one step = cov_finish (filter + CIGAR expansion + LDS pileup + statistics + every estimator's calculate_coverage
                          for every contig, all on the GPU) + fetch of the floats + the C++ scan loop's control flow (zero rows, ReadsMapped,
@@ -17,8 +21,8 @@ JSON line carries the two wider bases, each beside a CPU figure taken on the SAM
   (iii) end_to_end       BAM FILE -> TSV through the coverm-amd binary (streamed ingest) on a realistic-entropy BAM (random bases,
                          Phred-like qualities) of BASELINE config 5's size and flags; CPU = the same decoder (t threads) + oracle scan
 
-`parity_checked`: the oracle's per-contig output over 100 % of the workload is compared with the GPU step's (every f32 bit-for-bit,
-every integer statistic); the run exits non-zero if they differ.  For N > 1 each rank holds one sample and rank 0 receives the
+`parity_checked` (--full): the oracle's per-contig output over 100 % of the workload is compared with the GPU step's (every f32
+bit-for-bit, every integer statistic); the run exits non-zero if they differ.  For N > 1 each rank holds one sample and rank 0 receives the
 per-contig coverages through one RCCL gather.  Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -204,6 +208,28 @@ def finalise(ref, est, stats, summ, hist, name="sample0", estimates=None):
     sample = host.SampleResult(name, stats, hist, int(summ.num_detected_primary_alignments))
     rm = host.contig_coverage(ref.names, ref.lengths, [sample], taker, est, True, estimates=None if estimates is None else [estimates])
     return taker, rm
+
+
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array of `arrays` (name -> what a caller of the timed path receives) as d/<name>.npy, float32 kept as it is and
+    everything else as float64.  Should they pass DUMP_LIMIT bytes in all, each keeps a fixed, seeded sample of its rows (the same rows
+    for the same shape on every run) and the chosen row numbers are written beside it as <name>_rows.npy."""
+    os.makedirs(d, exist_ok=True)
+    conv = {}
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        conv[k] = np.ascontiguousarray(v, np.float32 if v.dtype == np.float32 else np.float64)
+    total = sum(v.nbytes + (8 * len(v) if v.ndim else 0) for v in conv.values())
+    frac = 1.0 if total <= DUMP_LIMIT else 0.95 * DUMP_LIMIT / total
+    for k, v in conv.items():
+        if frac < 1.0 and v.ndim and len(v) > 1:
+            rows = np.sort(np.random.default_rng(0).choice(len(v), max(1, int(len(v) * frac)), replace=False))
+            np.save(os.path.join(d, k + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 # ---------------------------------------------------------------------------------------------- end to end
@@ -521,6 +547,11 @@ def main():
                     help="seconds this command may take: the plan (legs and what each is expected to cost) is printed up front, and a leg that cannot finish inside what is left is skipped and recorded as skipped instead of dying in the caller's timeout")
     ap.add_argument("--tmp", default=os.environ.get("COVERM_BENCH_TMP", default_tmp()),
                     help="where the end-to-end leg writes its BAM (default: /dev/shm when it has room, so that storage speed is not part of the figure)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the parity check against the oracle, the CPU baseline, bases (ii) and (iii), "
+                         "configs 2 / 3 through the binary and, at N > 1, the product's --devices legs (each still subject to the --no-* switches above)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
     a = ap.parse_args()
     BUDGET["t0"] = time.time() - float(os.environ.get("COVERM_BENCH_ELAPSED", 0))      # (the relaunch below hands over what it used)
     BUDGET["limit"] = a.time_limit
@@ -528,10 +559,14 @@ def main():
     share = os.environ.get("COVERM_BENCH_SHARE_GPU") == "1"
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
-        # `python bench.py --gpus N` on its own: become N ranks (one per GPU) under torch.distributed.run, as the driver's launch line does
+        # `python bench.py --gpus N` on its own: run N ranks (one per GPU) under torch.distributed.run, as the driver's launch line does.
+        # They run as a child process, not through exec: check_devices has opened the GPU, and a process holding it must not replace itself.
         check_devices(a.gpus, share)
-        os.execvpe(sys.executable, relaunch_cmd(a.gpus, sys.argv[1:]), dict(os.environ, MASTER_ADDR="127.0.0.1", COVERM_BENCH_ELAPSED=str(time.time() - BUDGET["t0"])))
+        p = subprocess.run(relaunch_cmd(a.gpus, sys.argv[1:]), env=dict(os.environ, MASTER_ADDR="127.0.0.1", COVERM_BENCH_ELAPSED=str(time.time() - BUDGET["t0"])))
+        sys.exit(p.returncode)
     rank = int(os.environ.get("RANK", 0))
     world = int(os.environ.get("WORLD_SIZE", 1))
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
@@ -627,7 +662,16 @@ def main():
     else:
         total_reads = considered
     gpu_cov = taker.cached_coverages(0)
-    if hist is None:
+    if rank == 0 and a.dump_outputs:
+        outputs = {"coverage": gpu_cov.reshape(len(ref.lengths), len(est)), "summary": [getattr(summ, f) for f, _ in summ._fields_],
+                   "reads_mapped": [[r.num_mapped_reads, r.num_reads] for r in rm]}
+        outputs.update(("contig_stats_" + f, stats[f]) for f in stats.dtype.names if f != "reserved")
+        if hist is not None:
+            outputs["hist"] = hist
+        if gather_buf is not None:
+            outputs["gathered_coverage"] = torch.stack(gather_buf).cpu().numpy().reshape(world, len(ref.lengths), len(est))
+        dump_outputs(a.dump_outputs, outputs)
+    if hist is None and a.full:
         hist = sess.hist()        # (for the parity check of the integer statistics: the step itself no longer needs the bins on the host)
     pipe_bytes = sess.algorithmic_bytes()
     n_tiles = sess_tiles(sess, ref)
@@ -675,7 +719,7 @@ def main():
             "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "i32 depth / u64 sums / f32 estimators", "data": "synthetic",
             "estimators_evaluated_on": "device (k_estimate inside cov_finish: the reference's f32 expressions, one rounding per operation; floats checked bit for bit against the oracle in parity_checked)" if dev_est else "host (csrc/host_coverage.cpp calculate)",
-            "value_basis": "(i) device_resident: records already in HBM when the clock starts (bench contract); bases (ii) and (iii) below include the host side",
+            "value_basis": "(i) device_resident: records already in HBM when the clock starts (bench contract); bases (ii) and (iii) (--full) include the host side",
             "config": {"workload": "coverm contig, %d-read synthetic sorted BAM over %d contigs (%.2f Gbp) per GPU, "
                                    "--methods %s, records resident in HBM" % (a.reads, a.contigs,
                                                                              ref.lengths.sum() / 1e9, " ".join(METHODS)),
@@ -687,7 +731,7 @@ def main():
             "roofline": roof,
             "host": {"generation_s": gen_s, "nproc": os.cpu_count(), "usable_cpus": usable_cpus()},
         }
-        if not a.no_cpu_baseline and world == 1:     # CPU legs (parity at full size, baselines, end to end) on rank 0 at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:     # CPU legs (parity at full size, baselines, end to end) on rank 0 at N = 1 only
             threads = max(1, int(os.environ.get("COVERM_BENCH_THREADS", usable_cpus())))
             par, (cpu_mapped, cpu_dt), oracle_cfg2 = parity_check(ref, batch, gpu_cov, stats, hist)
             out["parity_checked"] = par
@@ -749,7 +793,7 @@ def main():
                 except Exception as ex:   # the headline legs above stand on their own
                     out["bases"]["end_to_end"] = {"error": repr(ex)[:1000]}
         fake = os.environ.get("COVERM_BENCH_MULTI_DEVICE_CHECK")     # e.g. "0,0": the --devices legs on a single-GPU box (functional check, not a measurement)
-        if fake and world == 1:
+        if a.full and fake and world == 1:
             try:
                 out["multi_device_end_to_end_functional_check"] = multi_device_legs(a, max(1, usable_cpus()), len(fake.split(",")), devs=fake)
                 if not out["multi_device_end_to_end_functional_check"].get("tables_equal", False):
@@ -757,9 +801,9 @@ def main():
             except Exception as ex:
                 out["multi_device_end_to_end_functional_check"] = {"error": repr(ex)[:1000]}
                 exit_code = 3
-        if world > 1 and not a.no_multi_device_e2e and not share and not leg_allowed("multi_device_end_to_end", a, world, out):
+        if a.full and world > 1 and not a.no_multi_device_e2e and not share and not leg_allowed("multi_device_end_to_end", a, world, out):
             pass
-        elif world > 1 and not a.no_multi_device_e2e and not share:
+        elif a.full and world > 1 and not a.no_multi_device_e2e and not share:
             # the product's own multi-GPU path (one process, N devices): run by rank 0 while the other ranks wait on the host (wait_for_root below)
             try:
                 threads = max(1, int(os.environ.get("COVERM_BENCH_THREADS", usable_cpus())))
@@ -810,13 +854,13 @@ def leg_estimates(a, world):
     scale = a.reads / 50e6
     e2e = a.e2e_reads / 200e6
     est = {"sample + device-resident steps": 45 * scale + 10}
-    if world == 1 and not a.no_cpu_baseline:
+    if a.full and world == 1 and not a.no_cpu_baseline:
         est["parity + cpu baseline + push-inclusive"] = 40 * scale
         if not a.no_binary_legs:
             est["binary_configs"] = 75 * scale
         if not a.no_e2e:
             est["end_to_end"] = (215 if a.no_level6 else 370) * e2e      # (five runs of the binary per level + two as one process)
-    if world > 1 and not a.no_multi_device_e2e:
+    if a.full and world > 1 and not a.no_multi_device_e2e:
         est["multi_device_end_to_end"] = (60 + 35 * world) * scale + 260 * e2e
     return est
 

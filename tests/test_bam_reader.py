@@ -12,7 +12,7 @@ from tests.fixtures import load_fixture
 from tests.golden import cases
 from tests.knobs import set_knobs
 
-REF_DATA = "/root/reference/tests/data"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 FIELDS = ("tid", "pos", "flag", "mapq", "nm", "nm_kind", "cigar_off", "cigar")
 
 
@@ -27,9 +27,9 @@ def same(af, d: bamio.BamData):
         assert af.qname == d.qname
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference fixtures only exist in the build container")
 def test_reference_fixture_files_decode_identically():
-    paths = sorted(glob.glob(REF_DATA + "/*.bam") + glob.glob(REF_DATA + "/*.sam"))
+    """The reference's own fixture files as it ships them, byte for byte: BAM under tests/golden/raw, SAM under tests/golden/raw_sam."""
+    paths = sorted(glob.glob(os.path.join(GOLDEN, "raw", "*.bam")) + glob.glob(os.path.join(GOLDEN, "raw_sam", "*.sam")))
     assert len(paths) >= 20
     for p in paths:
         same(cbam.read_alignment_file(p, threads=4), bamio.read_alignment_file(p))

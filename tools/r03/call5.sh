@@ -4,7 +4,7 @@ R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r03_call5; mkdir -p $OUT
 cd $R
 ( time timeout 1500 python -m pytest tests -m gpu -x -q ) > $OUT/pytest_gpu.log 2>&1
 tail -8 $OUT/pytest_gpu.log
-( time timeout 1500 python bench.py ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 1500 python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err
 tail -3 $OUT/bench.err
 python - <<PY
 import json

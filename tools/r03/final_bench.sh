@@ -1,7 +1,7 @@
 #!/bin/bash
 R=$GRAFT_REPO_ROOT; OUT=$R/gpurun_out/r03_final; mkdir -p $OUT
 cd $R
-( time timeout 600 python bench.py ) > $OUT/bench.json 2> $OUT/bench.err
+( time timeout 600 python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err
 tail -4 $OUT/bench.err
 python - <<PY
 import json

@@ -14,7 +14,7 @@ for rep in 1 2; do
 done
 cat $OUT/ab.log; cat $OUT/pytest_gpu.log
 unset COVERM_BENCH_CACHE
-( timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench_err.log ); echo "bench rc $?" >> $OUT/bench_err.log
+( timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.log ); echo "bench rc $?" >> $OUT/bench_err.log
 tail -c 1500 $OUT/bench_line.json; tail -2 $OUT/bench_err.log
 timeout 600 tools/prof_bench.sh r05b > $OUT/prof_bench.log 2>&1
 PROF_PMC=1 timeout 900 tools/prof_ingest.sh r05ing 20000000 > $OUT/prof_ingest.log 2>&1
