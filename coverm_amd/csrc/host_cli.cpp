@@ -74,6 +74,9 @@ struct Args {
     const char *min_covered_fraction = nullptr, *trim_min = "5", *trim_max = "95";
     uint64_t contig_end_exclusion = 75;
     std::string output_format = "dense", output_file, genome_definition, gff, gff_feature_type;
+    std::vector<std::string> genome_fasta_files;                       // genome mode: -f, -d (+ -x), --genome-fasta-list
+    std::string genome_fasta_directory, genome_fasta_list, genome_fasta_extension = "fna";
+    bool have_fasta_files = false, have_fasta_directory = false, have_fasta_list = false, use_full_contig_names = false;
     bool have_gff_feature_type = false;
     bool no_zeros = false, proper_pairs_only = false, exclude_supplementary = false, include_secondary = false;
     bool single_genome = false, have_separator = false, no_stream = false;
@@ -165,6 +168,39 @@ void genome_table(const Run &R, Sample &S, std::vector<uint8_t> &mask) {
         if (it != R.c2g.end()) { S.genome_of_tid[t] = it->second; mask[t] = 1; in++; }
     }
     if (!in) die("Error: There are no found reference sequences that are a part of a genome");
+}
+
+// Genomes from FASTA files (-f / -d -x / --genome-fasta-list; genome_parsing.rs:10-70) into R.genomes / R.c2g, the table
+// --genome-definition fills.  Returns the error message, or "" when resolved.
+std::string resolve_fasta_genomes(Run &R) {
+    const Args &a = R.a;
+    char err[1024] = {0};
+    std::vector<std::string> paths = a.genome_fasta_files;
+    if (a.have_fasta_directory || a.have_fasta_list) {
+        covh_path_list *l = covh_genome_fasta_paths(a.have_fasta_directory ? a.genome_fasta_directory.c_str() : nullptr, a.genome_fasta_extension.c_str(),
+                                                    a.have_fasta_list ? a.genome_fasta_list.c_str() : nullptr, err, sizeof err);
+        if (!l) return err;
+        for (size_t i = 0; i < covh_path_list_count(l); i++) paths.push_back(covh_path_list_get(l, i));
+        covh_path_list_free(l);
+    }
+    std::vector<const char *> pp;
+    for (auto &p : paths) pp.push_back(p.c_str());
+    const double t0 = now();
+    covh_genome_set *gs = covh_genome_set_from_fasta(pp.data(), pp.size(), a.use_full_contig_names ? 1 : 0, std::max(1, a.threads), err, sizeof err);
+    if (!gs) return err;
+    const double t1 = now();
+    for (size_t g = 0; g < covh_genome_set_n_genomes(gs); g++) R.genomes.push_back(covh_genome_set_genome_name(gs, g));
+    const size_t nc = covh_genome_set_n_contigs(gs);
+    R.c2g.reserve(nc);
+    for (size_t i = 0; i < nc; i++) {
+        const char *name; int32_t g;
+        covh_genome_set_contig(gs, i, &name, &g);
+        R.c2g.emplace(name, g);
+    }
+    covh_genome_set_free(gs);
+    if (timing_on())
+        fprintf(stderr, "[coverm-amd] genomes from FASTA: %zu files, %zu contigs, read %.3fs, table %.3fs\n", paths.size(), nc, t1 - t0, now() - t1);
+    return "";
 }
 
 bool is_bgzf(const std::string &path) {
@@ -467,6 +503,8 @@ int run_cli(int argc, char **argv) {
     if (argc < 2 || (strcmp(argv[1], "contig") && strcmp(argv[1], "genome"))) {
         fprintf(stderr, "usage: coverm-amd contig|genome -b <bam>... [-m <methods>...] [options]   (see src/cli.rs of CoverM for the flags; "
                         "engine flags: --device N | --devices a,b,..., --no-stream)\n"
+                        "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
+                        "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n");
         return 2;
     }
@@ -497,6 +535,16 @@ int run_cli(int argc, char **argv) {
         else if (k == "-s" || k == "--separator") { a.separator = val()[0]; a.have_separator = true; }
         else if (k == "--single-genome") a.single_genome = true;
         else if (k == "--genome-definition") a.genome_definition = val();
+        else if (a.mode == "genome" && (k == "-f" || k == "--genome-fasta-files")) {
+            a.have_fasta_files = true;
+            const size_t n0 = a.genome_fasta_files.size();
+            collect(i, a.genome_fasta_files);
+            if (a.genome_fasta_files.size() == n0) die("missing value for " + k);
+        }
+        else if (a.mode == "genome" && (k == "-d" || k == "--genome-fasta-directory")) { a.genome_fasta_directory = val(); a.have_fasta_directory = true; }
+        else if (a.mode == "genome" && (k == "-x" || k == "--genome-fasta-extension")) a.genome_fasta_extension = val();
+        else if (a.mode == "genome" && k == "--genome-fasta-list") { a.genome_fasta_list = val(); a.have_fasta_list = true; }
+        else if (a.mode == "genome" && k == "--use-full-contig-names") a.use_full_contig_names = true;
         else if (k == "--gff") a.gff = val();
         else if (k == "--gff-feature-type") { a.gff_feature_type = val(); a.have_gff_feature_type = true; }
         else if (k == "-t" || k == "--threads") a.threads = (int)parse_uint(k, val(), 65535);
@@ -518,6 +566,19 @@ int run_cli(int argc, char **argv) {
         else if (k == "--no-stream") a.no_stream = true;
         else if (k == "-v" || k == "--verbose" || k == "-q" || k == "--quiet") {}   // logging verbosity: nothing to tune here
         else die("unknown argument " + k);
+    }
+    {   // clap's conflicts_with table for the genome sources (cli.rs:1878-1990); --genome-definition beside --genome-fasta-list is
+        // allowed, and the definition wins (coverm.rs:1262-1294)
+        const std::pair<bool, const char *> src[] = {{a.have_fasta_files, "--genome-fasta-files"}, {a.have_fasta_directory, "--genome-fasta-directory"},
+                                                     {a.have_fasta_list, "--genome-fasta-list"}};
+        const std::pair<bool, const char *> other[] = {{a.have_separator, "--separator"}, {a.single_genome, "--single-genome"}};
+        auto conflict = [](const char *x, const char *y) { die(std::string("the argument '") + x + "' cannot be used with '" + y + "'"); };
+        for (size_t i = 0; i < 3; i++) {
+            if (!src[i].first) continue;
+            for (size_t j = i + 1; j < 3; j++) if (src[j].first) conflict(src[i].second, src[j].second);
+            for (auto &o : other) if (o.first) conflict(src[i].second, o.second);
+            if (i < 2 && !a.genome_definition.empty()) conflict(src[i].second, "--genome-definition");
+        }
     }
     if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
     if (a.devices.empty()) a.devices.push_back(0);
@@ -605,7 +666,8 @@ int run_cli(int argc, char **argv) {
     // ---- genome definition
     std::vector<std::string> &genomes = R.genomes;
     R.by_names = !contig && !a.have_separator && !a.single_genome;
-    if (R.by_names) {
+    const bool fasta_genomes = R.by_names && a.genome_definition.empty() && (a.have_fasta_files || a.have_fasta_directory || a.have_fasta_list);
+    if (R.by_names && !fasta_genomes) {
         if (a.genome_definition.empty()) die("genome mode over BAM files needs --separator, --single-genome or --genome-definition");
         FILE *fh = fopen(a.genome_definition.c_str(), "r");
         if (!fh) die("cannot open " + a.genome_definition);
@@ -650,6 +712,10 @@ int run_cli(int argc, char **argv) {
         cfg.min_percent_identity = f.pid_single; cfg.min_aligned_percent = f.pct_single;
     }
     const size_t nd = a.devices.size(), nb = a.bams.size();
+    // genomes from FASTA files are resolved beside the sessions' start-up; the error of a failed resolution is the run's, before
+    // any ingest, as if it had been resolved first
+    std::future<std::string> fasta_ahead;
+    if (fasta_genomes) fasta_ahead = std::async(std::launch::async, [&R] { return resolve_fasta_genomes(R); });
     if (!a.no_stream && !R.per_gene && !no_gpu_ingest())
         for (size_t i = 0; i < std::min<size_t>(nb, std::max<size_t>(nd, 2)); i++) {      // (the file type is checked by covh_bam_read_header itself)
             const std::string path = a.bams[i];
@@ -679,6 +745,7 @@ int run_cli(int argc, char **argv) {
                 if (rc[d] != COV_OK) { std::lock_guard<std::mutex> lk(em); emsg[d] = cov_last_error(nullptr); }
             });
         for (auto &t : th) t.join();
+        if (fasta_ahead.valid()) { const std::string e = fasta_ahead.get(); if (!e.empty()) die(e); }
         for (size_t d = 0; d < nd; d++) if (rc[d] != COV_OK) die(emsg[d]);
     }
     {

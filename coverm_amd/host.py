@@ -490,3 +490,106 @@ def gene_coverage(names, target_len, genes: Genes, stoit_name: str, records, cfg
     if rc:
         raise HostError(rc, _lib().covh_last_error().decode())
     return ReadsMapped(int(rm.num_mapped_reads), int(rm.num_reads))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; genome_parsing.rs:10-70) through
+# covh_genome_fasta_paths and covh_genome_set_*.
+def _genome_fasta_lib():
+    L = _lib()
+    L.covh_genome_fasta_paths.restype = C.c_void_p
+    L.covh_genome_fasta_paths.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+    L.covh_path_list_count.restype = C.c_size_t
+    L.covh_path_list_count.argtypes = [C.c_void_p]
+    L.covh_path_list_get.restype = C.c_char_p
+    L.covh_path_list_get.argtypes = [C.c_void_p, C.c_size_t]
+    L.covh_path_list_free.argtypes = [C.c_void_p]
+    L.covh_genome_set_from_fasta.restype = C.c_void_p
+    L.covh_genome_set_from_fasta.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    L.covh_genome_set_n_genomes.restype = C.c_size_t
+    L.covh_genome_set_n_genomes.argtypes = [C.c_void_p]
+    L.covh_genome_set_genome_name.restype = C.c_char_p
+    L.covh_genome_set_genome_name.argtypes = [C.c_void_p, C.c_size_t]
+    L.covh_genome_set_n_contigs.restype = C.c_size_t
+    L.covh_genome_set_n_contigs.argtypes = [C.c_void_p]
+    L.covh_genome_set_contig.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]
+    L.covh_genome_set_genome_of_tid.restype = C.c_size_t
+    L.covh_genome_set_genome_of_tid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.covh_genome_set_free.argtypes = [C.c_void_p]
+    return L
+
+
+def _path_list(directory, extension, list_file) -> List[str]:
+    L = _genome_fasta_lib()
+    err = C.create_string_buffer(1024)
+    h = L.covh_genome_fasta_paths(directory.encode() if directory is not None else None,
+                                  extension.encode() if extension is not None else None,
+                                  list_file.encode() if list_file is not None else None, err, 1024)
+    if not h:
+        raise IOError(err.value.decode())
+    try:
+        return [L.covh_path_list_get(h, i).decode() for i in range(L.covh_path_list_count(h))]
+    finally:
+        L.covh_path_list_free(h)
+
+
+def genome_fasta_directory(directory: str, extension: str = "fna") -> List[str]:
+    """-d DIR -x EXT: the regular files of DIR whose name ends in "." + EXT (one leading '.' of EXT accepted), sorted bytewise."""
+    return _path_list(directory, extension, None)
+
+
+def genome_fasta_list(list_file: str) -> List[str]:
+    """--genome-fasta-list FILE: one path per line, a trailing '\\r' stripped, blank lines skipped."""
+    return _path_list(None, None, list_file)
+
+
+class GenomeFastaError(RuntimeError):
+    """What read_genome_fasta_files would have ended the run with (the message is the reference's where it has one)."""
+
+
+class GenomeSet:
+    """GenomesAndContigs (genomes_and_contigs.rs) read from FASTA files: one genome per file, in the order given."""
+
+    def __init__(self, paths: Sequence[str], use_full_contig_names: bool = False, threads: int = 1):
+        L = _genome_fasta_lib()
+        arr = (C.c_char_p * max(1, len(paths)))(*[p.encode() for p in paths])
+        err = C.create_string_buffer(1024)
+        self._h = L.covh_genome_set_from_fasta(arr, len(paths), int(use_full_contig_names), int(threads), err, 1024)
+        if not self._h:
+            raise GenomeFastaError(err.value.decode())
+
+    @property
+    def genomes(self) -> List[str]:
+        L = _genome_fasta_lib()
+        return [L.covh_genome_set_genome_name(self._h, g).decode() for g in range(L.covh_genome_set_n_genomes(self._h))]
+
+    def contigs(self) -> List[tuple]:
+        """(contig name, genome index) in file order."""
+        L = _genome_fasta_lib()
+        out = []
+        for i in range(L.covh_genome_set_n_contigs(self._h)):
+            name, g = C.c_char_p(), C.c_int32()
+            L.covh_genome_set_contig(self._h, i, C.byref(name), C.byref(g))
+            out.append((name.value.decode(), int(g.value)))
+        return out
+
+    def pairs(self) -> List[tuple]:
+        """(genome name, contig name) in file order: the rows of the equivalent genome definition file."""
+        gn = self.genomes
+        return [(gn[g], c) for c, g in self.contigs()]
+
+    def genome_of_tid(self, names: List[str]) -> np.ndarray:
+        """Genome index of each target name (-1 = in no genome), through covh_genome_set_genome_of_tid."""
+        h, keep = _header(names, np.zeros(len(names), np.uint64))
+        out = np.empty(len(names), np.int32)
+        _genome_fasta_lib().covh_genome_set_genome_of_tid(self._h, C.byref(h), out.ctypes.data)
+        del keep
+        return out
+
+    def __del__(self):
+        try:
+            if self._h:
+                _genome_fasta_lib().covh_genome_set_free(self._h)
+                self._h = None
+        except Exception:
+            pass

@@ -282,6 +282,35 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
                        void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
                        size_t n_est, int print_zero_coverage_genes, covh_reads_mapped *reads_mapped_out);
 
+/* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
+ * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.
+ * covh_genome_fasta_paths resolves a directory (directory != NULL: regular files, symlinks followed, whose name ends in
+ * "." + extension; NULL or "fna" by default, one leading '.' accepted; sorted bytewise) or a list file (list_file != NULL: one
+ * path per line, a trailing '\r' stripped, blank lines skipped).  NULL with a message when nothing is found. */
+typedef struct covh_path_list covh_path_list;
+covh_path_list *covh_genome_fasta_paths(const char *directory, const char *extension, const char *list_file, char *err, size_t errcap);
+size_t covh_path_list_count(const covh_path_list *l);
+const char *covh_path_list_get(const covh_path_list *l, size_t i);
+void covh_path_list_free(covh_path_list *l);
+/* One genome per file, in the order given, named by the file stem of the path once its last ".gz" (else ".bz", else ".xz")
+ * and what follows are cut off; its contigs are the files' record ids, cut at the first space unless use_full_contig_names.
+ * Plain text or gzip (by magic bytes); files are read on up to `threads` threads, with the same result for any count.
+ * NULL with the first error a one-file-at-a-time read meets: unreadable, empty or unsupported file, not FASTA, a genome
+ * name from two files, a contig in two records. */
+typedef struct covh_genome_set covh_genome_set;
+covh_genome_set *covh_genome_set_from_fasta(const char *const *paths, size_t n, int use_full_contig_names, int threads, char *err,
+                                            size_t errcap);
+size_t covh_genome_set_n_genomes(const covh_genome_set *s);
+const char *covh_genome_set_genome_name(const covh_genome_set *s, size_t genome);
+size_t covh_genome_set_n_contigs(const covh_genome_set *s);
+/* contig i in file order: its name and the index of its genome */
+void covh_genome_set_contig(const covh_genome_set *s, size_t i, const char **name, int32_t *genome);
+/* genome index of a contig name of `len` bytes; -1 = in no genome */
+int32_t covh_genome_set_genome_of(const covh_genome_set *s, const char *contig, size_t len);
+/* out[tid] = genome index of each target of h (-1 = in no genome); returns how many targets are in a genome */
+size_t covh_genome_set_genome_of_tid(const covh_genome_set *s, const covh_header *h, int32_t *out);
+void covh_genome_set_free(covh_genome_set *s);
+
 /* ---- the orchestrator of `coverm contig|genome --bam-files ...` (src/bin/coverm.rs:1315-1704, 2088-2131, 1539-1628): argv as the
  * coverm-amd binary takes it (argv[1] = "contig" | "genome", the reference's flag names, plus --device N / --devices a,b,...
  * and --no-stream).  Writes the table to --output-file or stdout; returns the process exit code (1 after printing an error). */
