@@ -4,6 +4,7 @@
 // entry point fails with COV_ERR_HIP.
 #include "pileup_kernels.hip.h"
 #include "prep_lean.hip.h"
+#include "genome_kernels.hip.h"
 #include "ingest_kernels.hip.h"
 
 #include <algorithm>
@@ -38,6 +39,8 @@ static_assert(sizeof(cov_contig_stats) == 128 && offsetof(cov_contig_stats, sum_
               offsetof(cov_contig_stats, hist_off) == 120, "cov_contig_stats layout");
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
+static_assert(sizeof(cov_genome_stats) == 24 && sizeof(cov_genome_stats) == sizeof(covk::DevGenomeStats) && offsetof(cov_genome_stats, genome_len) == offsetof(covk::DevGenomeStats, genome_len) &&
+              offsetof(cov_genome_stats, any_nonzero) == offsetof(covk::DevGenomeStats, any_nonzero), "cov_genome_stats mirrors the device struct");
 static_assert(sizeof(cov_estimator) == sizeof(covk::DevEstimator) && offsetof(cov_estimator, contig_end_exclusion) == offsetof(covk::DevEstimator, excl) &&
               offsetof(cov_estimator, trim_max) == offsetof(covk::DevEstimator, trim_max) && COV_EST_MAX == covk::EST_MAX && COV_EST_ANIR == covk::EST_ANIR, "cov_estimator mirrors the device struct");
 
@@ -123,6 +126,17 @@ struct cov_session {
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
     bool have_mask = false;
+    // cov_set_genomes: the table genome -> targets (CSR, ascending tid; rows cut into segments of GENOME_SEG, genome_kernels.hip.h), the
+    // genomes' accumulators and merged histogram, and the block the host fetches: [cov_genome_stats x n_genomes][floats x n_genomes x est.n]
+    bool have_genomes = false, gen_valid = false;
+    bool lean_finish = false;      // inside cov_finish_genomes: order and error verdict on the device, no per-contig block to the host
+    bool in_spill = false;         // the pass a spill runs over a partial store: no genome entries
+    DevBuf<u64> d_order;           // k_order_*: [0] first record that breaks the order (~0: none), [1 ..] per-block maxima
+    uint32_t n_genomes = 0, n_gseg = 0;
+    DevBuf<u32> d_grow, d_gtids, d_gseg_genome, d_gseg_start;
+    DevBuf<DevGenome> d_genomes;
+    DevBuf<u64> d_ghist, d_ghist_top;
+    DevBuf<uint8_t> d_gout; uint8_t *h_gout = nullptr; size_t h_gout_cap = 0;
     // results of the device pipeline live in ONE block [DevGlobal][DevContig x n_targets] (d_res): one DMA brings them to
     // the host, and cov_gather sends the same block over RCCL.  d_glob / d_ctg are views into it (never freed themselves).
     DevBuf<uint8_t> d_res;
@@ -264,7 +278,8 @@ size_t result_block_bytes(u32 n_targets) { return sizeof(DevGlobal) + (size_t)st
 // 350 MB at 2 M contigs and four estimators, 0.06 s of hipHostMalloc that used to sit in the sample's one cov_finish.  cov_set_targets starts
 // it on a helper thread (the ingest or the pushes pass meanwhile); cov_finish takes what the helper got, or allocates as before.
 static size_t result_host_bytes(const cov_session *s, u32 nT) {
-    return result_block_bytes(nT) + (size_t)std::max<u32>(nT, 1) * std::max<u32>(s->est.n, 1u) * sizeof(float);
+    // (with a target mask no per-contig floats come back — the entries are genomes — so the block does not grow with the estimators)
+    return result_block_bytes(nT) + (size_t)std::max<u32>(nT, 1) * (s->have_mask ? 1u : std::max<u32>(s->est.n, 1u)) * sizeof(float);
 }
 static void result_host_take(cov_session *s) {
     if (!s->h_res_prep.valid()) return;
@@ -566,6 +581,8 @@ void cov_destroy(cov_session *s) {
     (void)hipSetDevice(s->cfg.device);
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->d_tlen.release(); s->d_tile_contig.release(); s->d_tile_start.release(); s->d_mask.release();
+    s->d_grow.release(); s->d_gtids.release(); s->d_gseg_genome.release(); s->d_gseg_start.release(); s->d_genomes.release(); s->d_ghist.release(); s->d_ghist_top.release(); s->d_order.release();
+    s->d_gout.release(); if (s->h_gout) (void)hipHostFree(s->h_gout); s->h_gout = nullptr;
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
     s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
     s->d_cx_list.release(); s->d_cx_cnt.release(); s->d_cx_cur.release(); s->d_cx_scan.release(); s->d_cx_top.release(); s->d_cx_runs.release();
@@ -612,6 +629,14 @@ void cov_destroy(cov_session *s) {
     delete s;
 }
 
+// Genomes off.  Estimators that were valid for genome entries only (ANIr over the not-supplementary identity sum: the per-contig
+// k_estimate reads the primary-read sum, which such a session never computes) are dropped with them: set them again.
+static void genomes_off(cov_session *s) {
+    if (s->have_genomes && (s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY))
+        for (uint32_t k = 0; k < s->est.n; k++)
+            if (s->est.e[k].kind == COV_EST_ANIR) { s->est = EstParams{}; s->est_valid = false; break; }
+    s->have_genomes = false; s->gen_valid = false;
+}
 cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *target_len) {
     if (!s || (!target_len && n_targets)) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
@@ -654,6 +679,7 @@ cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *t
     }
     HIPCHK(hipStreamSynchronize(s->stream));
     s->have_mask = false;
+    genomes_off(s);
     s->finished = false;
     if (n_targets >= 65536u && !s->h_res_prep.valid() && result_host_bytes(s, n_targets) > s->h_res_cap) {
         const size_t need = result_host_bytes(s, n_targets);
@@ -667,9 +693,15 @@ cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *t
     return COV_OK;
 }
 
+static cov_status set_target_mask_(cov_session *s, const uint8_t *mask);
 cov_status cov_set_target_mask(cov_session *s, const uint8_t *mask) {
     if (!s) return COV_ERR_INVALID_ARG;
+    genomes_off(s);
+    return set_target_mask_(s, mask);
+}
+static cov_status set_target_mask_(cov_session *s, const uint8_t *mask) {
     HIPCHK(hipSetDevice(s->cfg.device));
+    s->gen_valid = false;
     if (!mask) { s->have_mask = false; s->h_mask.clear(); return COV_OK; }
     s->h_mask.assign(mask, mask + s->n_targets);
     HIPCHK(s->d_mask.reserve(std::max<size_t>(1, s->n_targets), s->stream));
@@ -677,6 +709,58 @@ cov_status cov_set_target_mask(cov_session *s, const uint8_t *mask) {
     HIPCHK(hipStreamSynchronize(s->stream));
     s->have_mask = true;
     s->finished = false;
+    return COV_OK;
+}
+
+// The table genome -> targets: a counting sort of the targets by genome (stable, so a row holds ascending tids), rows cut into segments.
+// Built on the host at every call (cov_set_targets drops it, so once per sample in the CLI), like the tile tables of cov_set_targets, and
+// kept on the device.
+cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_t n_genomes) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (!genome_of_tid || n_genomes == 0) return cov_set_target_mask(s, nullptr);
+    const u32 nT = s->n_targets;
+    for (uint32_t k = 0; k < s->est.n; k++)
+        if (s->est.e[k].kind == COV_EST_ANIR && (s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY)) {
+            s->err = "cov_set_genomes: ANIr of a genome needs COV_WANT_IDENTITY with the not-supplementary sum (genome.rs:220)"; return COV_ERR_INVALID_ARG;
+        }
+    std::vector<uint8_t> mask(nT);
+    std::vector<u32> row((size_t)n_genomes + 1, 0);
+    for (u32 t = 0; t < nT; t++) {
+        const int32_t g = genome_of_tid[t];
+        if (g < -1 || (g >= 0 && (uint32_t)g >= n_genomes)) { s->err = "cov_set_genomes: genome index outside [-1, n_genomes)"; return COV_ERR_INVALID_ARG; }
+        mask[t] = g >= 0;
+        if (g >= 0) row[(size_t)g + 1]++;
+    }
+    for (uint32_t g = 0; g < n_genomes; g++) row[g + 1] += row[g];
+    std::vector<u32> tids(std::max<u32>(row[n_genomes], 1u)), cur(row.begin(), row.end() - 1), seg_genome, seg_start;
+    for (u32 t = 0; t < nT; t++) if (genome_of_tid[t] >= 0) tids[cur[genome_of_tid[t]]++] = t;
+    for (uint32_t g = 0; g < n_genomes; g++)
+        for (u32 i = row[g]; i < row[g + 1]; i += GENOME_SEG) { seg_genome.push_back(g); seg_start.push_back(i); }
+    const cov_status m = set_target_mask_(s, mask.data());
+    if (m != COV_OK) return m;
+    const size_t n_seg = seg_genome.size();
+    hipStream_t st = s->stream;
+    HIPCHK(s->d_grow.reserve(row.size(), st)); HIPCHK(s->d_gtids.reserve(tids.size(), st));
+    HIPCHK(s->d_gseg_genome.reserve(std::max<size_t>(1, n_seg), st)); HIPCHK(s->d_gseg_start.reserve(std::max<size_t>(1, n_seg), st));
+    HIPCHK(s->d_genomes.reserve(n_genomes, st));
+    HIPCHK(s->d_ghist_top.reserve((size_t)(n_genomes + 1023u) / 1024u + 1, st));
+    HIPCHK(s->d_gout.reserve((size_t)n_genomes * (sizeof(cov_genome_stats) + COV_EST_MAX * sizeof(float)), st));
+    HIPCHK(hipMemcpyAsync(s->d_grow.p, row.data(), row.size() * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(s->d_gtids.p, tids.data(), tids.size() * 4, hipMemcpyHostToDevice, st));
+    if (n_seg) {
+        HIPCHK(hipMemcpyAsync(s->d_gseg_genome.p, seg_genome.data(), n_seg * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->d_gseg_start.p, seg_start.data(), n_seg * 4, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    const size_t need = (size_t)n_genomes * (sizeof(cov_genome_stats) + COV_EST_MAX * sizeof(float));
+    if (need > s->h_gout_cap) {
+        if (s->h_gout) (void)hipHostFree(s->h_gout);
+        s->h_gout = nullptr; s->h_gout_cap = 0;
+        HIPCHK(hipHostMalloc((void **)&s->h_gout, need, hipHostMallocDefault));
+        s->h_gout_cap = need;
+    }
+    s->n_genomes = n_genomes; s->n_gseg = (uint32_t)n_seg;
+    s->have_genomes = true;
     return COV_OK;
 }
 
@@ -749,7 +833,7 @@ cov_status cov_reset(cov_session *s) {
         if (a != COV_OK) s->err.clear();
     }
     s->adopted = false; s->n_records = 0; s->n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->mates_valid = 0;
-    s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing_rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false;
+    s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing_rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
 
@@ -762,7 +846,7 @@ static cov_status convert_results(cov_session *s, const DevGlobal &G, const DevC
                                   cov_summary *summary, int64_t min_ok_tid = -1, uint64_t rec_base = 0) {
     const u32 nT = s->n_targets;
     const bool want_hist = s->cfg.want & COV_WANT_HIST;
-    if (G.internal_error) { s->err = "internal error: depth exceeded its proven bound"; return COV_ERR_STATE; }
+    if (G.internal_error) { s->err = "internal error: depth or histogram size exceeded its proven bound"; return COV_ERR_STATE; }
     // errors in file order (the reference panics at the first offending record)
     uint64_t err_rec = ~0ull; int err_code = 0;
     if (G.first_error != ~0ull) { err_rec = G.first_error >> 8; err_code = (int)(G.first_error & 0xff); }
@@ -870,6 +954,35 @@ static cov_status convert_results(cov_session *s, const DevGlobal &G, const DevC
     return COV_OK;
 }
 
+// convert_results without the per-contig block (cov_finish_genomes): the same verdicts in the same precedence — internal error, the order
+// rule when it breaks no later than the first erroring record, that record's error — from DevGlobal and k_order_check's word.
+static cov_status verdict_results(cov_session *s, const DevGlobal &G, uint64_t unsorted_at, uint64_t n_records, cov_summary *summary) {
+    if (G.internal_error) { s->err = "internal error: depth or histogram size exceeded its proven bound"; return COV_ERR_STATE; }
+    uint64_t err_rec = ~0ull; int err_code = 0;
+    if (G.first_error != ~0ull) { err_rec = G.first_error >> 8; err_code = (int)(G.first_error & 0xff); }
+    if (unsorted_at != ~0ull && unsorted_at <= err_rec) {
+        s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
+        return COV_ERR_UNSORTED;
+    }
+    if (err_code) {
+        char b[256];
+        const char *what = err_code == 2 ? "Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format"
+                         : err_code == 3 ? "Unexpected data type of NM aux tag"
+                         : err_code == 4 ? "aligned block starts at or beyond the end of its reference sequence"
+                         : err_code == 7 ? "record refers to a reference id outside the header (Corrupt BAM file?)"
+                                         : "invalid CIGAR operation";
+        snprintf(b, sizeof b, "%s (record %llu)", what, (unsigned long long)err_rec);
+        s->err = b;
+        return (cov_status)err_code;
+    }
+    if (summary) {
+        uint64_t prim = 0, cons = 0;
+        for (u32 k = 0; k < COUNTER_SLOTS * 8; k++) { prim += G.prim_slots[k]; cons += G.cons_slots[k]; }
+        summary->num_detected_primary_alignments = prim; summary->n_records = n_records; summary->n_considered = cons; summary->hist_total = 0;
+    }
+    return COV_OK;
+}
+
 static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summary *summary, bool &again);
 
 // The pipeline over what the store holds.  The buckets of long-CIGAR records are sized optimistically: a pass that finds them too
@@ -893,9 +1006,21 @@ cov_status cov_finish(cov_session *s, cov_contig_stats *stats, cov_summary *summ
     return st;
 }
 
+cov_status cov_finish_genomes(cov_session *s, cov_summary *summary) {
+    covr::Range rr("cov_finish_genomes");
+    if (!s) return COV_ERR_INVALID_ARG;
+    s->merged_valid = false;
+    if (s->spill.active) { s->err = "cov_finish_genomes: part of the sample's contigs left the bounded record store: cov_finish, and aggregate on the host"; return COV_ERR_STATE; }
+    s->lean_finish = true;
+    const cov_status st = finish_store(s, nullptr, summary);
+    s->lean_finish = false;
+    return st;
+}
+
 static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summary *summary, bool &again) {
     again = false;
-    if (!s || (!stats && s->n_targets)) return COV_ERR_INVALID_ARG;
+    if (!s || (!stats && s->n_targets && !s->lean_finish)) return COV_ERR_INVALID_ARG;
+    const bool lean = s->lean_finish;
     s->depth_all_valid = false;
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
@@ -905,7 +1030,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     const bool want_hist = s->cfg.want & COV_WANT_HIST, want_id = s->cfg.want & COV_WANT_IDENTITY;
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
     bool compacted = false;      // the compact histogram was built by this pass (else: by the first cov_fetch_hist)
-    s->est_valid = false;
+    s->est_valid = false; s->gen_valid = false;
     s->ev_fresh = -1;
 
     HIPCHK(s->d_runs.reserve(std::max<size_t>(1, R), st));
@@ -1097,12 +1222,12 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
             s->hist_fetch_seen = false;
         }
     }
-    // (with a target mask the entries are genomes, aggregated on the host: masked-out contigs have no bins in the arena, and nobody may fetch
-    // per-contig floats — no k_estimate launch, no floats in the copy)
+    // (with a target mask the entries are genomes — aggregated below when cov_set_genomes gave their table, else by the caller: masked-out
+    // contigs have no bins in the arena, and nobody may fetch per-contig floats — no k_estimate launch, no floats in the copy)
     const size_t block = result_block_bytes(nT), nf = s->have_mask ? 0 : (size_t)nT * s->est.n;
     {
         result_host_take(s);
-        const size_t need = result_host_bytes(s, nT);
+        const size_t need = lean ? sizeof(DevGlobal) + sizeof(DevContig) : result_host_bytes(s, nT);      // (lean: DevGlobal + the order word)
         if (need > s->h_res_cap) {
             if (s->h_res) (void)hipHostFree(s->h_res);
             s->h_res = nullptr; s->h_res_cap = 0;
@@ -1125,6 +1250,52 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
         time_end(s, COV_K_ESTIMATE);
         HIPCHK(hipGetLastError());
     }
+    // genome entries (cov_set_genomes): reduce the contigs' accumulators over each genome's row, merge their histograms, evaluate.  Not
+    // after a spill: the contigs that left the store are on the host, the caller aggregates there.
+    const bool genomes = s->have_genomes && s->est.n != 0 && !s->spill.active && !s->in_spill;
+    if (lean && !genomes) { s->err = "cov_finish_genomes: cov_set_genomes and cov_set_estimators first, and no spill of the bounded record store (cov_finish then)"; return COV_ERR_STATE; }
+    if (genomes) {
+        const u32 nG = s->n_genomes, n_seg = s->n_gseg;
+        GenomeTable gt{s->d_grow.p, s->d_gtids.p, s->d_gseg_genome.p, s->d_gseg_start.p, nG, n_seg};
+        const u64 excl = s->cfg.contig_end_exclusion;
+        const u64 ghist_cap = (u64)R + nT + 1;      // the genomes' bins are at most the contigs' (every genome bin is some contig's bin)
+        if (want_hist) HIPCHK(s->d_ghist.reserve((size_t)ghist_cap, st));
+        time_begin(s, COV_K_GENOME);
+        hipLaunchKernelGGL(k_genome_init, dim3((nG + 255u) / 256u), dim3(256), 0, st, s->d_genomes.p, nG);
+        if (n_seg) hipLaunchKernelGGL(k_genome_reduce, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl, gt, s->d_genomes.p);
+        if (want_id && !(s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY))
+            hipLaunchKernelGGL(k_genome_identity, dim3(nG), dim3(64), 0, st, (const DevContig *)s->d_ctg.p, gt, s->d_genomes.p);
+        if (want_hist) {
+            const u32 gb = (nG + 1023u) / 1024u;
+            u64 *total = s->d_ghist_top.p + gb;
+            hipLaunchKernelGGL(k_genome_hist_sum, dim3(gb), dim3(1024), 0, st, (const DevGenome *)s->d_genomes.p, nG, s->d_ghist_top.p);
+            hipLaunchKernelGGL(k_genome_hist_off, dim3(gb), dim3(1024), 0, st, s->d_genomes.p, nG, (const u64 *)s->d_ghist_top.p, total, ghist_cap, s->d_glob.p);
+            hipLaunchKernelGGL(k_zero_u64, dim3(1024), dim3(256), 0, st, s->d_ghist.p, (const u64 *)total, ghist_cap);
+            if (n_seg && R && s->n_tiles)
+                hipLaunchKernelGGL(k_genome_hist_merge, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl,
+                                   (const u32 *)s->d_arena.p, gt, (const DevGenome *)s->d_genomes.p, s->d_ghist.p, ghist_cap);
+        }
+        DevGenomeStats *gstats = reinterpret_cast<DevGenomeStats *>(s->d_gout.p);
+        float *gest = reinterpret_cast<float *>(s->d_gout.p + (size_t)nG * sizeof(DevGenomeStats));
+        if (nG >= 65536u)
+            hipLaunchKernelGGL(k_genome_estimate_lanes, dim3((nG + 255u) / 256u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
+        else
+            hipLaunchKernelGGL(k_genome_estimate, dim3((nG + 3u) / 4u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
+        time_end(s, COV_K_GENOME);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(s->h_gout, s->d_gout.p, (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float)), hipMemcpyDeviceToHost, st));
+    }
+    if (lean) {
+        // the order rule of convert_results on the device: the first considered record of a seen contig must not lie before the last one of
+        // any seen contig in front of it (contig.rs:129-132); the verdict is one word behind DevGlobal
+        const u32 ob = (nT + 1023u) / 1024u;
+        HIPCHK(s->d_order.reserve((size_t)ob + 2, st));
+        hipLaunchKernelGGL(k_order_max, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
+        hipLaunchKernelGGL(k_order_check, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(s->h_res + sizeof(DevGlobal), s->d_order.p, 8, hipMemcpyDeviceToHost, st));
+    } else
     // one copy: the result block and, behind it, the estimators' floats
     HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal) + (size_t)nT * sizeof(DevContig) + (nf ? (block - sizeof(DevGlobal) - (size_t)nT * sizeof(DevContig)) + nf * sizeof(float) : 0),
                           hipMemcpyDeviceToHost, st));
@@ -1158,12 +1329,20 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
         s->algo_bytes = (uint64_t)R * 24 + ncig * 4 + (uint64_t)nT * sizeof(DevContig);
     }
 
+    if (lean) {
+        u64 unsorted_at; memcpy(&unsorted_at, s->h_res + sizeof(DevGlobal), 8);
+        const cov_status cst = verdict_results(s, s->h_glob, unsorted_at, R, summary);
+        if (cst != COV_OK) return cst;
+        s->last_chist_total = 0; s->hist_compacted = false; s->est_valid = false; s->gen_valid = true; s->finished = true;
+        return COV_OK;
+    }
     const cov_status cst = convert_results(s, s->h_glob, s->h_ctg, R, stats, summary, s->spill.inflight, s->spill.records);
     if (cst != COV_OK) return cst;
     s->last_chist_total = 0;
     if (want_hist) for (u32 c = 0; c < nT; c++) s->last_chist_total += stats[c].hist_len;      // (the host laid the compact histogram out: convert_results)
     s->hist_compacted = compacted;
     s->est_valid = s->est.n != 0 && !s->have_mask;
+    s->gen_valid = genomes;
     s->finished = true;
     return COV_OK;
 }
@@ -1198,7 +1377,10 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
     const bool want_hist = s->cfg.want & COV_WANT_HIST;
     std::vector<cov_contig_stats> st(nT);
     cov_summary sm{};
+    s->in_spill = true;
+    const bool lean_was = s->lean_finish; s->lean_finish = false;
     cov_status rc = finish_store(s, st.data(), &sm);
+    s->in_spill = false; s->lean_finish = lean_was;
     if (rc != COV_OK) return rc;
     const u64 R = s->n_records;
     cov_session::Spill &S = s->spill;
@@ -1214,7 +1396,7 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
         if ((int64_t)c == cstar || !st[c].n_pass) continue;
         if (S.have[c]) { s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)"; return COV_ERR_UNSORTED; }
         S.stats[c] = st[c]; S.ctg[c] = s->h_ctg[c]; S.have[c] = 1;
-        if (s->est.n) {
+        if (s->est.n && !s->have_mask) {
             if (s->spill_est.size() != (size_t)nT * s->est.n) s->spill_est.assign((size_t)nT * s->est.n, 0.0f);
             memcpy(&s->spill_est[(size_t)c * s->est.n], s->h_estf + (size_t)c * s->est.n, s->est.n * sizeof(float));
         }
@@ -2262,14 +2444,40 @@ cov_status cov_set_estimators(cov_session *s, const cov_estimator *est, uint32_t
             return COV_ERR_INVALID_ARG;
         }
         if (kind == COV_EST_TRIMMED_MEAN && !(s->cfg.want & COV_WANT_HIST)) { s->err = "cov_set_estimators: a trimmed mean needs COV_WANT_HIST"; return COV_ERR_INVALID_ARG; }
-        if (kind == COV_EST_ANIR && (!(s->cfg.want & COV_WANT_IDENTITY) || (s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY))) {
+        if (kind == COV_EST_ANIR && s->have_genomes) {      // genome entries take the not-supplementary sum (genome.rs:220)
+            if (!(s->cfg.want & COV_WANT_IDENTITY) || (s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY)) {
+                s->err = "cov_set_estimators: ANIr of a genome needs COV_WANT_IDENTITY with the not-supplementary sum"; return COV_ERR_INVALID_ARG;
+            }
+        } else if (kind == COV_EST_ANIR && (!(s->cfg.want & COV_WANT_IDENTITY) || (s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY))) {
             s->err = "cov_set_estimators: ANIr needs COV_WANT_IDENTITY with the primary-read sum"; return COV_ERR_INVALID_ARG;
         }
     }
     s->est = EstParams{};
     for (uint32_t k = 0; k < n_est; k++) memcpy(&s->est.e[k], &est[k], sizeof(cov_estimator));
     s->est.n = n_est;
-    s->est_valid = false;
+    s->est_valid = false; s->gen_valid = false;
+    return COV_OK;
+}
+
+static cov_status genome_fetch_ready(cov_session *s, const char *what) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->spill.active) { s->err = std::string(what) + ": part of the sample's contigs left the bounded record store: aggregate cov_finish's per-contig results on the host"; return COV_ERR_STATE; }
+    if (!s->finished || !s->gen_valid) { s->err = std::string(what) + ": cov_set_genomes and cov_set_estimators, then cov_finish"; return COV_ERR_STATE; }
+    return COV_OK;
+}
+cov_status cov_fetch_genome_estimates(cov_session *s, float *out) {
+    const cov_status r = genome_fetch_ready(s, "cov_fetch_genome_estimates");
+    if (r != COV_OK) return r;
+    const size_t nf = (size_t)s->n_genomes * s->est.n;
+    if (nf && !out) return COV_ERR_INVALID_ARG;
+    if (nf) memcpy(out, s->h_gout + (size_t)s->n_genomes * sizeof(cov_genome_stats), nf * sizeof(float));
+    return COV_OK;
+}
+cov_status cov_fetch_genome_stats(cov_session *s, cov_genome_stats *out) {
+    const cov_status r = genome_fetch_ready(s, "cov_fetch_genome_stats");
+    if (r != COV_OK) return r;
+    if (!out) return COV_ERR_INVALID_ARG;
+    memcpy(out, s->h_gout, (size_t)s->n_genomes * sizeof(cov_genome_stats));
     return COV_OK;
 }
 

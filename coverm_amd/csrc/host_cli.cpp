@@ -111,6 +111,8 @@ struct Sample {
     std::vector<cov_contig_stats> stats;
     std::vector<uint64_t> hist;
     std::vector<float> estimates;      // calculate_coverage of every contig, evaluated on the device (Run::dev_est): n_targets x estimators
+    // Run::dev_genome: the genomes aggregated and evaluated on the device — n_genomes x estimators floats and one cov_genome_stats per genome
+    std::vector<float> genome_estimates; std::vector<cov_genome_stats> genome_stats; bool genome_dev = false, any_seen = false;
     uint64_t prim = 0, n_records = 0;
     covh_reads_mapped gene_rm{0, 0};
     double t_open = 0, t_ingest = 0, t_finish = 0; uint64_t peak_bytes = 0; bool streamed = false, device_ingest = false;
@@ -134,6 +136,8 @@ struct Run {
     bool contig = true, by_names = false, per_gene = false, fs = false, fp = false;
     std::vector<covh_estimator> est;
     bool dev_est = false;      // `coverm contig` with estimators the device evaluates (cov_set_estimators): no per-contig finalisation, no histogram fetch on the host
+    // contig-names genome scan with estimators the device evaluates (cov_set_genomes): no host pass over the contigs, no histogram fetch
+    bool dev_genome = false;
     uint32_t want = 0;
     cov_config cfg{};
     std::vector<std::string> genomes;
@@ -168,6 +172,15 @@ void genome_table(const Run &R, Sample &S, std::vector<uint8_t> &mask) {
         if (it != R.c2g.end()) { S.genome_of_tid[t] = it->second; mask[t] = 1; in++; }
     }
     if (!in) die("Error: There are no found reference sequences that are a part of a genome");
+}
+
+// The contig-names scan's participation of one BAM's references: the genome table for the device (Run::dev_genome), else the mask alone
+void set_genomes_or_mask(Run &R, cov_session *s, const Sample &S, const std::vector<uint8_t> &mask) {
+    if (!R.dev_genome) { check(s, cov_set_target_mask(s, mask.data())); return; }
+    const double t0 = now();
+    check(s, cov_set_genomes(s, S.genome_of_tid.data(), (uint32_t)R.genomes.size()));
+    check(s, cov_set_estimators(s, reinterpret_cast<const cov_estimator *>(R.est.data()), (uint32_t)R.est.size()));
+    if (timing_on()) fprintf(stderr, "[coverm-amd] %s: genome table to the device (cov_set_genomes) %.4fs\n", S.stoit.c_str(), now() - t0);
 }
 
 // Genomes from FASTA files (-f / -d -x / --genome-fasta-list; genome_parsing.rs:10-70) into R.genomes / R.c2g, the table
@@ -221,7 +234,31 @@ void fetch_results(Run &R, cov_session *s, Sample &S, const cov_summary &summ) {
     if (R.dev_est) {
         S.estimates.resize(S.tlen.size() * R.est.size());
         check(s, cov_fetch_estimates(s, S.estimates.data()));
-    } else if (R.want & COV_WANT_HIST) { S.hist.resize(summ.hist_total); check(s, cov_fetch_hist(s, S.hist.data())); }
+        return;
+    }
+    if (R.dev_genome && cov_store_spills(s) == 0) {
+        S.genome_estimates.resize(R.genomes.size() * R.est.size()); S.genome_stats.resize(R.genomes.size());
+        check(s, cov_fetch_genome_estimates(s, S.genome_estimates.data()));
+        check(s, cov_fetch_genome_stats(s, S.genome_stats.data()));
+        S.genome_dev = true; S.any_seen = summ.n_considered != 0;
+        if (timing_on())
+            fprintf(stderr, "[coverm-amd] %s: genome results from the device: %zu genomes x %zu estimators, %zu bytes\n", S.stoit.c_str(), R.genomes.size(), R.est.size(),
+                    S.genome_estimates.size() * sizeof(float) + S.genome_stats.size() * sizeof(cov_genome_stats));
+        return;
+    }
+    // (Run::dev_genome after a spill of the bounded record store: finished contigs are on the host, and so is the aggregation)
+    if (R.want & COV_WANT_HIST) {
+        S.hist.resize(summ.hist_total); check(s, cov_fetch_hist(s, S.hist.data()));
+        if (timing_on()) fprintf(stderr, "[coverm-amd] %s: histogram fetch: %llu bins, %llu bytes\n", S.stoit.c_str(), (unsigned long long)summ.hist_total, (unsigned long long)summ.hist_total * 8ull);
+    }
+}
+
+// cov_finish of one sample.  Run::dev_genome: the genome results are all the host takes, so the per-contig block stays on the device
+// (cov_finish_genomes) — unless the bounded record store spilled: finished contigs are on the host then, and so is the aggregation.
+void finish_sample(Run &R, cov_session *s, Sample &S, cov_summary &summ) {
+    if (R.dev_genome && cov_store_spills(s) == 0) { check(s, cov_finish_genomes(s, &summ)); return; }
+    S.stats.resize(S.tlen.size());
+    check(s, cov_finish(s, S.stats.data(), &summ));
 }
 
 // Decode + push + finish of one BAM (or one tid span of it) on one session.  Leaves the session finished.
@@ -259,13 +296,13 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         set_header(S, covh_bam_header_n_targets(hd), [&](uint32_t t) { return covh_bam_header_target_name(hd, t); },
                    [&](uint32_t t) { return covh_bam_header_target_len(hd, t); });
         check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); check(s, cov_set_target_mask(s, mask.data())); }
+        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
         S.t_open = now() - t0;
         uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
         // (an assembly's statistics are 128 B x millions of contigs: the array is obtained and touched beside the ingest, not behind it)
         std::future<void> stats_ahead;
-        if (S.tlen.size() >= 65536) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
+        if (S.tlen.size() >= 65536 && !R.dev_genome) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
         struct StatsWait { std::future<void> &f; ~StatsWait() { if (f.valid()) f.get(); } } stats_wait{stats_ahead};
         int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, span_index, span_count, &nrec, tm, err, sizeof err);
         if (stats_ahead.valid()) stats_ahead.get();
@@ -292,9 +329,8 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
                         S.stoit.c_str(), span_index, span_count, tm[4], tm[0], tm[1], tm[5], tm[6], tm[2], tm[3], (unsigned long long)nrec,
                         tm[7] == 2 ? "the mapped file (registered up front)" : tm[7] == 1 ? "the mapped file" : tm[7] == 3 ? "staging slots (copied from the mapping)" : "staging slots (pread)");
             S.t_ingest = now() - t0;
-            S.stats.resize(S.tlen.size());
             cov_summary summ;
-            check(s, cov_finish(s, S.stats.data(), &summ));
+            finish_sample(R, s, S, summ);
             fetch_results(R, s, S, summ);
             S.prim = R.fp ? pair_prim : summ.num_detected_primary_alignments;      // filter.rs:129-131 counts every primary record of the input
             S.t_finish = now() - t0 - S.t_ingest;
@@ -312,7 +348,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         set_header(S, covh_bam_stream_n_targets(st), [&](uint32_t t) { return covh_bam_stream_target_name(st, t); },
                    [&](uint32_t t) { return covh_bam_stream_target_len(st, t); });
         check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); check(s, cov_set_target_mask(s, mask.data())); }
+        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
         S.t_open = now() - t0;
         cov_batch b;
         int rc;
@@ -327,9 +363,8 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
                     S.stoit.c_str(), span_index, span_count, t[0], t[1], t[2], t[3], t[4], (unsigned long long)S.n_records, S.peak_bytes / 1e6);
         }
         S.t_ingest = now() - t0;
-        S.stats.resize(S.tlen.size());
         cov_summary summ;
-        check(s, cov_finish(s, S.stats.data(), &summ));
+        finish_sample(R, s, S, summ);
         fetch_results(R, s, S, summ);
         S.prim = summ.num_detected_primary_alignments;
         S.t_finish = now() - t0 - S.t_ingest;
@@ -349,7 +384,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         set_header(S, covh_bam_header_n_targets(hd), [&](uint32_t t) { return covh_bam_header_target_name(hd, t); },
                    [&](uint32_t t) { return covh_bam_header_target_len(hd, t); });
         check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); check(s, cov_set_target_mask(s, mask.data())); }
+        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
         check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
         uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, 0, 1, &nrec, tm, err, sizeof err);
@@ -414,13 +449,12 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
     S.t_open = now() - t0;
     if (!have_records) {
         check(s, cov_set_targets(s, nt, S.tlen.data()));
-        if (R.by_names) check(s, cov_set_target_mask(s, mask.data()));
+        if (R.by_names) set_genomes_or_mask(R, s, S, mask);
         check(s, cov_push_batch(s, &batch));
     }
     S.t_ingest = now() - t0;
-    S.stats.resize(nt);
     cov_summary summ;
-    check(s, cov_finish(s, S.stats.data(), &summ));
+    finish_sample(R, s, S, summ);
     fetch_results(R, s, S, summ);
     if (!prim_from_host) S.prim = summ.num_detected_primary_alignments;
     if (R.per_gene) {   // genes.rs:182-344: per-gene reductions over this sample's depth, while the session holds it
@@ -757,6 +791,14 @@ int run_cli(int argc, char **argv) {
         R.dev_est = ok;
         if (ok) for (size_t d = 0; d < nd; d++) check(sess[d], cov_set_estimators(sess[d], reinterpret_cast<const cov_estimator *>(est.data()), (uint32_t)est.size()));
     }
+    {
+        // ... and for the contig-names genome scan (one entry per genome, cov_set_genomes) under the same conditions; not with --gff, not when
+        // a file is cut into spans over several devices (each rank would hold a part of every genome).  The estimators are set per sample,
+        // behind the genome table (ANIr takes the not-supplementary identity sum there).
+        bool ok = R.by_names && !R.per_gene && !(nd > 1 && nb < nd) && !getenv("COVERM_HOST_ESTIMATES") && !est.empty() && est.size() <= COV_EST_MAX;
+        for (const covh_estimator &e : est) ok = ok && e.kind != COVH_TPM && e.kind != COVH_PILEUP_COUNTS;
+        R.dev_genome = ok;
+    }
     const double t_sessions = now();
     covh_bam_set_pinned(1);
     // (measured, profiles/r03_tail_variants.log: releasing the staging slots beside the last rounds shortens the exit by ~0.03 s and
@@ -899,7 +941,12 @@ int run_cli(int argc, char **argv) {
         else if (a.have_separator || a.single_genome)
             rc = covh_genome_coverage_separator(&hdr, &hs, 1, (uint8_t)(a.single_genome ? '0' : a.separator), taker, !a.no_zeros, est.data(), est.size(),
                                                 a.single_genome, &rm[bi]);
-        else {
+        else if (S.genome_dev) {
+            std::vector<const char *> gn;
+            for (auto &g : genomes) gn.push_back(g.c_str());
+            rc = covh_genome_coverage_estimated(S.stoit.c_str(), S.prim, S.any_seen, gn.data(), gn.size(), taker, !a.no_zeros, est.data(), est.size(), S.genome_estimates.data(),
+                                                S.genome_stats.data(), &rm[bi]);
+        } else {
             std::vector<const char *> gn;
             for (auto &g : genomes) gn.push_back(g.c_str());
             rc = covh_genome_coverage_with_contig_names(&hdr, &hs, 1, S.genome_of_tid.data(), gn.data(), gn.size(), taker, !a.no_zeros, est.data(),

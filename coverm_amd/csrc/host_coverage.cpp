@@ -689,6 +689,40 @@ int covh_genome_coverage_with_contig_names(const covh_header *h, const covh_samp
     return COV_OK;
 }
 
+// The same scan of one sample with the genomes aggregated and evaluated on the device (cov_set_genomes / cov_fetch_genome_estimates:
+// the same floats, bit for bit): what is left is the loop over genomes above — zero rows, --no-zeros, ReadsMapped, the taker calls.
+int covh_genome_coverage_estimated(const char *stoit_name, uint64_t num_detected_primary_alignments, int any_contig_seen,
+                                   const char *const *genome_names, size_t n_genomes, covh_taker *taker, int print_zero,
+                                   const covh_estimator *est, size_t n_est, const float *estimates, const cov_genome_stats *gstats,
+                                   covh_reads_mapped *rm_out) {
+    if (!check_excl(est, n_est)) { g_err = "estimators disagree on contig_end_exclusion"; return COV_ERR_INVALID_ARG; }
+    for (size_t k = 0; k < n_est; k++)
+        if (est[k].kind == COVH_PILEUP_COUNTS || est[k].kind == COVH_TPM) { g_err = "covh_genome_coverage_estimated: coverage histogram and TPM are evaluated on the host"; return COV_ERR_INVALID_ARG; }
+    if (n_genomes && n_est && (!estimates || !gstats)) { g_err = "covh_genome_coverage_estimated: no estimates"; return COV_ERR_INVALID_ARG; }
+    taker->start_stoit(stoit_name);
+    u64 mapped_total = 0;
+    if (!any_contig_seen && num_detected_primary_alignments == 0) {
+        // warn only (:230-234)
+    } else {
+        for (size_t gi = 0; gi < n_genomes; gi++) {
+            const float *c = estimates + gi * n_est;
+            bool nonzero = false;
+            for (size_t k = 0; k < n_est; k++) nonzero |= c[k] > 0.0f;
+            if (nonzero) mapped_total += gstats[gi].reads_in_genome;
+            if (print_zero || nonzero) {
+                taker->start_entry(gi, genome_names[gi]);
+                for (size_t k = 0; k < n_est; k++) {
+                    if (c[k] > 0.0f) taker->add_single_coverage(c[k]);
+                    else print_zero_coverage(est[k], *taker, gstats[gi].genome_len);
+                }
+                taker->finish_entry();
+            }
+        }
+    }
+    if (rm_out) { rm_out->num_mapped_reads = mapped_total; rm_out->num_reads = num_detected_primary_alignments; }
+    return COV_OK;
+}
+
 // ------------------------------------------------------------------ genome.rs:419-929
 namespace {
 struct SepCtx {

@@ -1979,9 +1979,10 @@ __device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
     return v;
 }
 
-// The trimmed mean's total (estimators.rs:596-640, restated over prefix sums as described above) by the WHOLE wave for one contig: 64 bins per
-// step.  Every argument is wave-uniform; every lane returns the total.
-__device__ __forceinline__ u64 trimmed_total_wave(const u32 *__restrict__ bins, u32 nh, u64 bin0_extra, u64 min_index, u64 max_index) {
+// The trimmed mean's total (estimators.rs:596-640, restated over prefix sums as described above) by the WHOLE wave for one entry: 64 bins per
+// step.  Every argument is wave-uniform; every lane returns the total.  BIN: u32 (a contig's bins in the arena) or u64 (a genome's merged bins).
+template <typename BIN>
+__device__ __forceinline__ u64 trimmed_total_wave(const BIN *__restrict__ bins, u32 nh, u64 bin0_extra, u64 min_index, u64 max_index) {
     const int lane = lane_id();
     u64 total = 0, carry = 0;        // carry = prefix of the bins in front of this batch (wave-uniform)
     int state = 0;                   // 0: before s, 1: between s and e, 2: done
@@ -2015,48 +2016,46 @@ __device__ __forceinline__ u64 trimmed_total_wave(const u32 *__restrict__ bins, 
     return total;
 }
 
-// LANES = false: one WAVE per contig (lane 0 evaluates, the wave walks the histogram); LANES = true: one LANE per contig — for assemblies
+// What calculate_coverage sees of one entry: the integer statistics EntryAcc::add_contig accumulates (host_coverage.cpp) and the two sums over
+// the entry's unobserved contig lengths (estimators.rs:226-242: with and without the contig_end_exclusion rule).  A contig entry has no
+// unobserved length (contig.rs:62-66); a genome entry (genome_kernels.hip.h) carries those of its contigs without a considered record.
+struct EstEntry {
+    u64 win_len, win_sum_d, win_sum_d2, win_covered, win_min_d, full_len, full_covered, n_reads, mismatches;
+    u64 bin0_extra;            // window positions at depth 0 the bins do not hold: untouched tiles, and the unobserved bases (estimators.rs:596)
+    u64 unobs_win, unobs_full;
+    double identity;
+    u32 nh;                    // bins
+};
+
+// LANES = false: one WAVE per entry (lane 0 evaluates, the wave walks the histogram); LANES = true: one LANE per entry — for assemblies
 // (10^5 - 10^7 contigs, a few dozen bins each: a wave per contig is 2 M nearly idle waves, 1.46 ms at 2 M contigs) — where a lane walks
-// its own contig's bins one by one (the same integers in the same order of bins; integer sums, so the floats are the same bits) and the few
-// contigs with more than EST_SERIAL_BINS bins are walked by the whole wave, one after the other.
+// its own entry's bins one by one (the same integers in the same order of bins; integer sums, so the floats are the same bits) and the few
+// entries with more than EST_SERIAL_BINS bins are walked by the whole wave, one after the other.
+// `in`: this lane has an entry (LANES; lanes behind the last one walk along and write nothing); `live`: evaluate, else the row is zeros.
 constexpr u32 EST_SERIAL_BINS = 96;
-template <bool LANES>
-__device__ __forceinline__ void estimate_body(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
-                                              const u32 *__restrict__ arena, const EstParams &P, float *__restrict__ out) {
+template <bool LANES, typename BIN>
+__device__ __forceinline__ bool estimate_entry(const EstEntry &E, const BIN *__restrict__ bins, bool in, bool live, const EstParams &P, float *__restrict__ o) {
 #pragma clang fp contract(off)
     const int lane = lane_id();
-    const u32 c_raw = LANES ? blockIdx.x * 256u + threadIdx.x : blockIdx.x * 4u + (threadIdx.x >> 6);
-    if (!LANES && c_raw >= n_targets) return;
-    const bool in = c_raw < n_targets;
-    const u32 c = in ? c_raw : n_targets - 1u;        // (LANES: lanes behind the last contig walk along, write nothing)
-    const DevContig *C = &ctg[c];
-    float *o = out + (size_t)c * P.n;
-    const bool touched = C->n_pass != 0;
-    if (!LANES && !touched) { if ((u32)lane < P.n) o[lane] = 0.0f; return; }     // (the host prints such a contig through print_zero_coverage)
-    // the integer statistics as convert_results + EntryAcc::add_contig would hand them to calculate (host_coverage.cpp)
-    const u64 L = tlen[c];
-    const bool has_win = 2 * excl < L;
-    const u64 win_len = has_win ? L - 2 * excl : 0;
-    const u64 win_sum_d = has_win ? C->sum_d : 0, win_sum_d2 = has_win ? C->sum_d2 : 0, win_covered = has_win ? C->cov_win : 0;
-    const u64 win_min_d = has_win ? ((C->proc_win < win_len || C->min_d == 0xffffffffu) ? 0u : C->min_d) : 0xffffffffu;
-    const u64 full_len = L, full_covered = C->cov_full, n_reads = C->n_primary, mismatches = C->sum_nm - C->sum_indel;
-    const u32 nh = has_win ? C->max_d + 1u : 0u;          // = the compact histogram's length (k_hist_off<1>; no target mask here)
-    const u64 bin0_extra = win_len - C->proc_win;       // window positions of tiles no record touched: depth 0 (k_hist_compact adds the same)
-    const u32 *bins = arena + C->hist_off;
+    const u64 win_len = E.win_len, win_sum_d = E.win_sum_d, win_sum_d2 = E.win_sum_d2, win_covered = E.win_covered, win_min_d = E.win_min_d;
+    const u64 full_len = E.full_len, full_covered = E.full_covered, n_reads = E.n_reads, mismatches = E.mismatches;
+    const u32 nh = E.nh;
+    const u64 bin0_extra = E.bin0_extra;
+    bool nonzero = false;
     for (u32 k = 0; k < P.n; k++) {
         const DevEstimator e = P.e[k];
         float r = 0.0f;
         switch (e.kind) {
         case EST_MEAN: {
-            const u64 T = win_len;
+            const u64 T = win_len + E.unobs_win;
             if (T == 0 || (est_f32(win_covered) / est_f32(T)) < e.min_frac) break;
             const float num = e.exclude_mismatches ? est_f32(win_sum_d - mismatches) : est_f32(win_sum_d);
             r = num / est_f32(T);
             break;
         }
         case EST_TRIMMED_MEAN: {
-            const u64 T = win_len;
-            const bool walk = (!LANES || (in && touched)) && T != 0 && !((est_f32(win_covered) / est_f32(T)) < e.min_frac) && win_covered != 0;
+            const u64 T = win_len + E.unobs_win;
+            const bool walk = (!LANES || (in && live)) && T != 0 && !((est_f32(win_covered) / est_f32(T)) < e.min_frac) && win_covered != 0;
             const u64 min_index = est_f32_to_usize(__builtin_floorf(e.trim_min * est_f32(T)));
             const u64 max_index = est_f32_to_usize(__builtin_ceilf(e.trim_max * est_f32(T)));
             u64 total = 0;
@@ -2082,10 +2081,10 @@ __device__ __forceinline__ void estimate_body(const DevContig *__restrict__ ctg,
                         } else total += n * (u64)i;
                     }
                 }
-                for (u64 bm = __ballot(walk && !serial); bm != 0; bm &= bm - 1) {      // deep contigs: the whole wave on each
+                for (u64 bm = __ballot(walk && !serial); bm != 0; bm &= bm - 1) {      // deep entries: the whole wave on each
                     const int l = __builtin_ctzll(bm);
                     const u64 bp = bcast_u64((u64)(uintptr_t)bins, l);
-                    const u64 t = trimmed_total_wave(reinterpret_cast<const u32 *>((uintptr_t)bp), __builtin_amdgcn_readlane(nh, l), bcast_u64(bin0_extra, l),
+                    const u64 t = trimmed_total_wave(reinterpret_cast<const BIN *>((uintptr_t)bp), __builtin_amdgcn_readlane(nh, l), bcast_u64(bin0_extra, l),
                                                      bcast_u64(min_index, l), bcast_u64(max_index, l));
                     if (lane == l) total = t;
                 }
@@ -2095,42 +2094,74 @@ __device__ __forceinline__ void estimate_body(const DevContig *__restrict__ ctg,
             break;
         }
         case EST_COVERED_FRACTION: {
-            const u64 T = full_len;
+            const u64 T = full_len + E.unobs_full;
             if (T == 0 || (est_f32(full_covered) / est_f32(T)) < e.min_frac) break;
             r = est_f32(full_covered) / est_f32(T);
             break;
         }
         case EST_COVERED_BASES: {
-            const u64 T = full_len;
+            const u64 T = full_len + E.unobs_full;
             if (T == 0 || (est_f32(full_covered) / est_f32(T)) < e.min_frac) break;
             r = est_f32(full_covered);
             break;
         }
         case EST_RPKM: {
-            const u64 T = full_len;
+            const u64 T = full_len + E.unobs_full;
             if (T == 0 || (est_f32(full_covered) / est_f32(T)) < e.min_frac) break;
             r = est_f32(n_reads * 1000000000ull) / est_f32(T);
             break;
         }
         case EST_VARIANCE: {
-            const u64 T = win_len;
+            const u64 T = win_len + E.unobs_win;
             if (T == 0) break;
             if ((est_f32(win_covered) / est_f32(T)) < e.min_frac || T < 3 || win_len == 0) break;
-            const u64 kk = win_min_d, N = win_len;
+            // k = the lowest occupied depth: 0 as soon as unobserved bases land in counts[0]
+            const u64 kk = E.unobs_win > 0 ? 0ull : win_min_d, N = T;
             const u64 ex = win_sum_d - kk * N;
             const u64 ex2 = win_sum_d2 - 2 * kk * win_sum_d + kk * kk * N;
             r = (est_f32(ex2) - est_f32(ex * ex) / est_f32(T)) / est_f32(T - 1);
             break;
         }
-        case EST_LENGTH: r = est_f32(full_len); break;
+        case EST_LENGTH: r = est_f32(full_len + E.unobs_full); break;
         case EST_READ_COUNT: r = est_f32(n_reads); break;
-        case EST_READS_PER_BASE: r = est_f32(n_reads) / est_f32(full_len); break;
-        case EST_ANIR: r = n_reads == 0 ? 0.0f : (float)(C->id_primary / (double)n_reads); break;
+        case EST_READS_PER_BASE: r = est_f32(n_reads) / est_f32(full_len + E.unobs_full); break;
+        case EST_ANIR: r = n_reads == 0 ? 0.0f : (float)(E.identity / (double)n_reads); break;
         default: break;
         }
-        if (LANES) { if (in) o[k] = touched ? r : 0.0f; }
+        if (!live) r = 0.0f;
+        nonzero |= r > 0.0f;
+        if (LANES) { if (in) o[k] = r; }
         else if (lane == 0) o[k] = r;
     }
+    return nonzero;
+}
+
+// `coverm contig`: entry = contig c.
+template <bool LANES>
+__device__ __forceinline__ void estimate_body(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
+                                              const u32 *__restrict__ arena, const EstParams &P, float *__restrict__ out) {
+    const int lane = lane_id();
+    const u32 c_raw = LANES ? blockIdx.x * 256u + threadIdx.x : blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (!LANES && c_raw >= n_targets) return;
+    const bool in = c_raw < n_targets;
+    const u32 c = in ? c_raw : n_targets - 1u;        // (LANES: lanes behind the last contig walk along, write nothing)
+    const DevContig *C = &ctg[c];
+    float *o = out + (size_t)c * P.n;
+    const bool touched = C->n_pass != 0;
+    if (!LANES && !touched) { if ((u32)lane < P.n) o[lane] = 0.0f; return; }     // (the host prints such a contig through print_zero_coverage)
+    // the integer statistics as convert_results + EntryAcc::add_contig would hand them to calculate (host_coverage.cpp)
+    const u64 L = tlen[c];
+    const bool has_win = 2 * excl < L;
+    EstEntry E;
+    E.win_len = has_win ? L - 2 * excl : 0;
+    E.win_sum_d = has_win ? C->sum_d : 0; E.win_sum_d2 = has_win ? C->sum_d2 : 0; E.win_covered = has_win ? C->cov_win : 0;
+    E.win_min_d = has_win ? ((C->proc_win < E.win_len || C->min_d == 0xffffffffu) ? 0u : C->min_d) : 0xffffffffu;
+    E.full_len = L; E.full_covered = C->cov_full; E.n_reads = C->n_primary; E.mismatches = C->sum_nm - C->sum_indel;
+    E.nh = has_win ? C->max_d + 1u : 0u;              // = the compact histogram's length (k_hist_off<1>; no target mask here)
+    E.bin0_extra = E.win_len - C->proc_win;           // window positions of tiles no record touched: depth 0 (k_hist_compact adds the same)
+    E.unobs_win = 0; E.unobs_full = 0;                // unobserved lengths [0] (contig.rs:62-66)
+    E.identity = C->id_primary;
+    (void)estimate_entry<LANES, u32>(E, arena + C->hist_off, in, touched, P, o);
 }
 __global__ __launch_bounds__(256) void k_estimate(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
                                                   const u32 *__restrict__ arena, EstParams P, float *__restrict__ out) {

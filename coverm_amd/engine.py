@@ -190,6 +190,48 @@ class Session:
         self._check(self._lib.cov_fetch_estimates(self._h, out.ctypes.data if out.size else None))
         return out
 
+    def set_genomes(self, genome_of_tid, n_genomes: int):
+        """cov_set_genomes (after set_targets): genome_of_tid[t] = genome of target t, -1 = outside every genome.  Implies the target mask;
+        with estimators set, every finish then also aggregates the contigs into genomes and evaluates the estimators per genome on the
+        device.  None / n_genomes = 0 turns it off."""
+        if genome_of_tid is None or n_genomes == 0:
+            self._n_genomes = 0
+            self._check(self._lib.cov_set_genomes(self._h, None, C.c_uint32(0)))
+            return
+        g = np.ascontiguousarray(genome_of_tid, dtype=np.int32)
+        assert len(g) == self.n_targets
+        self._n_genomes = int(n_genomes)
+        self._check(self._lib.cov_set_genomes(self._h, g.ctypes.data if len(g) else None, C.c_uint32(n_genomes)))
+
+    def finish_genomes(self):
+        """cov_finish_genomes: the pipeline and its verdicts without the per-contig statistics (genomes and estimators set)."""
+        summ = CovSummary()
+        self._check(self._lib.cov_finish_genomes(self._h, C.byref(summ)))
+        self.summary = summ
+        return summ
+
+    def genome_estimates(self):
+        """cov_fetch_genome_estimates: n_genomes x n_estimators f32 of the last finish."""
+        out = np.empty((getattr(self, "_n_genomes", 0), getattr(self, "_n_est", 0)), dtype=np.float32)
+        self._check(self._lib.cov_fetch_genome_estimates(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def genome_stats(self):
+        """cov_fetch_genome_stats: one native.GENOME_STATS_DTYPE entry per genome."""
+        out = np.zeros(getattr(self, "_n_genomes", 0), dtype=native.GENOME_STATS_DTYPE)
+        self._check(self._lib.cov_fetch_genome_stats(self._h, out.ctypes.data if out.size else None))
+        return out
+
+    def genome_kernel_ms(self):
+        """(ms, launches) of the genome kernels of the last finish (COV_K_GENOME)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_GENOME, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def store_spills(self):
+        return int(self._lib.cov_store_spills(self._h))
+
     def kernel_ms(self):
         out = {}
         for k, name in native.KERNEL_NAMES.items():

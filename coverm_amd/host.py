@@ -344,6 +344,25 @@ def mosdepth_genome_coverage_with_contig_names(names, target_len, samples, genom
     return _finish(rc, rm, len(samples))
 
 
+def genome_coverage_estimated(stoit_name: str, num_detected_primary_alignments: int, any_contig_seen: bool, genomes: List[str],
+                              coverage_taker: CoverageTaker, print_zero_coverage_genomes: bool, coverage_estimators, estimates,
+                              genome_stats) -> ReadsMapped:
+    """The contig-names genome scan of one sample whose genomes were aggregated and evaluated on the device: `estimates` =
+    Session.genome_estimates(), `genome_stats` = Session.genome_stats() (native.GENOME_STATS_DTYPE)."""
+    e = np.ascontiguousarray(estimates, np.float32)
+    gs = np.ascontiguousarray(genome_stats)
+    assert gs.dtype == native.GENOME_STATS_DTYPE and len(gs) == len(genomes) and e.size == len(genomes) * len(coverage_estimators)
+    rm = (_ReadsMapped * 1)()
+    gn = (C.c_char_p * max(1, len(genomes)))(*[x.encode() for x in genomes])
+    L = _lib()
+    L.covh_genome_coverage_estimated.argtypes = [C.c_char_p, C.c_uint64, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p,
+                                                 C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+    rc = L.covh_genome_coverage_estimated(stoit_name.encode(), num_detected_primary_alignments, int(bool(any_contig_seen)), gn, len(genomes),
+                                          coverage_taker._h, int(print_zero_coverage_genomes), _est_array(coverage_estimators),
+                                          len(coverage_estimators), e.ctypes.data if e.size else None, gs.ctypes.data if len(gs) else None, rm)
+    return _finish(rc, rm, 1)[0]
+
+
 def mosdepth_genome_coverage(names, target_len, samples, split_char: str, coverage_taker: CoverageTaker,
                              print_zero_coverage_genomes: bool, coverage_estimators, single_genome: bool
                              ) -> List[ReadsMapped]:

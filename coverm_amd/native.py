@@ -16,7 +16,8 @@ ERR_UNSORTED, ERR_NM_MISSING, ERR_NM_BADTYPE, ERR_POS_OOB, ERR_BAD_CIGAR, ERR_BA
 ERR_INVALID_ARG, ERR_HIP, ERR_STATE = 16, 17, 18
 WANT_HIST, WANT_IDENTITY = 1, 2
 WANT_IDENTITY_PRIMARY_ONLY, WANT_IDENTITY_NONSUPP_ONLY = 4, 8
-K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 7
+K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 8
+K_GENOME = 7      # cov_set_genomes: reduce + histogram merge + estimate over genomes (Session.genome_kernel_ms)
 KERNEL_NAMES = {K_PREP: "k_prep", K_RANGES: "k_ranges", K_PILEUP: "k_pileup", K_IDENTITY: "k_identity",
                 K_HIST: "k_hist", K_HIST_COMPACT: "k_hist_compact", K_ESTIMATE: "k_estimate"}
 
@@ -48,9 +49,14 @@ CONTIG_STATS_DTYPE = np.dtype([
     ("win_min_d", "<u4"), ("win_max_d", "<u4"), ("hist_len", "<u4"), ("reserved", "<u4"), ("hist_off", "<u8")])
 assert CONTIG_STATS_DTYPE.itemsize == 128
 
+# numpy mirror of cov_genome_stats (24 bytes)
+GENOME_STATS_DTYPE = np.dtype([("reads_in_genome", "<u8"), ("genome_len", "<u8"), ("n_contigs_seen", "<u4"), ("any_nonzero", "<u4")])
+assert GENOME_STATS_DTYPE.itemsize == 24
+
 EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "cov_set_targets",
            "cov_set_target_mask", "cov_push_batch", "cov_push_batch_device", "cov_finish", "cov_fetch_hist",
-           "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths"]
+           "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths",
+           "cov_set_genomes", "cov_finish_genomes", "cov_fetch_genome_estimates", "cov_fetch_genome_stats"]
 
 _lib = None
 
@@ -104,6 +110,12 @@ def lib():
     L.cov_last_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint32 * 4)]
     L.cov_set_estimators.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
     L.cov_fetch_estimates.argtypes = [C.c_void_p, C.c_void_p]
+    L.cov_set_genomes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.cov_finish_genomes.argtypes = [C.c_void_p, C.POINTER(CovSummary)]
+    L.cov_fetch_genome_estimates.argtypes = [C.c_void_p, C.c_void_p]
+    L.cov_fetch_genome_stats.argtypes = [C.c_void_p, C.c_void_p]
+    L.cov_store_spills.argtypes = [C.c_void_p]
+    L.cov_store_spills.restype = C.c_uint32
     _lib = L
     return L
 

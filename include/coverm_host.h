@@ -121,6 +121,16 @@ int covh_genome_coverage_with_contig_names(const covh_header *h, const covh_samp
                                            size_t n_genomes, covh_taker *taker, int print_zero_coverage_genomes,
                                            const covh_estimator *est, size_t n_est,
                                            covh_reads_mapped *reads_mapped_out);
+/* The contig-names genome scan of ONE sample with the genomes already aggregated and evaluated on the device (cov_set_genomes):
+ * estimates = the n_genomes x n_est floats of cov_fetch_genome_estimates, gstats = cov_fetch_genome_stats' entries, any_contig_seen =
+ * some reference of the sample had a considered record (cov_summary.n_considered != 0; genome.rs:230-234 prints nothing otherwise when
+ * the sample has no primary alignment either).  What is left here is genome.rs:236-302's control flow: zero rows, --no-zeros,
+ * ReadsMapped, the taker calls, in genome order — the entries covh_genome_coverage_with_contig_names emits.  COVH_PILEUP_COUNTS and
+ * COVH_TPM are never evaluated on the device: COV_ERR_INVALID_ARG. */
+int covh_genome_coverage_estimated(const char *stoit_name, uint64_t num_detected_primary_alignments, int any_contig_seen,
+                                   const char *const *genome_names, size_t n_genomes, covh_taker *taker, int print_zero_coverage_genomes,
+                                   const covh_estimator *est, size_t n_est, const float *estimates, const cov_genome_stats *gstats,
+                                   covh_reads_mapped *reads_mapped_out);
 int covh_genome_coverage_separator(const covh_header *h, const covh_sample *samples, size_t n_samples,
                                    uint8_t split_char, covh_taker *taker, int print_zero_coverage_genomes,
                                    const covh_estimator *est, size_t n_est, int single_genome,

@@ -149,7 +149,8 @@ typedef enum {
     COV_K_HIST = 4,     /* histogram arena layout + zero fill (before the pileup) */
     COV_K_HIST_COMPACT = 5, /* compact histogram (behind the pileup) */
     COV_K_ESTIMATE = 6, /* CoverageEstimator::calculate_coverage of every contig (cov_set_estimators) */
-    COV_K_COUNT = 7
+    COV_K_GENOME = 7,   /* cov_set_genomes: contigs reduced into genomes, histograms merged, calculate_coverage of every genome */
+    COV_K_COUNT = 8
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -290,7 +291,8 @@ cov_status cov_algorithmic_bytes(const cov_session *s, uint64_t *bytes);
  * cov_contig_stats) bit for bit; a host that takes them skips the per-contig finalisation and, unless it prints histograms, the
  * histogram fetch.  Kinds = enum CoverageEstimator's variant order (coverm_host.h covh_kind).  Not offered: COV_EST_TPM (f64 exp / ln of the
  * host's libm) and COV_EST_PILEUP_COUNTS (prints the histogram itself) — COV_ERR_INVALID_ARG, evaluate those on the host.  Needs
- * COV_WANT_HIST for a trimmed mean and COV_WANT_IDENTITY for ANIr, no target mask (genome modes aggregate contigs first: host). */
+ * COV_WANT_HIST for a trimmed mean and COV_WANT_IDENTITY for ANIr.  With a target mask the entries are genomes, not contigs: cov_fetch_estimates
+ * then returns COV_ERR_STATE, and the estimators are evaluated per genome when cov_set_genomes (below) gave the genomes' table. */
 typedef struct {
     int32_t kind;                      /* COV_EST_* */
     float min_fraction_covered_bases;
@@ -313,6 +315,39 @@ typedef struct {
 #define COV_EST_MAX 16
 cov_status cov_set_estimators(cov_session *s, const cov_estimator *est, uint32_t n_est); /* n_est = 0: off (the default) */
 cov_status cov_fetch_estimates(cov_session *s, float *out);                              /* after cov_finish: n_targets * n_est floats */
+
+/* ---- the contig-names genome scan on the device (mosdepth_genome_coverage_with_contig_names, genome.rs:17-322): one entry per GENOME.
+ * cov_set_genomes after cov_set_targets: genome_of_tid[t] = the genome of target t, -1 = outside every genome.  It implies the target mask
+ * cov_set_target_mask(genome_of_tid[t] >= 0) would set (genome.rs:170-171) and keeps a table genome -> targets in ascending target order
+ * on the device.  NULL or n_genomes = 0 turns it off (and drops the mask); cov_set_targets and cov_set_target_mask turn it off as well
+ * (estimators holding a genome's ANIr are dropped with it: the per-contig evaluation has no identity sum for them — set them again).
+ * With genomes set, cov_set_estimators is accepted together with the mask, and cov_finish also
+ *   - reduces the per-contig results over each genome's targets: integer sums, min / max depth, the unobserved lengths of the targets
+ *     without a considered record (estimators.rs:226-242), and the not-supplementary identity sum added target by target in ascending
+ *     order (one ordered chain per genome: f64 addition is not associative, genome.rs:220-223);
+ *   - merges the depth histograms of each genome's targets (COV_WANT_HIST);
+ *   - evaluates every estimator for every genome with the expressions cov_fetch_estimates' floats come from, the reads counted as
+ *     genome.rs:173-174 counts them (every considered record) — ANIr therefore needs the not-supplementary identity sum here.
+ * cov_fetch_genome_estimates: n_genomes x n_est floats, bit for bit what coverm_host.h's covh_genome_coverage_with_contig_names computes
+ * from cov_contig_stats and the histogram; cov_fetch_genome_stats: what the scan's control flow needs beside them (ReadsMapped, zero rows,
+ * --no-zeros).  A host that takes both needs neither the per-contig statistics nor the histogram.  After a spill of the bounded record
+ * store (below) the contigs that left are on the host: both fetches return COV_ERR_STATE, aggregate on the host then. */
+typedef struct {
+    uint64_t reads_in_genome;  /* sum of n_pass over the genome's targets (genome.rs:173-174) */
+    uint64_t genome_len;       /* sum of the lengths of its targets */
+    uint32_t n_contigs_seen;   /* targets with a considered record */
+    uint32_t any_nonzero;      /* some estimator's value is > 0 */
+} cov_genome_stats;
+cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_t n_genomes);
+/* cov_finish for a host that takes the genome results only (genomes and estimators set): the same pipeline and the same verdicts —
+ * COV_ERR_UNSORTED / COV_ERR_NM_* / COV_ERR_POS_OOB / ... exactly when cov_finish returns them, the order rule judged on the device — but no
+ * cov_contig_stats array: the per-contig block (160 B per target) stays on the device and no pass over the targets runs on the host.
+ * summary->hist_total is 0.  cov_fetch_genome_estimates / cov_fetch_genome_stats / cov_kernel_ms afterwards as after cov_finish; cov_fetch_hist
+ * and cov_gather need a cov_finish.  COV_ERR_STATE without genomes or estimators, and after a spill of the bounded record store (cov_finish
+ * then, and aggregate on the host). */
+cov_status cov_finish_genomes(cov_session *s, cov_summary *summary);
+cov_status cov_fetch_genome_estimates(cov_session *s, float *out);          /* after cov_finish: n_genomes * n_est floats */
+cov_status cov_fetch_genome_stats(cov_session *s, cov_genome_stats *out);   /* after cov_finish: n_genomes entries */
 
 /* ---- bounded record store.  The reference holds one contig at a time and flushes it when the tid changes (contig.rs:128-155), so a
  * sample may be arbitrarily large.  The session's record store keeps as many contigs as fit under a cap (2^31 records / 2^31 CIGAR
