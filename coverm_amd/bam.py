@@ -175,11 +175,12 @@ def read_streamed(path: str, threads: int = None, span_index: int = 0, span_coun
                                     coff, cat("cigar"))
 
 
-def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, mask=None, span=(0, 1), want_mates: bool = False):
+def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, mask=None, span=(0, 1), want_mates: bool = False, group: bool = False):
     """Device ingest (covh_bam_read_header + covh_bam_gpu_ingest): the GPU inflates the BGZF blocks, finds the records and fills
     the session's record store.  Sets the session's targets from the file's header.  Returns (ref_names, ref_lens, n_records,
     timing dict); raises IngestFallback when the file needs the CPU reader.  span = (index, count): one tid span of the file
-    (covh_bam_gpu_ingest_span; the spans of a file partition its records in order)."""
+    (covh_bam_gpu_ingest_span; the spans of a file partition its records in order).  group: the file need not be sorted by reference —
+    the ingest is told that grouping follows (cov_ingest_want_grouping) and Session.group_records() runs behind it."""
     L = _lib()
     if not getattr(L, "_ingest_bound", False):
         L.covh_bam_read_header.restype = C.c_void_p
@@ -211,6 +212,8 @@ def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, 
         L.cov_ingest_want_mates.argtypes = [C.c_void_p, C.c_int]
         if L.cov_ingest_want_mates(session._h, int(want_mates)) != 0:
             raise RuntimeError("cov_ingest_want_mates failed")
+        if session._lib.cov_ingest_want_grouping(session._h, int(group)) != 0:
+            raise RuntimeError("cov_ingest_want_grouping failed")
         n = C.c_uint64(0)
         t = (C.c_double * 8)()
         rc = L.covh_bam_gpu_ingest_span(path.encode(), threads, session._h, hd, int(check_crc), int(span[0]), int(span[1]), C.byref(n), t, err, 512)
@@ -218,6 +221,8 @@ def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, 
             raise IngestFallback(err.value.decode())
         if rc != 0:
             raise IOError(err.value.decode())
+        if group:
+            session.group_records()
         return names, lens, int(n.value), dict(read=t[0], slot_wait=t[1], end=t[2], total=t[3], begin=t[4], walk=t[5], feed=t[6])
     finally:
         L.covh_bam_header_free(hd)

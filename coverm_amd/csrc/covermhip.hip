@@ -6,6 +6,7 @@
 #include "prep_lean.hip.h"
 #include "genome_kernels.hip.h"
 #include "ingest_kernels.hip.h"
+#include "group_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -13,6 +14,7 @@
 #include <chrono>
 #include <cstdio>
 #include <dlfcn.h>
+#include <functional>
 #include <sched.h>
 #include <cstdlib>
 #include <cstring>
@@ -154,6 +156,10 @@ struct cov_session {
     // mates of the records the device ingest extracted (cov_ingest_want_mates): next_refID + read-name hash, for cov_pair_filter_apply
     DevBuf<int32_t> s_mtid; DevBuf<u64> s_qh1; DevBuf<u32> s_qh2;
     bool want_mates = false;
+    bool want_grouping = false;      // cov_ingest_want_grouping: cov_group_records will follow, so decreasing keys are no reason to hand a file back
+    bool ing_was_span = false;       // records of a cov_ingest_span rank are in the store: cov_group_records refuses
+    float grp_ms[4] = {};            // the last cov_group_records: whole call on the stream, order check, sort passes, gather
+    uint32_t grp_launches = 0;
     uint64_t mates_valid = 0;        // the mate columns describe records [0, mates_valid) of the store
     uint64_t n_records = 0, n_cigar = 0;
     bool adopted = false;
@@ -832,7 +838,7 @@ cov_status cov_reset(cov_session *s) {
         if (a != COV_OK && !(spilled && a == COV_ERR_STATE)) return a;
         if (a != COV_OK) s->err.clear();
     }
-    s->adopted = false; s->n_records = 0; s->n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->mates_valid = 0;
+    s->adopted = false; s->n_records = 0; s->n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->mates_valid = 0; s->ing_was_span = false;
     s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing_rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
@@ -1685,6 +1691,7 @@ cov_status cov_ingest_span(cov_session *s, int64_t key_lo, int64_t key_hi, int s
     if (!s || !s->ing_active || s->ing_fed_any || key_lo < 0 || key_hi < key_lo || file_hi < file_lo || file_hi > s->ing_comp) return COV_ERR_INVALID_ARG;
     s->ing_key_lo = key_lo; s->ing_key_hi = key_hi; s->ing_search_first = search_first_record != 0; s->ing_open_end = open_end != 0;
     s->ing_span_lo = file_lo; s->ing_span_hi = file_hi;
+    if (key_lo > 0 || key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end) s->ing_was_span = true;
     return COV_OK;
 }
 
@@ -1704,7 +1711,7 @@ static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
         u32 st = (u32)res[2];
         s->ing_tail_key = res[7];
         const bool span = s->ing_key_lo > 0 || s->ing_key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end;
-        if (!span && !s->want_mates) st &= ~64u;       // whole file: cov_finish reports disorder in file order, beside the other per-record errors
+        if (!span && (!s->want_mates || s->want_grouping)) st &= ~64u;       // whole file: cov_finish reports disorder in file order, beside the other per-record errors
         if (st && !s->ing_fail) { s->ing_fail = st; s->ing_fail_dbg[0] = res[4]; s->ing_fail_dbg[1] = res[5]; s->ing_fail_dbg[2] = res[6]; }
         u64 R = s->n_records + s->ing_rec_total, Cg = s->n_cigar + s->ing_cig_total;
         if (!s->ing_fail && nrec && R && !s->want_mates && (R + nrec > s->cap_records || Cg + ncig > s->cap_cigar)) {
@@ -2061,9 +2068,57 @@ cov_status cov_ingest_want_mates(cov_session *s, int on) {
     return COV_OK;
 }
 
+cov_status cov_ingest_want_grouping(cov_session *s, int on) {
+    if (!s || s->ing_active) return COV_ERR_INVALID_ARG;
+    s->want_grouping = on != 0;
+    return COV_OK;
+}
+
 // ---------------------------------------------------------------------------------------------- reader-stage pair filter (pair_kernels.hip.h)
 static_assert(sizeof(cov_pair_filter) == sizeof(covp::PairFilter) && offsetof(cov_pair_filter, min_aligned_length_pair) == offsetof(covp::PairFilter, min_aligned_length_pair) &&
               offsetof(cov_pair_filter, min_mapq) == offsetof(covp::PairFilter, min_mapq), "cov_pair_filter mirrors the device struct");
+
+// The store replaced by its records order[0 .. S) (order[new] = old): CIGAR offsets by a scan over the selected records' CIGAR lengths, whose
+// consumer moves the fixed fields and the CIGAR words (pair_kernels.hip.h); with_mates: the three mate columns travel along.
+static cov_status gather_store(cov_session *s, const u32 *order, u32 S, bool with_mates) {
+    hipStream_t st = s->stream;
+    DevBuf<u32> d_bsum; DevBuf<u64> d_tot;
+    DevBuf<int32_t> n_tid, n_pos, n_mtid; DevBuf<uint16_t> n_flag; DevBuf<uint8_t> n_mapq, n_nmk; DevBuf<u32> n_nm, n_lseq, n_coff, n_cig, n_qh2; DevBuf<u64> n_qh1;
+    struct Rel { std::function<void()> f; ~Rel() { f(); } } rel{[&] {      // (after the swap below: the old store)
+        n_tid.release(); n_pos.release(); n_mtid.release(); n_flag.release(); n_mapq.release(); n_nmk.release(); n_nm.release(); n_lseq.release(); n_coff.release(); n_cig.release();
+        n_qh1.release(); n_qh2.release(); d_bsum.release(); d_tot.release(); }};
+    const u32 nb = (S + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    HIPCHK(d_bsum.reserve((size_t)nb + 1, st)); HIPCHK(d_tot.reserve(1, st));
+    const covp::SelCigarLen clen{order, s->s_coff.p};
+    hipLaunchKernelGGL((covp::k_scan_sums<covp::SelCigarLen>), dim3(nb), dim3(256), 0, st, clen, S, d_bsum.p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_tot.p);
+    HIPCHK(hipGetLastError());
+    u64 n_cig_sel = 0;
+    HIPCHK(hipMemcpyAsync(&n_cig_sel, d_tot.p, sizeof n_cig_sel, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(n_tid.reserve(S, st)); HIPCHK(n_pos.reserve(S, st)); HIPCHK(n_flag.reserve(S, st)); HIPCHK(n_mapq.reserve(S, st)); HIPCHK(n_nmk.reserve(S, st));
+    HIPCHK(n_nm.reserve(S, st)); HIPCHK(n_lseq.reserve(S, st)); HIPCHK(n_coff.reserve((size_t)S + 1, st)); HIPCHK(n_cig.reserve((size_t)n_cig_sel + 1, st));
+    covp::SelGather G{};
+    G.order = order;
+    G.src = covp::Store{s->s_tid.p, s->s_pos.p, s->s_flag.p, s->s_mapq.p, s->s_nmk.p, s->s_nm.p, s->s_lseq.p, s->s_coff.p, s->s_cig.p};
+    G.dst = covp::Store{n_tid.p, n_pos.p, n_flag.p, n_mapq.p, n_nmk.p, n_nm.p, n_lseq.p, n_coff.p, n_cig.p};
+    hipLaunchKernelGGL((covp::k_scan_apply<covp::SelCigarLen, covp::SelGather>), dim3(nb), dim3(256), 0, st, clen, G, S, (const u32 *)d_bsum.p);
+    HIPCHK(hipGetLastError());
+    if (with_mates) {
+        HIPCHK(n_mtid.reserve(S, st)); HIPCHK(n_qh1.reserve(S, st)); HIPCHK(n_qh2.reserve(S, st));
+        hipLaunchKernelGGL(covg::k_group_gather_mates, dim3((S + 255u) / 256u), dim3(256), 0, st, order, S, (const int32_t *)s->s_mtid.p, (const u64 *)s->s_qh1.p, (const u32 *)s->s_qh2.p,
+                           n_mtid.p, n_qh1.p, n_qh2.p);
+        HIPCHK(hipGetLastError());
+    }
+    const u32 end_off = (u32)n_cig_sel;
+    HIPCHK(hipMemcpyAsync(n_coff.p + S, &end_off, sizeof end_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));
+    std::swap(s->s_tid, n_tid); std::swap(s->s_pos, n_pos); std::swap(s->s_flag, n_flag); std::swap(s->s_mapq, n_mapq); std::swap(s->s_nmk, n_nmk);
+    std::swap(s->s_nm, n_nm); std::swap(s->s_lseq, n_lseq); std::swap(s->s_coff, n_coff); std::swap(s->s_cig, n_cig);
+    if (with_mates) { std::swap(s->s_mtid, n_mtid); std::swap(s->s_qh1, n_qh1); std::swap(s->s_qh2, n_qh2); }
+    s->n_records = S; s->n_cigar = n_cig_sel;
+    return COV_OK;
+}
 
 cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint64_t *n_selected, uint64_t *n_primary) {
     if (!s || !f) return COV_ERR_INVALID_ARG;
@@ -2203,33 +2258,99 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     const covp::PairEmit emit{d_partner.p, d_order.p};
     hipLaunchKernelGGL((covp::k_scan_apply<covp::PairSlots, covp::PairEmit>), dim3(nb), dim3(256), 0, st, slots, emit, R, (const u32 *)d_bsum.p);
     // ---- the selected store: CIGAR offsets by a second scan, whose consumer moves the records
-    const u32 nb2 = (S + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
-    HIPCHK(d_bsum.reserve((size_t)std::max(nb, nb2) + 1, st));      // (never grows: S <= R)
-    const covp::SelCigarLen clen{d_order.p, s->s_coff.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covp::SelCigarLen>), dim3(nb2), dim3(256), 0, st, clen, S, d_bsum.p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb2, d_w.p + 3);
     HIPCHK(hipGetLastError());
-    u64 n_cig_sel = 0;
-    HIPCHK(hipMemcpyAsync(&n_cig_sel, d_w.p + 3, sizeof n_cig_sel, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    DevBuf<int32_t> n_tid, n_pos; DevBuf<uint16_t> n_flag; DevBuf<uint8_t> n_mapq, n_nmk; DevBuf<u32> n_nm, n_lseq, n_coff, n_cig;
-    struct Rel3 { DevBuf<int32_t> &a, &b; DevBuf<uint16_t> &c; DevBuf<uint8_t> &d, &e; DevBuf<u32> &f, &g, &h, &i;
-                  ~Rel3() { a.release(); b.release(); c.release(); d.release(); e.release(); f.release(); g.release(); h.release(); i.release(); } }
-        rel3{n_tid, n_pos, n_flag, n_mapq, n_nmk, n_nm, n_lseq, n_coff, n_cig};      // (after the swap below: the old store)
-    HIPCHK(n_tid.reserve(S, st)); HIPCHK(n_pos.reserve(S, st)); HIPCHK(n_flag.reserve(S, st)); HIPCHK(n_mapq.reserve(S, st)); HIPCHK(n_nmk.reserve(S, st));
-    HIPCHK(n_nm.reserve(S, st)); HIPCHK(n_lseq.reserve(S, st)); HIPCHK(n_coff.reserve((size_t)S + 1, st)); HIPCHK(n_cig.reserve((size_t)n_cig_sel + 1, st));
-    covp::SelGather G{};
-    G.order = d_order.p;
-    G.src = covp::Store{s->s_tid.p, s->s_pos.p, s->s_flag.p, s->s_mapq.p, s->s_nmk.p, s->s_nm.p, s->s_lseq.p, s->s_coff.p, s->s_cig.p};
-    G.dst = covp::Store{n_tid.p, n_pos.p, n_flag.p, n_mapq.p, n_nmk.p, n_nm.p, n_lseq.p, n_coff.p, n_cig.p};
-    hipLaunchKernelGGL((covp::k_scan_apply<covp::SelCigarLen, covp::SelGather>), dim3(nb2), dim3(256), 0, st, clen, G, S, (const u32 *)d_bsum.p);
+    { const cov_status g = gather_store(s, d_order.p, S, false); if (g != COV_OK) return g; }
+    s->mates_valid = 0;      // the mate columns still describe the unselected store: spent
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- records grouped by reference (group_kernels.hip.h)
+cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    covr::Range rr("group records by reference (cov_group_records)");
+    if (n_moved) *n_moved = 0;
+    if (s->ing_active) { s->err = "cov_group_records: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->adopted) { s->err = "cov_group_records: needs the session's own record store, not an adopted device batch (cov_push_batch_device)"; return COV_ERR_STATE; }
+    if (s->ing_was_span) { s->err = "cov_group_records: the store holds one tid span of a file (cov_ingest_span), which is cut where a file sorted by reference changes tid"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_group_records: a sample that is not sorted by reference must fit the record store (part of it already left the bounded store, judged in file order)"; return COV_ERR_STATE; }
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    const u32 R = (u32)s->n_records, nT = s->n_targets;
+    for (float &m : s->grp_ms) m = 0.f;
+    s->grp_launches = 0;
+    if (R < 2) return COV_OK;
+    const bool mates = s->mates_valid == s->n_records && s->mates_valid != 0;
+    hipEvent_t *ev = s->ev[COV_K_GROUP];      // [0] begin, [1] end; the split: events of its own (a few per sample)
+    hipEvent_t ev_mid[2] = {nullptr, nullptr};
+    DevBuf<u32> d_flag, d_hist, d_key[2], d_idx[2]; DevBuf<u64> d_cnt;
+    struct Rel { std::function<void()> f; ~Rel() { f(); } } rel{[&] {
+        d_flag.release(); d_hist.release(); d_key[0].release(); d_key[1].release(); d_idx[0].release(); d_idx[1].release(); d_cnt.release();
+        for (hipEvent_t e : ev_mid) if (e) (void)hipEventDestroy(e); }};
+    for (hipEvent_t &e : ev_mid) HIPCHK(hipEventCreate(&e));
+    auto elapsed = [&](hipEvent_t a, hipEvent_t b) { float ms = 0.f; (void)hipEventElapsedTime(&ms, a, b); return ms; };
+
+    // ---- keys never decrease: the store is grouped already
+    HIPCHK(d_flag.reserve(1, st));
+    HIPCHK(hipMemsetAsync(d_flag.p, 0, sizeof(u32), st));
+    HIPCHK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(covg::k_group_check, dim3(std::min<u32>((R + 255u) / 256u, 8192u)), dim3(256), 0, st, (const int32_t *)s->s_tid.p, R, nT, d_flag.p);
     HIPCHK(hipGetLastError());
-    const u32 end_off = (u32)n_cig_sel;
-    HIPCHK(hipMemcpyAsync(n_coff.p + S, &end_off, sizeof end_off, hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ev_mid[0], st));
+    s->grp_launches++;
+    u32 decreasing = 0;
+    HIPCHK(hipMemcpyAsync(&decreasing, d_flag.p, sizeof decreasing, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    std::swap(s->s_tid, n_tid); std::swap(s->s_pos, n_pos); std::swap(s->s_flag, n_flag); std::swap(s->s_mapq, n_mapq); std::swap(s->s_nmk, n_nmk);
-    std::swap(s->s_nm, n_nm); std::swap(s->s_lseq, n_lseq); std::swap(s->s_coff, n_coff); std::swap(s->s_cig, n_cig);
-    s->n_records = S; s->n_cigar = n_cig_sel; s->mates_valid = 0;      // the mate columns still describe the unselected store: spent
+    s->grp_ms[1] = elapsed(ev[0], ev_mid[0]);
+    if (!decreasing) { s->grp_ms[0] = s->grp_ms[1]; return COV_OK; }
+
+    // ---- stable LSD radix sort of the record indices
+    const u32 P = grpk::n_passes(nT), n_wg = grpk::n_tiles(R), n_hist = n_wg * grpk::RADIX;
+    const u32 nb = (n_hist + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    DevBuf<u32> d_bsum;
+    struct Rel1 { DevBuf<u32> &a; ~Rel1() { a.release(); } } rel1{d_bsum};
+    HIPCHK(d_hist.reserve(n_hist, st)); HIPCHK(d_bsum.reserve((size_t)nb + 1, st)); HIPCHK(d_cnt.reserve(2, st));
+    HIPCHK(d_idx[0].reserve(R, st));
+    if (P > 1) { HIPCHK(d_key[0].reserve(R, st)); HIPCHK(d_idx[1].reserve(R, st)); }
+    if (P > 2) HIPCHK(d_key[1].reserve(R, st));
+    HIPCHK(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(u64), st));
+    const int32_t *tid = s->s_tid.p;
+    for (u32 p = 0; p < P; p++) {
+        const bool first = p == 0, last = p + 1 == P;
+        const u32 *key_in = first ? nullptr : d_key[(p - 1) & 1u].p, *idx_in = first ? nullptr : d_idx[(p - 1) & 1u].p;
+        u32 *key_out = last ? nullptr : d_key[p & 1u].p, *idx_out = d_idx[p & 1u].p;
+        if (first) hipLaunchKernelGGL(covg::k_group_hist<true>, dim3(n_wg), dim3(256), 0, st, tid, key_in, R, nT, p, d_hist.p, n_wg);
+        else hipLaunchKernelGGL(covg::k_group_hist<false>, dim3(n_wg), dim3(256), 0, st, tid, key_in, R, nT, p, d_hist.p, n_wg);
+        const covg::HistVal hv{d_hist.p}; const covg::HistPut hp{d_hist.p};      // in place: a thread of the scan writes the items it read itself
+        hipLaunchKernelGGL((covp::k_scan_sums<covg::HistVal>), dim3(nb), dim3(256), 0, st, hv, n_hist, d_bsum.p);
+        hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_cnt.p + 1);
+        hipLaunchKernelGGL((covp::k_scan_apply<covg::HistVal, covg::HistPut>), dim3(nb), dim3(256), 0, st, hv, hp, n_hist, (const u32 *)d_bsum.p);
+        const dim3 g(n_wg), b(256);
+        if (first && last) hipLaunchKernelGGL((covg::k_group_scatter<true, true>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
+        else if (first) hipLaunchKernelGGL((covg::k_group_scatter<true, false>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
+        else if (last) hipLaunchKernelGGL((covg::k_group_scatter<false, true>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
+        else hipLaunchKernelGGL((covg::k_group_scatter<false, false>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
+        HIPCHK(hipGetLastError());
+        s->grp_launches += 5;
+    }
+    const u32 *order = d_idx[(P - 1) & 1u].p;
+    hipLaunchKernelGGL(covg::k_group_moved, dim3(std::min<u32>((R + 255u) / 256u, 4096u)), dim3(256), 0, st, order, R, d_cnt.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev_mid[1], st));
+    s->grp_launches++;
+    // ---- ONE gather of the store (and of the mate columns, which stay valid for cov_pair_filter_apply)
+    { const cov_status g = gather_store(s, order, R, mates); if (g != COV_OK) return g; }
+    HIPCHK(hipEventRecord(ev[1], st));
+    s->grp_launches += mates ? 4 : 3;
+    u64 moved = 0;
+    HIPCHK(hipMemcpyAsync(&moved, d_cnt.p, sizeof moved, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->grp_ms[0] = elapsed(ev[0], ev[1]); s->grp_ms[2] = elapsed(ev_mid[0], ev_mid[1]); s->grp_ms[3] = elapsed(ev_mid[1], ev[1]);
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] group: %u records, %u passes, %llu moved; order check %.3f ms, sort %.3f ms, gather %.3f ms\n", R, P, (unsigned long long)moved, s->grp_ms[1], s->grp_ms[2],
+                s->grp_ms[3]);
+    if (n_moved) *n_moved = moved;
+    s->finished = false; s->depth_all_valid = false; s->ev_fresh = -1;
     return COV_OK;
 }
 
@@ -2419,6 +2540,11 @@ cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist) {
 
 cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total, uint32_t *launches) {
     if (!s || k < 0 || k >= COV_K_COUNT) return COV_ERR_INVALID_ARG;
+    if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records
+        if (ms_total) *ms_total = s->grp_ms[0];
+        if (launches) *launches = s->grp_launches;
+        return COV_OK;
+    }
     if (ms_total) *ms_total = s->k_ms[k];
     if (launches) *launches = s->k_launches[k];
     return COV_OK;

@@ -80,6 +80,7 @@ struct Args {
     bool have_gff_feature_type = false;
     bool no_zeros = false, proper_pairs_only = false, exclude_supplementary = false, include_secondary = false;
     bool single_genome = false, have_separator = false, no_stream = false;
+    bool unsorted = false, verbose = false;      // --unsorted: the files need not be sorted by reference, records are grouped on the device (cov_group_records)
     char separator = '~';
     uint32_t min_aligned_length = 0, min_aligned_length_pair = 0;
     const char *min_pid = nullptr, *min_aligned_pct = nullptr, *min_pid_pair = nullptr, *min_aligned_pct_pair = nullptr;
@@ -261,6 +262,18 @@ void finish_sample(Run &R, cov_session *s, Sample &S, cov_summary &summ) {
     check(s, cov_finish(s, S.stats.data(), &summ));
 }
 
+// --unsorted: the records of the sample grouped by reference on the device, between the last record's arrival and the pair filter / finish
+void group_sample(Run &R, cov_session *s, const Sample &S) {
+    if (!R.a.unsorted) return;
+    uint64_t moved = 0;
+    check(s, cov_group_records(s, &moved));
+    if (R.a.verbose || timing_on()) {
+        double ms = 0; uint32_t launches = 0;
+        (void)cov_kernel_ms(s, COV_K_GROUP, &ms, &launches);
+        fprintf(stderr, "[coverm-amd] %s: --unsorted: %llu records moved while grouping by reference, %.3f ms on the device\n", S.stoit.c_str(), (unsigned long long)moved, ms);
+    }
+}
+
 // Decode + push + finish of one BAM (or one tid span of it) on one session.  Leaves the session finished.
 void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index, uint32_t span_count) {
     const Args &a = R.a;
@@ -300,6 +313,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         S.t_open = now() - t0;
         uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
+        check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
         // (an assembly's statistics are 128 B x millions of contigs: the array is obtained and touched beside the ingest, not behind it)
         std::future<void> stats_ahead;
         if (S.tlen.size() >= 65536 && !R.dev_genome) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
@@ -309,6 +323,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         if (rc == -2 && span_count > 1) throw SpanUnsorted(err);
         if (rc < 0) die(err);
         uint64_t pair_prim = 0; double t_pair = 0;
+        if (rc == 0) group_sample(R, s, S);
         if (rc == 0 && R.fp) {     // the reader-stage pair filter, on the device
             const double tp0 = now();
             cov_pair_filter pf; memset(&pf, 0, sizeof pf);
@@ -362,6 +377,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
             fprintf(stderr, "[coverm-amd] %s span %u/%u: stream read %.3fs inflate %.3fs parse %.3fs (coordinator waits: inflate %.3fs parse %.3fs), %llu records, buffers %.0f MB\n",
                     S.stoit.c_str(), span_index, span_count, t[0], t[1], t[2], t[3], t[4], (unsigned long long)S.n_records, S.peak_bytes / 1e6);
         }
+        group_sample(R, s, S);
         S.t_ingest = now() - t0;
         cov_summary summ;
         finish_sample(R, s, S, summ);
@@ -386,10 +402,12 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
         if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
         check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
+        check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
         uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, 0, 1, &nrec, tm, err, sizeof err);
         if (rc < 0) die(err);
         S.n_records = nrec;
+        if (rc == 0) group_sample(R, s, S);
         if (rc == 0 && R.fp) {
             cov_pair_filter pf; memset(&pf, 0, sizeof pf);
             pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
@@ -421,6 +439,9 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
     struct Closer { covh_bam *&p; ~Closer() { if (p) covh_bam_close(p); } } closer{bam};
     cov_batch selected; memset(&selected, 0, sizeof selected);
     struct Freer { cov_batch *b; ~Freer() { if (b->tid) covh_batch_free(b); } } freer{&selected};
+    cov_batch grouped; memset(&grouped, 0, sizeof grouped);
+    Freer freer_grouped{&grouped};
+    std::vector<int32_t> g_mtid; std::vector<uint32_t> g_qoff; std::string g_qnames;
     if (!have_records) {
         bam = covh_bam_open(S.path.c_str(), threads, R.fp ? 1 : 0, err, sizeof err);
         if (!bam) die(err);
@@ -428,7 +449,29 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         if (R.by_names) genome_table(R, S, mask);
         covh_bam_batch(bam, &batch);
         S.n_records = batch.n_records;
-        if (R.f.doing_filtering() && !(R.fs && !R.fp)) {
+        const int32_t *mtid = covh_bam_mtid(bam); const uint32_t *qoff = covh_bam_qname_off(bam); const char *qnames = covh_bam_qnames(bam);
+        const bool host_pair = R.f.doing_filtering() && !(R.fs && !R.fp);
+        if (a.unsorted && (host_pair || R.per_gene)) {
+            // the host's pair filter and the gene driver walk the whole-file arrays themselves: they see the sequence the device's grouping gives
+            uint64_t *order = nullptr, moved = 0;
+            if (covh_group_by_reference(batch.tid, batch.n_records, (uint32_t)S.tlen.size(), &order, &moved) != COV_OK) die("--unsorted: grouping the records on the host failed");
+            if (moved) {
+                const uint64_t n = batch.n_records;
+                const int src = covh_batch_select(&batch, order, n, threads, &grouped);
+                if (src != COV_OK) { covh_free(order); die("--unsorted: grouping the records on the host failed"); }
+                if (host_pair && qoff) {
+                    g_mtid.resize(n); g_qoff.resize(n + 1); g_qoff[0] = 0;
+                    for (uint64_t j = 0; j < n; j++) { g_mtid[j] = mtid[order[j]]; g_qoff[j + 1] = g_qoff[j] + (qoff[order[j] + 1] - qoff[order[j]]); }
+                    g_qnames.resize(g_qoff[n]);
+                    for (uint64_t j = 0; j < n; j++) memcpy(&g_qnames[g_qoff[j]], qnames + qoff[order[j]], g_qoff[j + 1] - g_qoff[j]);
+                    mtid = g_mtid.data(); qoff = g_qoff.data(); qnames = g_qnames.data();
+                }
+                batch = grouped;
+            }
+            covh_free(order);
+            if (a.verbose || timing_on()) fprintf(stderr, "[coverm-amd] %s: --unsorted: %llu records moved while grouping by reference on the host\n", S.stoit.c_str(), (unsigned long long)moved);
+        }
+        if (host_pair) {
             for (uint64_t i = 0; i < batch.n_records; i++) if (!(batch.flag[i] & 0x900)) S.prim++;   // filter.rs:129-131
             prim_from_host = true;
             covh_pair_filter pf; memset(&pf, 0, sizeof pf);
@@ -436,7 +479,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
             pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
             pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
             uint64_t *order = nullptr, n_order = 0;
-            const int prc = covh_pair_mode_order(&batch, covh_bam_mtid(bam), covh_bam_qname_off(bam), covh_bam_qnames(bam), &pf, threads, &order, &n_order);
+            const int prc = covh_pair_mode_order(&batch, mtid, qoff, qnames, &pf, threads, &order, &n_order);
             if (prc == COV_ERR_NM_MISSING) die("Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format");
             if (prc != COV_OK) die(prc == COV_ERR_NM_BADTYPE ? "Unexpected data type of NM aux tag" : "pair filter failed");
             const int src = covh_batch_select(&batch, order, n_order, threads, &selected);
@@ -451,6 +494,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
         check(s, cov_set_targets(s, nt, S.tlen.data()));
         if (R.by_names) set_genomes_or_mask(R, s, S, mask);
         check(s, cov_push_batch(s, &batch));
+        group_sample(R, s, S);      // (nothing moves when the host grouped the arrays above, or its pair filter selected from them)
     }
     S.t_ingest = now() - t0;
     cov_summary summ;
@@ -505,6 +549,7 @@ int run_filter(int argc, char **argv) {
         else if (k == "--min-mapq") f.mapq = (int)parse_uint(k, val(), 255);
         else if (k == "-t" || k == "--threads") threads = (int)parse_uint(k, val(), 65535);
         else if (k == "-v" || k == "--verbose" || k == "-q" || k == "--quiet") {}
+        else if (k == "--unsorted") die("filter does not take --unsorted: it streams its input in bounded memory and copies records byte for byte, in the input's order (sort the file by reference first)");
         else die("unknown argument " + k);
     }
     if (in.empty()) die("--bam-files is required");
@@ -536,7 +581,13 @@ int run_cli(int argc, char **argv) {
     if (argc >= 2 && !strcmp(argv[1], "filter")) return run_filter(argc, argv);
     if (argc < 2 || (strcmp(argv[1], "contig") && strcmp(argv[1], "genome"))) {
         fprintf(stderr, "usage: coverm-amd contig|genome -b <bam>... [-m <methods>...] [options]   (see src/cli.rs of CoverM for the flags; "
-                        "engine flags: --device N | --devices a,b,..., --no-stream)\n"
+                        "engine flags: --device N | --devices a,b,..., --no-stream, --unsorted)\n"
+                        "       --unsorted: the BAM / SAM files need not be sorted by reference (a mapper's output in read order).  The records of a file are\n"
+                        "       grouped on the device: references in header order, records without a reference last, the file's order kept inside a\n"
+                        "       reference.  The result is the result for the file with its records in that order: equal to the table of the\n"
+                        "       `samtools sort`ed file for every method but anir (whose f64 sums follow the record order); per-record errors name the\n"
+                        "       first offending record of that order.  The sample must fit the device's record store.  Not with filter, and not with\n"
+                        "       --devices when there are fewer files than devices.\n"
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n");
@@ -598,7 +649,9 @@ int run_cli(int argc, char **argv) {
             if (a.devices.empty()) die("--devices needs a list such as 0,1,2,3 or 0-7");
         }
         else if (k == "--no-stream") a.no_stream = true;
-        else if (k == "-v" || k == "--verbose" || k == "-q" || k == "--quiet") {}   // logging verbosity: nothing to tune here
+        else if (k == "--unsorted") a.unsorted = true;
+        else if (k == "-v" || k == "--verbose") a.verbose = true;      // (logging verbosity: only --unsorted has a line to print)
+        else if (k == "-q" || k == "--quiet") {}
         else die("unknown argument " + k);
     }
     {   // clap's conflicts_with table for the genome sources (cli.rs:1878-1990); --genome-definition beside --genome-fasta-list is
@@ -616,6 +669,9 @@ int run_cli(int argc, char **argv) {
     }
     if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
     if (a.devices.empty()) a.devices.push_back(0);
+    if (a.unsorted && a.devices.size() > 1 && a.bams.size() < a.devices.size())
+        die("--unsorted cannot be used with --devices when there are fewer BAM files than devices: a file would be cut into tid spans, which only a file sorted by reference has "
+            "(give at least as many files as devices, or one device)");
     R.contig = a.mode == "contig";
     const bool contig = R.contig;
     if (a.methods.empty()) a.methods.push_back(contig ? "mean" : "relative_abundance");   // cli.rs:2521, 2048

@@ -23,6 +23,7 @@
 
 #include "../../include/coverm_host.h"
 #include "reader_filter.h"
+#include "group_rank_core.h"
 
 namespace {
 
@@ -205,6 +206,24 @@ int covh_reader_filter_order(const cov_batch *b, const int32_t *mtid, const uint
 
 // Gathers the records `order[0..n)` of `src` into a new batch (page-locked when a device is usable): what the scan
 // receives after the reader stage.  Release with covh_batch_free.
+// Stable counting sort of the record indices by the key cov_group_records sorts by (group_rank_core.h): order[new] = old.
+int covh_group_by_reference(const int32_t *tid, uint64_t n, uint32_t n_targets, uint64_t **order_out, uint64_t *n_moved) {
+    if (!order_out || (n && !tid)) return COV_ERR_INVALID_ARG;
+    *order_out = nullptr;
+    if (n_moved) *n_moved = 0;
+    uint64_t *order = (uint64_t *)malloc((size_t)std::max<uint64_t>(n, 1) * sizeof(uint64_t));
+    if (!order) return COV_ERR_INVALID_ARG;
+    std::vector<uint64_t> start((size_t)n_targets + 2, 0);
+    for (uint64_t i = 0; i < n; i++) start[(size_t)grpk::key_of(tid[i], n_targets) + 1]++;
+    for (size_t k = 1; k < start.size(); k++) start[k] += start[k - 1];
+    for (uint64_t i = 0; i < n; i++) order[start[grpk::key_of(tid[i], n_targets)]++] = i;
+    uint64_t moved = 0;
+    for (uint64_t j = 0; j < n; j++) moved += order[j] != j;
+    if (n_moved) *n_moved = moved;
+    *order_out = order;
+    return COV_OK;
+}
+
 int covh_batch_select(const cov_batch *src, const uint64_t *order, uint64_t n, int threads, cov_batch *out) {
     if (!src || !out || (n && !order)) return COV_ERR_INVALID_ARG;
     auto alloc = [](size_t bytes) -> void * { void *p = cov_host_alloc(bytes ? bytes : 1); return p ? p : malloc(bytes ? bytes : 1); };

@@ -229,6 +229,22 @@ class Session:
         self._check(self._lib.cov_kernel_ms(self._h, native.K_GENOME, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def group_records(self):
+        """cov_group_records: the records of every reference made contiguous on the device (stable: references in ascending tid order, records
+        without a reference last, the file's order kept inside a reference), for a sample that is not sorted by reference.  Between the
+        last push / ingest and the pair filter / finish.  Returns the number of records whose index changed (0: the store was grouped
+        already and was left alone)."""
+        n = C.c_uint64(0)
+        self._check(self._lib.cov_group_records(self._h, C.byref(n)))
+        return int(n.value)
+
+    def group_kernel_ms(self):
+        """(ms, launches) of the last group_records (COV_K_GROUP)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_GROUP, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def store_spills(self):
         return int(self._lib.cov_store_spills(self._h))
 

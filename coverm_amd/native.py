@@ -16,8 +16,9 @@ ERR_UNSORTED, ERR_NM_MISSING, ERR_NM_BADTYPE, ERR_POS_OOB, ERR_BAD_CIGAR, ERR_BA
 ERR_INVALID_ARG, ERR_HIP, ERR_STATE = 16, 17, 18
 WANT_HIST, WANT_IDENTITY = 1, 2
 WANT_IDENTITY_PRIMARY_ONLY, WANT_IDENTITY_NONSUPP_ONLY = 4, 8
-K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 8
+K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 9
 K_GENOME = 7      # cov_set_genomes: reduce + histogram merge + estimate over genomes (Session.genome_kernel_ms)
+K_GROUP = 8       # cov_group_records: order check + sort passes + gather of the last call (Session.group_kernel_ms)
 KERNEL_NAMES = {K_PREP: "k_prep", K_RANGES: "k_ranges", K_PILEUP: "k_pileup", K_IDENTITY: "k_identity",
                 K_HIST: "k_hist", K_HIST_COMPACT: "k_hist_compact", K_ESTIMATE: "k_estimate"}
 
@@ -116,6 +117,8 @@ def lib():
     L.cov_fetch_genome_stats.argtypes = [C.c_void_p, C.c_void_p]
     L.cov_store_spills.argtypes = [C.c_void_p]
     L.cov_store_spills.restype = C.c_uint32
+    L.cov_group_records.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+    L.cov_ingest_want_grouping.argtypes = [C.c_void_p, C.c_int]
     _lib = L
     return L
 

@@ -262,6 +262,11 @@ int covh_reader_filter_order(const cov_batch *b, const int32_t *mtid, const uint
 int covh_bam_filter_file(const char *in_path, const char *out_path, const covh_pair_filter *f, int filter_pairs, int include_supplementary,
                          int include_secondary, int filter_out, int level, int threads, uint64_t *n_in, uint64_t *n_out, char *err, size_t errcap);
 void covh_free(void *p);
+/* --unsorted on the host (whole-file arrays: SAM text, --no-stream, files the device ingest declines, ahead of covh_pair_mode_order and the
+ * gene driver): the stable order cov_group_records gives on the device — order[new] = old, references in ascending tid order, records
+ * without a reference (tid < 0 or >= n_targets) last, the input's order kept inside a reference.  *order_out (n entries) is released with
+ * covh_free; *n_moved = entries with order[j] != j.  Gather with covh_batch_select. */
+int covh_group_by_reference(const int32_t *tid, uint64_t n, uint32_t n_targets, uint64_t **order_out, uint64_t *n_moved);
 /* Gathers records order[0..n) of src into a new batch (page-locked memory when a device is usable). */
 int covh_batch_select(const cov_batch *src, const uint64_t *order, uint64_t n, int threads, cov_batch *out);
 void covh_batch_free(cov_batch *b);

@@ -150,7 +150,8 @@ typedef enum {
     COV_K_HIST_COMPACT = 5, /* compact histogram (behind the pileup) */
     COV_K_ESTIMATE = 6, /* CoverageEstimator::calculate_coverage of every contig (cov_set_estimators) */
     COV_K_GENOME = 7,   /* cov_set_genomes: contigs reduced into genomes, histograms merged, calculate_coverage of every genome */
-    COV_K_COUNT = 8
+    COV_K_GROUP = 8,    /* cov_group_records: order check, sort passes and gather of the last call, summed (not part of a finish) */
+    COV_K_COUNT = 9
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -259,6 +260,21 @@ typedef struct {
 } cov_pair_filter;
 cov_status cov_ingest_want_mates(cov_session *s, int on);
 cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint64_t *n_selected, uint64_t *n_primary);
+/* ---- records grouped by reference on the device, for a BAM / SAM that is not sorted by reference (a mapper's output in read order).
+ * The pipeline needs the records of one reference to be contiguous, not sorted by position; one stable sort of the record indices by tid
+ * and one gather of the store do that in milliseconds where `samtools sort` takes minutes.
+ * Between the last push / cov_ingest_end and cov_pair_filter_apply / cov_finish / cov_finish_genomes / cov_copy_records:
+ * makes the records of every reference contiguous, references in ascending tid order, records without a reference last,
+ * the file's order kept inside a reference (stable).  *n_moved = records whose index changed (0: the store was grouped
+ * already and was not touched).  Every result afterwards is the result for the file whose records are the input's records in that
+ * order; per-record errors are reported for the first offending record of that order.
+ * COV_ERR_STATE: an adopted device batch (cov_push_batch_device), a tid span (cov_ingest_span with anything but the whole key range),
+ * after a spill of the bounded record store (a sample that is not sorted by reference must fit the store: the spill has already judged
+ * the order).  Needs room for a second copy of the store while it runs.
+ * cov_ingest_want_grouping(s, 1) before cov_ingest_begin announces it: a file whose keys decrease is then not handed back to the CPU
+ * reader for the pair filter's sake (cov_ingest_want_mates); span ingests keep refusing such a file. */
+cov_status cov_ingest_want_grouping(cov_session *s, int on);
+cov_status cov_group_records(cov_session *s, uint64_t *n_moved);
 /* Test hook: the session's own record store copied back into caller-sized host arrays (host == NULL: only the counts). */
 cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_records, uint64_t *n_cigar);
 
