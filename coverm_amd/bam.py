@@ -181,6 +181,11 @@ def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, 
     timing dict); raises IngestFallback when the file needs the CPU reader.  span = (index, count): one tid span of the file
     (covh_bam_gpu_ingest_span; the spans of a file partition its records in order).  group: the file need not be sorted by reference —
     the ingest is told that grouping follows (cov_ingest_want_grouping) and Session.group_records() runs behind it."""
+    if tuple(span) == (0, 1):
+        with open(path, "rb") as fh:
+            if fh.read(2) != b"\x1f\x8b":      # not BGZF: SAM text, decoded on the device as well (cov_sam_*)
+                names, lens, n, t = sam_ingest(session, path, mask=mask, want_mates=want_mates, group=group)
+                return names, lens, n, t
     L = _lib()
     if not getattr(L, "_ingest_bound", False):
         L.covh_bam_read_header.restype = C.c_void_p
@@ -228,6 +233,57 @@ def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, 
         L.covh_bam_header_free(hd)
 
 
+def sam_ingest(session, path, mask=None, want_mates: bool = False, group: bool = False):
+    """SAM text decoded on the device (covh_sam_open + covh_sam_gpu_ingest over cov_sam_*), window by window as the bytes are read.  path: a
+    file, a FIFO, "-" for standard input, or an object with fileno() (a pipe's read end), which is read through /dev/fd.  Sets the session's
+    targets from the @SQ lines.  Returns (ref_names, ref_lens, n_records, timing dict); raises IngestFallback for irregular text (a header
+    line behind the first alignment line), IOError for anything that is not SAM text and for malformed lines (the message names the line)."""
+    L = _lib()
+    if not getattr(L, "_sam_bound", False):
+        L.covh_sam_open.restype = C.c_void_p
+        L.covh_sam_open.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+        L.covh_sam_close.argtypes = [C.c_void_p]
+        L.covh_sam_close.restype = None
+        for f in (L.covh_sam_kind, L.covh_sam_is_pipe):
+            f.argtypes = [C.c_void_p]
+        L.covh_sam_n_targets.restype = C.c_uint32
+        L.covh_sam_n_targets.argtypes = [C.c_void_p]
+        L.covh_sam_target_name.restype = C.c_char_p
+        L.covh_sam_target_name.argtypes = [C.c_void_p, C.c_uint32]
+        L.covh_sam_target_len.restype = C.c_uint64
+        L.covh_sam_target_len.argtypes = [C.c_void_p, C.c_uint32]
+        L.covh_sam_gpu_ingest.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+        L._sam_bound = True
+    if hasattr(path, "fileno"):
+        path = "/dev/fd/%d" % path.fileno()
+    err = C.create_string_buffer(512)
+    h = L.covh_sam_open(os.fsencode(path), err, 512)
+    if not h:
+        raise IOError(err.value.decode() or "cannot read %s" % path)
+    try:
+        kind = L.covh_sam_kind(h)
+        if kind != 0:
+            raise IOError("%s: %s" % (path, "BGZF (a BAM), not SAM text" if kind == 1 else "not text (NUL bytes in the first piece)"))
+        nt = L.covh_sam_n_targets(h)
+        names = [L.covh_sam_target_name(h, i).decode() for i in range(nt)]
+        lens = np.asarray([L.covh_sam_target_len(h, i) for i in range(nt)], dtype=np.int64)
+        session.set_targets(lens, mask)
+        if session._lib.cov_ingest_want_mates(session._h, int(want_mates)) != 0 or session._lib.cov_ingest_want_grouping(session._h, int(group)) != 0:
+            raise RuntimeError("cov_ingest_want_mates / cov_ingest_want_grouping failed")
+        n = C.c_uint64(0)
+        t = (C.c_double * 4)()
+        rc = L.covh_sam_gpu_ingest(h, 1, session._h, C.byref(n), t, err, 512)
+        if rc == 1:
+            raise IngestFallback(err.value.decode())
+        if rc != 0:
+            raise IOError(err.value.decode())
+        if group:
+            session.group_records()
+        return names, lens, int(n.value), dict(read=t[0], slot_wait=t[1], feed=t[2], total=t[3])
+    finally:
+        L.covh_sam_close(h)
+
+
 class _DevPairFilter(C.Structure):   # cov_pair_filter
     _fields_ = [("filter_single", C.c_int32), ("min_mapq", C.c_uint8), ("pad", C.c_uint8 * 3), ("min_aligned_length_single", C.c_uint32),
                 ("min_percent_identity_single", C.c_float), ("min_aligned_percent_single", C.c_float), ("min_aligned_length_pair", C.c_uint32),
@@ -273,6 +329,17 @@ def session_records(session) -> RecordBatch:
     cb.n_records = n
     assert L.cov_copy_records(session._h, C.byref(cb), None, None) == 0
     return rb
+
+
+def session_mates(session, n_records: int):
+    """Test hook (cov_copy_mates): (mtid, qh1, qh2) of the records an ingest with want_mates left in the session's store."""
+    L = _lib()
+    L.cov_copy_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    mtid, qh1, qh2 = np.zeros(n_records, np.int32), np.zeros(n_records, np.uint64), np.zeros(n_records, np.uint32)
+    rc = L.cov_copy_mates(session._h, mtid.ctypes.data, qh1.ctypes.data, qh2.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("cov_copy_mates: %d" % rc)
+    return mtid, qh1, qh2
 
 
 def write_bam(path: str, names, lens, batch: RecordBatch, with_seq=True, level: int = 1, threads: int = None):

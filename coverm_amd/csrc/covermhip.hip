@@ -7,6 +7,7 @@
 #include "genome_kernels.hip.h"
 #include "ingest_kernels.hip.h"
 #include "group_kernels.hip.h"
+#include "sam_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -257,6 +258,19 @@ struct cov_session {
     hipEvent_t ing_ev[COV_INGEST_SLOTS] = {}, ing_fed = nullptr;
     double ing_s_alloc = 0;     // host seconds inside device allocations of the ingest
     double ing_s_part[4] = {0, 0, 0, 0};     // ... inside ingest_drain / launch_round / the upload calls / event waits (COVERM_CLI_TIMING)
+
+    // SAM text ingest (cov_sam_*): an ingest like the BGZF one as far as the session's state goes (ing_active, ing_rec_total, the slots' events,
+    // the upload stream, cov_ingest_abort), with sam_active on top.  Two text buffers of one window each take the uploads in turn; masks and
+    // line arrays exist once (the windows' kernels run in order on the session stream).
+    bool sam_active = false, sam_seen_record = false, sam_decode_timed = false;
+    uint64_t sam_window = 0, sam_expected = 0, sam_lines = 0, sam_bytes = 0, sam_err_line = 0;
+    uint32_t sam_err = 0, sam_k = 0;
+    DevBuf<uint8_t> m_text[2], m_blob;
+    DevBuf<u64> m_nl, m_tab, m_res, m_noff;
+    DevBuf<u32> m_line_end, m_cnt, m_rec_idx, m_cig_idx, m_bsum[3], m_slots;
+    samc::Table m_names{};
+    hipEvent_t sam_buf_free[2] = {}, sam_ev[4] = {};
+    float sam_ms = 0.f; uint32_t sam_launches = 0;
 
     // results of the last finish
     bool finished = false;
@@ -579,6 +593,8 @@ static void ingest_free_buffers(cov_session *s) {
     for (int k = 0; k < 3; k++) { s->g_win[k].release(); s->g_cwin[k].release(); }
     for (int k = 0; k < 4; k++) { s->g_seg[k].release(); s->g_recbase[k].release(); s->g_cigbase[k].release(); }
     s->g_tok.release(); s->g_ntok.release(); s->g_tok2.release(); s->g_ntok2.release();
+    for (auto &b : s->m_text) b.release();      // (the SAM text ingest's window: text, masks, line arrays)
+    s->m_nl.release(); s->m_tab.release(); s->m_line_end.release(); s->m_cnt.release(); s->m_rec_idx.release(); s->m_cig_idx.release();
 }
 
 void cov_destroy(cov_session *s) {
@@ -613,6 +629,11 @@ void cov_destroy(cov_session *s) {
     s->h_blocks = nullptr;
     if (s->ing_copy) { (void)hipStreamSynchronize(s->ing_copy); (void)hipStreamDestroy(s->ing_copy); }
     for (int k = 0; k < COV_INGEST_SLOTS; k++) if (s->ing_ev[k]) (void)hipEventDestroy(s->ing_ev[k]);
+    for (hipEvent_t e : s->sam_buf_free) if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->sam_ev) if (e) (void)hipEventDestroy(e);
+    for (auto &b : s->m_text) b.release();
+    s->m_blob.release(); s->m_nl.release(); s->m_tab.release(); s->m_res.release(); s->m_noff.release(); s->m_line_end.release(); s->m_cnt.release();
+    s->m_rec_idx.release(); s->m_cig_idx.release(); s->m_slots.release(); for (auto &b : s->m_bsum) b.release();
     if (s->ing_fed) (void)hipEventDestroy(s->ing_fed);
     s->d_res.release(); s->d_ctg.p = nullptr; s->d_glob.p = nullptr; s->d_desc.release(); s->d_gather.release();
     if (s->h_gather) (void)hipHostFree(s->h_gather);
@@ -815,7 +836,7 @@ cov_status cov_ingest_abort(cov_session *s) {
     if (!s) return COV_ERR_INVALID_ARG;
     if (!s->ing_active) return COV_OK;
     HIPCHK(hipSetDevice(s->cfg.device));
-    s->ing_active = false;
+    s->ing_active = false; s->sam_active = false;
     for (hipStream_t st : {s->ing_copy, s->stream, s->ing_aux, s->ing_parse, s->ing_ext})
         if (st) HIPCHK(hipStreamSynchronize(st));
     s->ing_rec_total = s->ing_cig_total = 0; s->ing_round_n = 0; s->ing_fail = 0;
@@ -1645,6 +1666,7 @@ static inline const InflateKernel &inflate_kernel(cov_session *s) { return s->in
 
 cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t first_record_offset, int check_crc) {
     if (!s) return COV_ERR_INVALID_ARG;
+    if (s->sam_active) { s->err = "cov_ingest_begin: a SAM text ingest is open (cov_sam_end or cov_ingest_abort first)"; return COV_ERR_STATE; }
     covr::Range rr("ingest: buffers, streams, events (cov_ingest_begin)");
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(ingest_prep_wait(s));
@@ -1918,6 +1940,7 @@ static cov_status ingest_upload_table(cov_session *s, u64 from) {
 cov_status cov_ingest_feed(cov_session *s, int slot, const void *host_bytes, uint64_t file_offset, uint64_t n_bytes,
                            const cov_bgzf_block *blocks, uint32_t n_blocks) {
     if (!s || !s->ing_active || slot < 0 || slot >= COV_INGEST_SLOTS || (n_bytes && !host_bytes) || (n_blocks && !blocks)) return COV_ERR_INVALID_ARG;
+    if (s->sam_active) { s->err = "cov_ingest_feed: a SAM text ingest is open (cov_sam_feed / cov_sam_end)"; return COV_ERR_STATE; }
     if (file_offset + n_bytes > s->ing_comp) { s->err = "cov_ingest_feed: bytes beyond the size given to cov_ingest_begin"; return COV_ERR_INVALID_ARG; }
     covr::Range rr("ingest: window upload (cov_ingest_feed)");
     HIPCHK(hipSetDevice(s->cfg.device));
@@ -2001,6 +2024,7 @@ cov_status cov_ingest_end(cov_session *s, uint64_t *n_records_out) {
 }
 static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out) {
     if (!s || !s->ing_active) return COV_ERR_INVALID_ARG;
+    if (s->sam_active) { s->err = "cov_ingest_end: a SAM text ingest is open (cov_sam_end)"; return COV_ERR_STATE; }
     covr::Range rr("ingest: last rounds + parse (cov_ingest_end)");
     s->ing_active = false;
     HIPCHK(hipSetDevice(s->cfg.device));
@@ -2059,6 +2083,212 @@ static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out) {
         s->finished = false;
     }
     if (n_records_out) *n_records_out = s->ing_rec_total;
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- SAM text ingest (covermhip.h cov_sam_*, sam_kernels.hip.h)
+// One window = one cov_sam_feed: upload on the copy stream, then on the session stream masks -> line scan -> (the host learns the number of
+// lines) -> per-line counts -> two scans -> (the host learns records, CIGAR words and the first error) -> decode into the store.  The host
+// waits twice per window; the upload of the next window runs beside the decode of this one (two text buffers).
+static cov_status sam_fail(cov_session *s) {
+    const u32 e = s->sam_err; const u64 line = s->sam_err_line;
+    (void)cov_ingest_abort(s);      // drains the device, appends nothing, leaves the session ready for cov_push_batch
+    const std::string at = " (line " + std::to_string(line) + ")";
+    switch (e) {
+    case samc::ERR_MALFORMED: s->err = "malformed SAM line" + at; return COV_ERR_INVALID_ARG;
+    case samc::ERR_CIGAR_OPS: s->err = "SAM line with a CIGAR of more than 65535 operations" + at; return COV_ERR_INVALID_ARG;
+    case samc::ERR_LINE_LONG: s->err = "SAM line longer than the decode window of " + std::to_string(s->sam_window) + " bytes" + at; return COV_ERR_INVALID_ARG;
+    default: s->err = "SAM text: a header line (@) behind the first alignment line" + at + " (handing the file to the CPU reader)"; return COV_ERR_INGEST_FALLBACK;
+    }
+}
+constexpr u32 SAM_ERR_AT_LINE = 4u;
+
+uint64_t cov_sam_window_bytes(const cov_session *s) { return s ? s->sam_window : 0; }
+
+cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t *name_off, uint32_t n_names, uint64_t expected_bytes) {
+    if (!s || (n_names && (!names_blob || !name_off))) return COV_ERR_INVALID_ARG;
+    if (s->ing_active) { s->err = "cov_sam_begin: an ingest is still open (cov_ingest_end / cov_sam_end or cov_ingest_abort first)"; return COV_ERR_STATE; }
+    HIPCHK(hipSetDevice(s->cfg.device));
+    HIPCHK(ingest_prep_wait(s));
+    if (!s->ing_copy) HIPCHK(ingest_prepare_(s));
+    if (s->adopted) {  // materialise an adopted device batch into the owned store first
+        cov_batch ab = s->adopted_batch;
+        s->adopted = false; s->n_records = 0; s->n_cigar = 0;
+        cov_status a = append(s, &ab, true);
+        if (a) return a;
+    }
+    hipStream_t st = s->stream;
+    HIPCHK(hipStreamSynchronize(st));
+    u64 W = 32ull << 20;
+    { long long v; if (covknob::get("sam_window_bytes", v) && v >= 256) W = (u64)v; }      // tests: many small windows
+    W = std::min<u64>(W, 1ull << 30);
+    s->sam_window = W;
+    const size_t text_cap = (size_t)((W + 1 + samc::MASK_WG_BYTES - 1) / samc::MASK_WG_BYTES * samc::MASK_WG_BYTES), n_words = (size_t)((W + 1 + 63) / 64);
+    for (int j = 0; j < 2; j++) {
+        HIPCHK(s->m_text[j].reserve(text_cap, st));
+        if (!s->sam_buf_free[j]) HIPCHK(hipEventCreateWithFlags(&s->sam_buf_free[j], hipEventDisableTiming));
+    }
+    for (hipEvent_t &e : s->sam_ev) if (!e) HIPCHK(hipEventCreate(&e));
+    HIPCHK(s->m_nl.reserve(n_words, st)); HIPCHK(s->m_tab.reserve(n_words, st)); HIPCHK(s->m_res.reserve(covs::RES_WORDS, st));
+    HIPCHK(s->m_bsum[0].reserve((n_words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK + 1, st));
+    // the reference names: blob, offsets, and the open-addressing table over them (sam_parse_core.h)
+    s->m_names = samc::Table{nullptr, 0u, nullptr, nullptr};
+    if (n_names) {
+        const u64 blob_bytes = name_off[n_names];
+        const u32 slots = samc::table_size(n_names);
+        std::vector<u32> h_slots(slots, 0u);
+        for (u32 i = 0; i < n_names; i++) samc::table_insert(h_slots.data(), slots - 1u, (const uint8_t *)names_blob, (const u64 *)name_off, i);
+        HIPCHK(s->m_blob.reserve((size_t)blob_bytes + 8, st)); HIPCHK(s->m_noff.reserve((size_t)n_names + 1, st)); HIPCHK(s->m_slots.reserve(slots, st));
+        if (blob_bytes) HIPCHK(hipMemcpyAsync(s->m_blob.p, names_blob, blob_bytes, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->m_noff.p, name_off, ((size_t)n_names + 1) * sizeof(u64), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->m_slots.p, h_slots.data(), (size_t)slots * sizeof(u32), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        s->m_names = samc::Table{s->m_slots.p, slots - 1u, s->m_blob.p, s->m_noff.p};
+    }
+    s->ing_batch = 0; s->ing_extracted = 0; s->ing_rec_total = s->ing_cig_total = 0; s->ing_fail = 0; s->ing_rec_spilled = 0; s->ing_round_n = 0;
+    s->sam_expected = expected_bytes; s->sam_lines = 0; s->sam_bytes = 0; s->sam_err = 0; s->sam_err_line = 0; s->sam_k = 0;
+    s->sam_seen_record = false; s->sam_decode_timed = false; s->sam_ms = 0.f; s->sam_launches = 0;
+    s->ing_active = true; s->sam_active = true;
+    return COV_OK;
+}
+
+cov_status cov_sam_slot_wait(cov_session *s, int slot) { return cov_ingest_slot_wait(s, slot); }
+
+static float sam_elapsed(hipEvent_t a, hipEvent_t b) { float ms = 0.f; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.f; }
+
+cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64_t n_bytes) {
+    if (!s || slot < 0 || slot >= COV_INGEST_SLOTS || (n_bytes && !host_bytes)) return COV_ERR_INVALID_ARG;
+    if (!s->sam_active) { s->err = "cov_sam_feed: no SAM text ingest is open (cov_sam_begin)"; return COV_ERR_STATE; }
+    if (n_bytes == 0) return COV_OK;
+    covr::Range rr("sam: window upload + decode (cov_sam_feed)");
+    HIPCHK(hipSetDevice(s->cfg.device));
+    const u64 W = s->sam_window;
+    if (n_bytes > W) { s->err = "cov_sam_feed: a piece larger than the window (cov_sam_window_bytes)"; return COV_ERR_INVALID_ARG; }
+    const uint8_t *hb = (const uint8_t *)host_bytes;
+    const bool open_end = hb[n_bytes - 1] != '\n';
+    if (open_end && n_bytes == W && !memchr(hb, '\n', n_bytes)) {      // a whole window without a line end
+        s->sam_err = samc::ERR_LINE_LONG; s->sam_err_line = s->sam_lines + 1;
+        return sam_fail(s);
+    }
+    const u32 j = s->sam_k & 1u;
+    uint8_t *text = s->m_text[j].p;
+    hipStream_t st = s->stream, cp = s->ing_copy;
+    if (s->sam_k >= 2) HIPCHK(hipStreamWaitEvent(cp, s->sam_buf_free[j], 0));      // the decode of window k - 2 has read this buffer
+    HIPCHK(hipMemcpyAsync(text, hb, n_bytes, hipMemcpyHostToDevice, cp));
+    u64 n = n_bytes;
+    if (open_end) { HIPCHK(hipMemsetAsync(text + n, '\n', 1, cp)); n++; }      // a last line without its line end is a record
+    HIPCHK(hipEventRecord(s->ing_ev[slot], cp));
+    HIPCHK(hipStreamWaitEvent(st, s->ing_ev[slot], 0));
+    u64 *res = s->m_res.p;
+    HIPCHK(hipMemsetAsync(res, 0xff, covs::RES_WORDS * sizeof(u64), st));
+    HIPCHK(hipMemsetAsync(res + covs::RES_LAST_AT, 0, sizeof(u64), st));
+    HIPCHK(hipEventRecord(s->sam_ev[0], st));
+    const u32 n_words = (u32)((n + 63) / 64), nbw = (n_words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    hipLaunchKernelGGL(covs::k_sam_masks, dim3((u32)((n + samc::MASK_WG_BYTES - 1) / samc::MASK_WG_BYTES)), dim3(256), 0, st, (const uint8_t *)text, n, s->m_nl.p, s->m_tab.p);
+    const covs::NlPop nlp{s->m_nl.p};
+    hipLaunchKernelGGL((covp::k_scan_sums<covs::NlPop>), dim3(nbw), dim3(256), 0, st, nlp, n_words, s->m_bsum[0].p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[0].p, nbw, res + covs::RES_LINES);
+    HIPCHK(hipGetLastError());
+    u64 *h = s->h_winres;
+    HIPCHK(hipMemcpyAsync(h, res, covs::RES_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    const u32 n_lines = (u32)h[covs::RES_LINES], nbl = (n_lines + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    HIPCHK(s->m_line_end.reserve(n_lines, st)); HIPCHK(s->m_cnt.reserve(n_lines, st)); HIPCHK(s->m_rec_idx.reserve(n_lines, st)); HIPCHK(s->m_cig_idx.reserve(n_lines, st));
+    HIPCHK(s->m_bsum[1].reserve((size_t)nbl + 1, st)); HIPCHK(s->m_bsum[2].reserve((size_t)nbl + 1, st));
+    const covs::Lines L{text, s->m_tab.p, s->m_line_end.p, n_lines};
+    hipLaunchKernelGGL((covp::k_scan_apply<covs::NlPop, covs::LineEmit>), dim3(nbw), dim3(256), 0, st, nlp, covs::LineEmit{s->m_nl.p, s->m_line_end.p}, n_words, (const u32 *)s->m_bsum[0].p);
+    hipLaunchKernelGGL(covs::k_sam_count, dim3((n_lines + 255u) / 256u), dim3(256), 0, st, L, s->m_cnt.p, res);
+    const covs::IsRec isr{s->m_cnt.p}; const covs::NCig ncg{s->m_cnt.p};
+    hipLaunchKernelGGL((covp::k_scan_sums<covs::IsRec>), dim3(nbl), dim3(256), 0, st, isr, n_lines, s->m_bsum[1].p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[1].p, nbl, res + covs::RES_RECORDS);
+    hipLaunchKernelGGL((covp::k_scan_apply<covs::IsRec, covs::Put>), dim3(nbl), dim3(256), 0, st, isr, covs::Put{s->m_rec_idx.p}, n_lines, (const u32 *)s->m_bsum[1].p);
+    hipLaunchKernelGGL((covp::k_scan_sums<covs::NCig>), dim3(nbl), dim3(256), 0, st, ncg, n_lines, s->m_bsum[2].p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[2].p, nbl, res + covs::RES_CIGAR);
+    hipLaunchKernelGGL((covp::k_scan_apply<covs::NCig, covs::Put>), dim3(nbl), dim3(256), 0, st, ncg, covs::Put{s->m_cig_idx.p}, n_lines, (const u32 *)s->m_bsum[2].p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->sam_ev[1], st));
+    HIPCHK(hipMemcpyAsync(h, res, covs::RES_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->sam_ms += sam_elapsed(s->sam_ev[0], s->sam_ev[1]); s->sam_launches += 11;
+    if (s->sam_decode_timed) { s->sam_ms += sam_elapsed(s->sam_ev[2], s->sam_ev[3]); s->sam_decode_timed = false; }      // the previous window's decode
+    const u64 nrec = h[covs::RES_RECORDS], ncig = h[covs::RES_CIGAR], err = h[covs::RES_ERR], first_rec = h[covs::RES_FIRST_REC], last_at = h[covs::RES_LAST_AT];
+    {   // the first offending line in file order: a malformed record, or a header line behind a record
+        u64 bad_line = ~0ull; u32 bad = 0;
+        if (err != ~0ull) { bad_line = err >> 8; bad = (u32)(err & 0xffu); }
+        if (last_at && (s->sam_seen_record || (first_rec != ~0ull && last_at - 1 > first_rec)) && last_at - 1 < bad_line) { bad_line = last_at - 1; bad = SAM_ERR_AT_LINE; }
+        // (last_at is the LAST header line of the window: the verdict is right, the line named may be a later one of several)
+        if (bad) { s->sam_err = bad; s->sam_err_line = s->sam_lines + bad_line + 1; return sam_fail(s); }
+    }
+    if (nrec) s->sam_seen_record = true;
+    s->sam_lines += n_lines; s->sam_bytes += n_bytes;
+    u64 R = s->n_records + s->ing_rec_total, Cg = s->n_cigar + s->ing_cig_total;
+    if (nrec && R && !s->want_mates && (R + nrec > s->cap_records || Cg + ncig > s->cap_cigar)) {
+        // bounded store, as ingest_drain does it: what has been decoded so far becomes the store's content, the complete contigs leave
+        // for the host, the contig in flight moves to the front; this window's records follow it
+        const u32 end_off = (u32)Cg;
+        HIPCHK(hipMemcpyAsync(s->s_coff.p + R, &end_off, sizeof end_off, hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        s->n_records = R; s->n_cigar = Cg;
+        s->ing_rec_spilled += s->ing_rec_total; s->ing_rec_total = 0; s->ing_cig_total = 0;
+        bool progress = false;
+        const cov_status sp = spill_store(s, progress);
+        if (sp != COV_OK) return sp;
+        R = s->n_records; Cg = s->n_cigar;
+    }
+    if (R + nrec >= 0xfffffff0ull || Cg + ncig >= 0xfffffff0ull) {
+        (void)cov_ingest_abort(s);
+        s->err = "more than 2^32 records or CIGAR words of one reference in the record store"; return COV_ERR_INVALID_ARG;
+    }
+    if (nrec) {
+        u64 Nn = R + nrec, Cn = Cg + ncig + 1;
+        if (s->sam_k == 0 && s->sam_expected > n_bytes) {      // first of several windows of a file whose size is known: size the store once
+            const double scale = (double)s->sam_expected / (double)n_bytes * 1.1;
+            Nn = std::max<u64>(Nn, std::min<u64>(R + (u64)((double)nrec * scale) + 1024, std::min<u64>(s->cap_records + 1024, 0xfffffff0ull)));
+            Cn = std::max<u64>(Cn, std::min<u64>(Cg + (u64)((double)ncig * scale) + 1024, std::min<u64>(s->cap_cigar + 1024, 0xfffffff0ull)));
+        }
+        HIPCHK(s->s_tid.reserve(Nn, st, R)); HIPCHK(s->s_pos.reserve(Nn, st, R)); HIPCHK(s->s_flag.reserve(Nn, st, R));
+        HIPCHK(s->s_mapq.reserve(Nn, st, R)); HIPCHK(s->s_nmk.reserve(Nn, st, R)); HIPCHK(s->s_nm.reserve(Nn, st, R));
+        HIPCHK(s->s_lseq.reserve(Nn, st, R)); HIPCHK(s->s_coff.reserve(Nn + 1, st, R + 1));
+        HIPCHK(s->s_cig.reserve(Cn, st, Cg));
+        if (s->want_mates) { HIPCHK(s->s_mtid.reserve(Nn, st, R)); HIPCHK(s->s_qh1.reserve(Nn, st, R)); HIPCHK(s->s_qh2.reserve(Nn, st, R)); }
+        covs::Out O{};
+        O.tid = s->s_tid.p; O.pos = s->s_pos.p; O.flag = s->s_flag.p; O.mapq = s->s_mapq.p; O.nm_kind = s->s_nmk.p; O.nm = s->s_nm.p;
+        O.l_seq = s->s_lseq.p; O.cigar_off = s->s_coff.p; O.cigar = s->s_cig.p; O.rec0 = R; O.cig0 = Cg;
+        if (s->want_mates) { O.mtid = s->s_mtid.p; O.qh1 = s->s_qh1.p; O.qh2 = s->s_qh2.p; }
+        HIPCHK(hipEventRecord(s->sam_ev[2], st));
+        hipLaunchKernelGGL(covs::k_sam_decode, dim3((n_lines + 255u) / 256u), dim3(256), 0, st, L, (const u32 *)s->m_cnt.p, (const u32 *)s->m_rec_idx.p, (const u32 *)s->m_cig_idx.p, s->m_names, O);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(s->sam_ev[3], st));
+        s->sam_decode_timed = true; s->sam_launches++;
+        s->ing_rec_total += nrec; s->ing_cig_total += ncig;
+    }
+    HIPCHK(hipEventRecord(s->sam_buf_free[j], st));
+    s->sam_k++;
+    return COV_OK;
+}
+
+cov_status cov_sam_end(cov_session *s, uint64_t *n_records_out) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (n_records_out) *n_records_out = 0;
+    if (!s->sam_active) { s->err = "cov_sam_end: no SAM text ingest is open (cov_sam_begin)"; return COV_ERR_STATE; }
+    HIPCHK(hipSetDevice(s->cfg.device));
+    s->ing_active = false; s->sam_active = false;
+    HIPCHK(hipStreamSynchronize(s->ing_copy));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    if (s->sam_decode_timed) { s->sam_ms += sam_elapsed(s->sam_ev[2], s->sam_ev[3]); s->sam_decode_timed = false; }
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] sam: device SAM decode: %llu bytes in %u windows of %llu, %llu lines, %llu records, kernels %.3f ms\n", (unsigned long long)s->sam_bytes, s->sam_k,
+                (unsigned long long)s->sam_window, (unsigned long long)s->sam_lines, (unsigned long long)(s->ing_rec_total + s->ing_rec_spilled), s->sam_ms);
+    if (s->ing_rec_total) {
+        const u64 Nn = s->n_records + s->ing_rec_total, Cn = s->n_cigar + s->ing_cig_total;
+        const u32 end_off = (u32)Cn;
+        HIPCHK(hipMemcpyAsync(s->s_coff.p + Nn, &end_off, sizeof end_off, hipMemcpyHostToDevice, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if (s->want_mates && s->mates_valid == s->n_records) s->mates_valid = Nn;
+        s->n_records = Nn; s->n_cigar = Cn;
+        s->finished = false;
+    }
+    if (n_records_out) *n_records_out = s->ing_rec_total + s->ing_rec_spilled;
     return COV_OK;
 }
 
@@ -2380,6 +2610,22 @@ cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_r
     return COV_OK;
 }
 
+// Test hook: what an ingest with cov_ingest_want_mates kept per record (the mate's reference, the 96-bit read-name hash), n_records each.
+cov_status cov_copy_mates(cov_session *s, int32_t *mtid, uint64_t *qh1, uint32_t *qh2) {
+    if (!s || s->adopted || !mtid || !qh1 || !qh2) return COV_ERR_STATE;
+    if (s->spill.active) { s->err = "cov_copy_mates: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    const uint64_t n = s->n_records;
+    if (!s->want_mates || (n && (!s->s_mtid.p || !s->s_qh1.p || !s->s_qh2.p))) { s->err = "cov_copy_mates: the records were not ingested with cov_ingest_want_mates"; return COV_ERR_STATE; }
+    HIPCHK(hipSetDevice(s->cfg.device));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(mtid, s->s_mtid.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(qh1, s->s_qh1.p, n * 8, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipMemcpyAsync(qh2, s->s_qh2.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return COV_OK;
+}
+
 cov_status cov_ingest_release(cov_session *s) {
     if (!s) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
@@ -2540,6 +2786,11 @@ cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist) {
 
 cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total, uint32_t *launches) {
     if (!s || k < 0 || k >= COV_K_COUNT) return COV_ERR_INVALID_ARG;
+    if (k == COV_K_SAM) {        // not part of a finish: the decode kernels of the last cov_sam_* ingest, summed over its windows
+        if (ms_total) *ms_total = s->sam_ms;
+        if (launches) *launches = s->sam_launches;
+        return COV_OK;
+    }
     if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records
         if (ms_total) *ms_total = s->grp_ms[0];
         if (launches) *launches = s->grp_launches;

@@ -16,11 +16,13 @@
 #include <zlib.h>
 
 #include <fcntl.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
 #include <unordered_map>
+#include <cerrno>
 #include <chrono>
 #include <condition_variable>
 #include <cstdio>
@@ -689,10 +691,14 @@ bool parse_bam(Bam &b, const Buf &u) {
 // ---- SAM text (htslib auto-detects the format; needed for e.g. tests/data/mapq_test.sam, filter.rs:758)
 bool parse_sam(Bam &b, const Buf &raw) {
     const char *s = (const char *)raw.data(), *e = s + raw.size();
-    std::vector<std::pair<std::string, size_t>> dummy;
+    // name -> tid: a map kept level with b.names (header lines may still arrive); emplace keeps the first of duplicate SN values, which is
+    // what a scan from the front finds
+    std::unordered_map<std::string, int32_t> ref_index;
+    size_t indexed = 0;
     auto find_ref = [&](const std::string &n) -> int32_t {
-        for (size_t i = 0; i < b.names.size(); i++) if (b.names[i] == n) return (int32_t)i;
-        return -1;
+        for (; indexed < b.names.size(); indexed++) ref_index.emplace(b.names[indexed], (int32_t)indexed);
+        const auto it = ref_index.find(n);
+        return it == ref_index.end() ? -1 : it->second;
     };
     b.cigar_off.assign(1, 0u);
     if (b.want_names) b.qname_off.assign(1, 0u);
@@ -2114,6 +2120,200 @@ int covh_bam_filter_file(const char *in_path, const char *out_path, const covh_p
                         t_part[0], t_part[1], t_part[2], t_part[3], t_part[4]);
     if (n_in) *n_in = n_rec;
     if (n_out) *n_out = n_sel;
+    return 0;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- SAM text to the device (covh_sam_*)
+// The input is a byte stream: a regular file, a FIFO, a character device or standard input, read with read() and nothing else (no lseek,
+// no mmap, no size).  covh_sam_open reads until the header is complete — the `@` lines in front of the first alignment line — and parses it
+// as parse_sam does; covh_sam_gpu_ingest then replays those bytes and reads on, into COV_INGEST_SLOTS page-locked slots of one decode
+// window each: a reader thread fills a slot while the previous one uploads, cuts it at its last '\n' and carries the rest into the next.
+#include "sam_parse_core.h"
+
+struct covh_sam {
+    std::string path, err;
+    int fd = -1; bool own_fd = false, pipe = false, eof = false;
+    int kind = 0;                     // 0 SAM text, 1 BGZF magic, 2 not text
+    uint64_t file_size = 0;           // regular file: its size (sizes the record store); else 0
+    std::vector<uint8_t> head;        // everything read so far
+    std::vector<std::string> names; std::vector<uint64_t> lens; std::string header_text;
+};
+
+namespace {
+// read() until `cap` bytes or the end of the stream; -1 on error.  halt (if given) is looked at between read() calls: once the feeder has
+// failed, a slow pipe is not waited on for the rest of a window
+ssize_t read_full(int fd, uint8_t *dst, size_t cap, bool &eof, const std::atomic<bool> *halt = nullptr) {
+    size_t got = 0;
+    while (got < cap) {
+        if (halt && halt->load(std::memory_order_relaxed)) break;
+        const ssize_t r = read(fd, dst + got, cap - got);
+        if (r < 0) { if (errno == EINTR) continue; return -1; }
+        if (r == 0) { eof = true; break; }
+        got += (size_t)r;
+    }
+    return (ssize_t)got;
+}
+void sam_header_line(covh_sam &h, const uint8_t *p, uint32_t n) {
+    h.header_text.append((const char *)p, n); h.header_text += '\n';
+    if (n >= 3 && p[1] == 'S' && p[2] == 'Q') {
+        samc::u32 so, sl; samc::u64 ln;
+        samc::sq_fields(p, n, so, sl, ln);
+        h.names.emplace_back((const char *)p + so, sl); h.lens.push_back(ln);
+    }
+}
+}  // namespace
+
+extern "C" {
+
+covh_sam *covh_sam_open(const char *path, char *err, size_t errcap) {
+    auto fail = [&](covh_sam *h, const std::string &m) -> covh_sam * {
+        if (err && errcap) snprintf(err, errcap, "%s", m.c_str());
+        if (h) { if (h->own_fd && h->fd >= 0) close(h->fd); delete h; }
+        return nullptr;
+    };
+    covh_sam *h = new covh_sam();
+    h->path = path;
+    if (!strcmp(path, "-")) h->fd = 0;
+    else { h->fd = open(path, O_RDONLY); h->own_fd = true; }
+    if (h->fd < 0) return fail(h, std::string("Unable to find BAM file ") + path);
+    struct stat sb;
+    if (fstat(h->fd, &sb) != 0) return fail(h, std::string("cannot stat ") + path);
+    h->pipe = !S_ISREG(sb.st_mode);
+    h->file_size = S_ISREG(sb.st_mode) ? (uint64_t)sb.st_size : 0;
+    // the header: read on until a line that is neither empty nor a header line is complete (or the stream ends)
+    size_t line = 0;       // start of the first line not yet looked at
+    bool done = false;
+    while (!done) {
+        const size_t CH = 1u << 16, at = h->head.size();
+        h->head.resize(at + CH);
+        const ssize_t r = read_full(h->fd, h->head.data() + at, CH, h->eof);
+        if (r < 0) return fail(h, std::string("read error on ") + path);
+        h->head.resize(at + (size_t)r);
+        if (at == 0) {      // the format, from the first bytes read
+            if (h->head.size() >= 2 && h->head[0] == 0x1f && h->head[1] == 0x8b) { h->kind = 1; return h; }
+            if (memchr(h->head.data(), 0, h->head.size())) { h->kind = 2; return h; }
+        }
+        const uint8_t *b = h->head.data();
+        for (;;) {
+            const uint8_t *nl = (const uint8_t *)memchr(b + line, '\n', h->head.size() - line);
+            if (!nl && !h->eof) break;
+            const size_t end = nl ? (size_t)(nl - b) : h->head.size();
+            uint32_t n = samc::trim_cr(b + line, (uint32_t)(end - line));
+            if (n && b[line] != '@') { done = true; break; }
+            if (n) sam_header_line(*h, b + line, n);
+            line = nl ? end + 1 : end;
+            if (!nl) { done = true; break; }
+        }
+        if (h->eof) done = true;
+    }
+    return h;
+}
+int covh_sam_kind(const covh_sam *h) { return h->kind; }
+int covh_sam_is_pipe(const covh_sam *h) { return h->pipe ? 1 : 0; }
+uint32_t covh_sam_n_targets(const covh_sam *h) { return (uint32_t)h->names.size(); }
+const char *covh_sam_target_name(const covh_sam *h, uint32_t i) { return h->names[i].c_str(); }
+uint64_t covh_sam_target_len(const covh_sam *h, uint32_t i) { return h->lens[i]; }
+const char *covh_sam_header_text(const covh_sam *h) { return h->header_text.c_str(); }
+void covh_sam_close(covh_sam *h) { if (!h) return; if (h->own_fd && h->fd >= 0) close(h->fd); delete h; }
+
+// 0 = the records are in the session's store; 1 = irregular input (a header line behind the first alignment line): nothing appended, decode
+// the file on the host if it can be read again; -1 = error.  tm: [0] read, [1] waiting for slots, [2] feed calls, [3] total (seconds).
+int covh_sam_gpu_ingest(covh_sam *h, int threads, cov_session *s, uint64_t *n_records, double *tm, char *err, size_t errcap) {
+    (void)threads;
+    auto fail = [&](int rc, const std::string &m) { if (err && errcap) snprintf(err, errcap, "%s", m.c_str()); return rc; };
+    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_start = now();
+    if (n_records) *n_records = 0;
+    if (h->kind != 0) return fail(-1, h->path + ": not SAM text");
+    std::string blob; std::vector<uint64_t> off(1, 0);
+    for (auto &nme : h->names) { blob += nme; off.push_back(blob.size()); }
+    if (cov_sam_begin(s, blob.data(), off.data(), (uint32_t)h->names.size(), h->file_size) != COV_OK) return fail(-1, cov_last_error(s));
+    const size_t W = (size_t)cov_sam_window_bytes(s);
+    struct Slots {
+        uint8_t *p[COV_INGEST_SLOTS] = {}; bool pinned[COV_INGEST_SLOTS] = {};
+        ~Slots() { for (int k = 0; k < COV_INGEST_SLOTS; k++) if (p[k]) { if (pinned[k]) cov_host_free(p[k]); else free(p[k]); } }
+    } slots;
+    for (int k = 0; k < COV_INGEST_SLOTS; k++) {
+        slots.p[k] = (uint8_t *)cov_host_alloc(W); slots.pinned[k] = slots.p[k] != nullptr;
+        if (!slots.p[k]) slots.p[k] = (uint8_t *)malloc(W);
+        if (!slots.p[k]) { (void)cov_ingest_abort(s); return fail(-1, "out of memory for the SAM staging slots"); }
+    }
+    // reader -> feeder: filled pieces in order; feeder -> reader: how many pieces have been fed (a slot is free once its piece was fed AND uploaded)
+    struct Piece { int slot; size_t n; };
+    std::mutex mu; std::condition_variable cv;
+    std::deque<Piece> q; bool reader_done = false, stop = false; std::string reader_err;
+    uint64_t fed = 0;
+    std::atomic<bool> halt{false};
+    double t_read = 0, t_wait = 0;
+    std::thread reader([&] {
+        std::vector<uint8_t> carry;           // the cut-off last line of the previous piece
+        size_t head_at = 0;                   // bytes of h->head already replayed
+        bool eof = false;
+        for (uint64_t i = 0; !eof; i++) {
+            const int k = (int)(i % COV_INGEST_SLOTS);
+            { std::lock_guard<std::mutex> lk(mu); if (stop) break; }
+            if (i >= COV_INGEST_SLOTS) {
+                const double t0 = now();
+                { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return stop || fed > i - COV_INGEST_SLOTS; }); if (stop) break; }
+                if (cov_sam_slot_wait(s, k) != COV_OK) { std::lock_guard<std::mutex> lk(mu); reader_err = cov_last_error(s); break; }
+                t_wait += now() - t0;
+            }
+            uint8_t *dst = slots.p[k];
+            size_t fill = carry.size();
+            if (fill) memcpy(dst, carry.data(), fill);
+            carry.clear();
+            const double t0 = now();
+            if (head_at < h->head.size()) { const size_t m = std::min(W - fill, h->head.size() - head_at); memcpy(dst + fill, h->head.data() + head_at, m); fill += m; head_at += m; }
+            if (head_at == h->head.size() && !h->head.empty()) { std::vector<uint8_t>().swap(h->head); head_at = 0; }
+            if (h->head.empty() && fill < W) {
+                if (h->eof) eof = true;
+                else {
+                    const ssize_t r = read_full(h->fd, dst + fill, W - fill, eof, &halt);
+                    if (r < 0) { std::lock_guard<std::mutex> lk(mu); reader_err = "read error on " + h->path; break; }
+                    fill += (size_t)r;
+                }
+            }
+            t_read += now() - t0;
+            size_t cut = fill;
+            if (!eof) {      // whole lines only: the bytes behind the last '\n' wait for the next piece (none: a line as long as the window, the device says so)
+                const void *nl = memrchr(dst, '\n', fill);
+                if (nl) { cut = (size_t)((const uint8_t *)nl - dst) + 1; carry.assign(dst + cut, dst + fill); }
+            }
+            { std::lock_guard<std::mutex> lk(mu); q.push_back(Piece{k, cut}); }
+            cv.notify_all();
+        }
+        { std::lock_guard<std::mutex> lk(mu); reader_done = true; }
+        cv.notify_all();
+    });
+    int rc = 0; std::string msg;
+    double t_feed = 0;
+    for (;;) {
+        Piece pc{-1, 0};
+        {
+            std::unique_lock<std::mutex> lk(mu);
+            cv.wait(lk, [&] { return !q.empty() || reader_done; });
+            if (q.empty()) break;
+            pc = q.front(); q.pop_front();
+        }
+        const double t0 = now();
+        const cov_status st = pc.n ? cov_sam_feed(s, pc.slot, slots.p[pc.slot], pc.n) : COV_OK;
+        t_feed += now() - t0;
+        if (st != COV_OK) { rc = st == COV_ERR_INGEST_FALLBACK ? 1 : -1; msg = cov_last_error(s); break; }
+        { std::lock_guard<std::mutex> lk(mu); fed++; }
+        cv.notify_all();
+    }
+    { std::lock_guard<std::mutex> lk(mu); stop = true; halt = true; }
+    cv.notify_all();
+    reader.join();
+    if (rc == 0 && !reader_err.empty()) { rc = -1; msg = reader_err; }
+    if (rc != 0) { (void)cov_ingest_abort(s); return fail(rc, h->path + ": " + msg); }
+    uint64_t nrec = 0;
+    if (cov_sam_end(s, &nrec) != COV_OK) return fail(-1, cov_last_error(s));
+    for (int k = 0; k < COV_INGEST_SLOTS; k++) (void)cov_sam_slot_wait(s, k);
+    if (n_records) *n_records = nrec;
+    if (tm) { tm[0] = t_read; tm[1] = t_wait; tm[2] = t_feed; tm[3] = now() - t_start; }
     return 0;
 }
 

@@ -28,6 +28,7 @@
 #include <mutex>
 #include <stdexcept>
 #include <cerrno>
+#include <sys/stat.h>
 #include <string>
 #include <thread>
 #include <unordered_map>
@@ -131,6 +132,7 @@ struct HeaderAhead { covh_bam_header *hd = nullptr; std::string err; };
 
 struct Run {
     std::mutex hdr_mutex;
+    std::map<std::string, covh_sam *> sam_ahead;      // pipes, opened (and their format told) before the sessions exist
     std::map<std::string, std::future<HeaderAhead>> hdr_ahead;   // headers of the first BAM files, read beside the runtime's start-up
     Args a;
     Filter f;
@@ -150,7 +152,16 @@ struct Run {
 
 void check(cov_session *s, cov_status st) { if (st != COV_OK) die(cov_last_error(s)); }
 
+// "-" (standard input), a FIFO or a character device: a stream that can be read once, with read() alone
+bool input_is_pipe(const std::string &path) {
+    if (path == "-") return true;
+    struct stat sb;
+    return stat(path.c_str(), &sb) == 0 && (S_ISFIFO(sb.st_mode) || S_ISCHR(sb.st_mode));
+}
+bool sam_on_host() { static const bool on = getenv("COVERM_SAM_ON_HOST") != nullptr; return on; }
+
 std::string stoit_of(const std::string &path) {   // file stem, bam_generator.rs:358-365
+    if (path == "-") return "stdin";
     std::string p = path;
     const size_t sl = p.find_last_of('/');
     if (sl != std::string::npos) p = p.substr(sl + 1);
@@ -218,6 +229,7 @@ std::string resolve_fasta_genomes(Run &R) {
 }
 
 bool is_bgzf(const std::string &path) {
+    if (input_is_pipe(path)) return false;      // (a pipe's format is told from the bytes read, covh_sam_open)
     FILE *f = fopen(path.c_str(), "rb");
     if (!f) return false;
     unsigned char m[2] = {0, 0};
@@ -279,6 +291,7 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
     const Args &a = R.a;
     // pair-mode filtering (filter.rs:117-228) runs on the device over what the device ingest extracted (mate reference + read-name
     // hash per record, cov_pair_filter_apply); only when that path declines the file does the whole file come to the host
+    const bool piped = input_is_pipe(S.path);
     const bool bgzf = is_bgzf(S.path);
     const bool pair_dev = R.fp && !a.no_stream && !R.per_gene && bgzf && !no_gpu_ingest() && !pair_on_host();
     const bool stream = !a.no_stream && (!R.fp || pair_dev) && !R.per_gene && bgzf;
@@ -393,6 +406,78 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
     cov_batch batch; memset(&batch, 0, sizeof batch);
     struct HostRecords { std::vector<int32_t> tid, pos; std::vector<uint16_t> flag; std::vector<uint8_t> mapq, nmk; std::vector<uint32_t> nm, lseq, coff, cig; } hr;
     bool have_records = false, prim_from_host = false;
+    // ---- SAM text (a file or a pipe): decoded on the device window by window as it is read (cov_sam_*); what follows the ingest — grouping,
+    // the pair filter, finish, or the records' way back for --gff — is what follows the BGZF ingest
+    const bool sam_dev = !bgzf && !a.no_stream && !sam_on_host() && span_count == 1 && !(R.fp && pair_on_host()) && (piped || !no_gpu_ingest());
+    if (!bgzf && piped && !sam_dev) die("a pipe ('-b -', a FIFO) is decoded on the device only: COVERM_SAM_ON_HOST / COVERM_PAIR_ON_HOST need a file");
+    if (sam_dev) {
+        covh_sam *h = nullptr;
+        {   // ingest() runs in one thread per device: the map is shared, as hdr_ahead is
+            std::lock_guard<std::mutex> lk(R.hdr_mutex);
+            auto it = R.sam_ahead.find(S.path);
+            if (it != R.sam_ahead.end()) { h = it->second; R.sam_ahead.erase(it); }
+        }
+        if (!h) h = covh_sam_open(S.path.c_str(), err, sizeof err);
+        if (!h) die(err);
+        struct SamClose { covh_sam *p; ~SamClose() { covh_sam_close(p); } } samclose{h};
+        int rc = covh_sam_kind(h) == 0 ? 0 : 1;
+        if (rc) snprintf(err, sizeof err, "%s", "the file is not text (NUL bytes in its first piece)");
+        uint64_t nrec = 0; double tm[4] = {0, 0, 0, 0};
+        if (rc == 0) {
+            set_header(S, covh_sam_n_targets(h), [&](uint32_t t) { return covh_sam_target_name(h, t); }, [&](uint32_t t) { return covh_sam_target_len(h, t); });
+            check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
+            if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
+            S.t_open = now() - t0;
+            check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
+            check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
+            rc = covh_sam_gpu_ingest(h, threads, s, &nrec, tm, err, sizeof err);
+            if (rc < 0) die(err);
+        }
+        uint64_t pair_prim = 0;
+        if (rc == 0) group_sample(R, s, S);
+        if (rc == 0 && R.fp) {
+            cov_pair_filter pf; memset(&pf, 0, sizeof pf);
+            pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
+            pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
+            pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
+            uint64_t nsel = 0;
+            const cov_status prc = cov_pair_filter_apply(s, &pf, &nsel, &pair_prim);
+            if (prc == COV_ERR_INGEST_FALLBACK) { rc = 1; snprintf(err, sizeof err, "%s", cov_last_error(s)); }
+            else check(s, prc);
+        }
+        if (rc != 0) {
+            if (piped) die(S.stoit + ": " + err + " — a pipe cannot be read again: write the stream to a file");
+            if (a.verbose || timing_on()) fprintf(stderr, "[coverm-amd] %s: SAM text handed to the host route (whole file): %s\n", S.stoit.c_str(), err);
+            check(s, cov_reset(s));
+        } else {
+            S.n_records = nrec; S.device_ingest = true;
+            if (timing_on()) {
+                double ms = 0; uint32_t launches = 0;
+                (void)cov_kernel_ms(s, COV_K_SAM, &ms, &launches);
+                fprintf(stderr, "[coverm-amd] %s: device SAM decode from %s: read %.3fs, slot waits %.3fs, feed calls %.3fs, total %.3fs, %llu records, decode kernels %.3f ms\n",
+                        S.stoit.c_str(), covh_sam_is_pipe(h) ? "a pipe" : "the file", tm[0], tm[1], tm[2], tm[3], (unsigned long long)nrec, ms);
+            }
+            if (!R.per_gene) {
+                S.t_ingest = now() - t0;
+                cov_summary summ;
+                finish_sample(R, s, S, summ);
+                fetch_results(R, s, S, summ);
+                S.prim = R.fp ? pair_prim : summ.num_detected_primary_alignments;
+                S.t_finish = now() - t0 - S.t_ingest;
+                return;
+            }
+            if (R.fp) { S.prim = pair_prim; prim_from_host = true; }
+            uint64_t n = 0, nc = 0;
+            check(s, cov_copy_records(s, nullptr, &n, &nc));
+            hr.tid.resize(n); hr.pos.resize(n); hr.flag.resize(n); hr.mapq.resize(n); hr.nmk.resize(n); hr.nm.resize(n); hr.lseq.resize(n);
+            hr.coff.resize(n + 1); hr.cig.resize(nc + 1);
+            batch.tid = hr.tid.data(); batch.pos = hr.pos.data(); batch.flag = hr.flag.data(); batch.mapq = hr.mapq.data(); batch.nm = hr.nm.data();
+            batch.nm_kind = hr.nmk.data(); batch.l_seq = hr.lseq.data(); batch.cigar_off = hr.coff.data(); batch.cigar = hr.cig.data(); batch.n_records = n;
+            check(s, cov_copy_records(s, &batch, nullptr, nullptr));
+            if (n == 0) hr.coff[0] = 0;
+            have_records = true;
+        }
+    }
     if (R.per_gene && bgzf && !a.no_stream && span_count == 1 && !no_gpu_ingest() && !getenv("COVERM_GENES_DECODE_ON_HOST") && !pair_on_host()) {
         covh_bam_header *hd = covh_bam_read_header(S.path.c_str(), err, sizeof err);
         if (!hd) die(err);
@@ -588,13 +673,17 @@ int run_cli(int argc, char **argv) {
                         "       `samtools sort`ed file for every method but anir (whose f64 sums follow the record order); per-record errors name the\n"
                         "       first offending record of that order.  The sample must fit the device's record store.  Not with filter, and not with\n"
                         "       --devices when there are fewer files than devices.\n"
+                        "       -b takes BAM files and SAM text; `-b -` reads SAM text from standard input and a FIFO or character device is read as a\n"
+                        "       pipe (e.g. minimap2 -a ref.fa reads.fq | coverm-amd contig -b - --unsorted -m mean; sample name `stdin`, or the path's stem).\n"
+                        "       SAM text is decoded on the device as it streams in, in bounded memory; --no-stream or COVERM_SAM_ON_HOST=1 decode a SAM\n"
+                        "       FILE whole on the host instead (the cross-check).  BAM from a pipe and gzip-compressed SAM are not supported.\n"
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n");
         return 2;
     }
     a.mode = argv[1];
-    auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && argv[i + 1][0] != '-') dst.push_back(argv[++i]); };
+    auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && (argv[i + 1][0] != '-' || !argv[i + 1][1])) dst.push_back(argv[++i]); };      // ("-": standard input)
     for (int i = 2; i < argc; i++) {
         const std::string k = argv[i];
         auto val = [&]() -> const char * { if (i + 1 >= argc) die("missing value for " + k); return argv[++i]; };
@@ -672,6 +761,20 @@ int run_cli(int argc, char **argv) {
     if (a.unsorted && a.devices.size() > 1 && a.bams.size() < a.devices.size())
         die("--unsorted cannot be used with --devices when there are fewer BAM files than devices: a file would be cut into tid spans, which only a file sorted by reference has "
             "(give at least as many files as devices, or one device)");
+    {   // SAM text and pipes: one stream is one sample on one device
+        size_t n_stdin = 0, n_pipe = 0, n_text = 0;
+        for (auto &b : a.bams) {
+            const bool piped = input_is_pipe(b);
+            n_stdin += b == "-"; n_pipe += piped;
+            struct stat sb;
+            n_text += piped || (stat(b.c_str(), &sb) == 0 && S_ISREG(sb.st_mode) && sb.st_size >= 2 && !is_bgzf(b));
+        }
+        if (n_stdin > 1) die("'-b -' (standard input) can be given once only");
+        if (n_pipe && a.no_stream) die("--no-stream reads the whole file on the host, which a pipe ('-b -', a FIFO) does not allow: write the stream to a file first");
+        if (n_text && a.devices.size() > 1 && a.bams.size() < a.devices.size())
+            die("--devices with fewer files than devices needs BAM files: SAM text and pipes are decoded as one stream, a sample is one device's "
+                "(give at least as many files as devices, or one device)");
+    }
     R.contig = a.mode == "contig";
     const bool contig = R.contig;
     if (a.methods.empty()) a.methods.push_back(contig ? "mean" : "relative_abundance");   // cli.rs:2521, 2048
@@ -817,6 +920,17 @@ int run_cli(int argc, char **argv) {
                 return h;
             }));
         }
+    // a pipe's format is told from its first bytes READ, before any device work: BAM from a pipe is refused here
+    for (auto &b : a.bams) {
+        if (!input_is_pipe(b) || R.sam_ahead.count(b)) continue;
+        char e[512] = {0};
+        covh_sam *h = covh_sam_open(b.c_str(), e, sizeof e);
+        if (!h) die(e);
+        R.sam_ahead.emplace(b, h);
+        if (covh_sam_kind(h) == 1) die("BAM from a pipe is not supported yet; SAM text is (e.g. `samtools view -h`), or pass the file's path");
+        if (covh_sam_kind(h) == 2) die(stoit_of(b) + ": the stream is neither SAM text nor BAM (NUL bytes in its first piece)");
+    }
+    struct SamDrain { Run &R; ~SamDrain() { for (auto &kv : R.sam_ahead) covh_sam_close(kv.second); R.sam_ahead.clear(); } } sam_drain{R};
     struct HdrDrain { Run &R; ~HdrDrain() { for (auto &kv : R.hdr_ahead) { HeaderAhead h = kv.second.get(); if (h.hd) covh_bam_header_free(h.hd); } } } hdr_drain{R};
     std::vector<cov_session *> sess(nd, nullptr);
     struct SessFree { std::vector<cov_session *> &v; ~SessFree() { if (!g_skip_teardown.load()) for (auto *s : v) if (s) cov_destroy(s); } } sess_free{sess};

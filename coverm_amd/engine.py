@@ -245,6 +245,19 @@ class Session:
         self._check(self._lib.cov_kernel_ms(self._h, native.K_GROUP, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def sam_ingest(self, path_or_fileobj, mates=False, group=False):
+        """SAM text decoded on the device into this session's store (cov_sam_*): a path, "-" for standard input, or an object with fileno().
+        Sets the targets from the @SQ lines; returns (ref_names, ref_lens, n_records, timing dict) — see coverm_amd.bam.sam_ingest."""
+        from . import bam
+        return bam.sam_ingest(self, path_or_fileobj, want_mates=mates, group=group)
+
+    def sam_kernel_ms(self):
+        """(ms, launches) of the decode kernels of the last SAM text ingest (COV_K_SAM)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_SAM, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def store_spills(self):
         return int(self._lib.cov_store_spills(self._h))
 

@@ -233,6 +233,24 @@ int covh_bam_gpu_ingest_span(const char *path, int threads, cov_session *s, cons
                              uint32_t span_count, uint64_t *n_records, double *timing8, char *err, size_t errcap);
 int covh_bam_gpu_ingest(const char *path, int threads, cov_session *s, const covh_bam_header *hd, int check_crc, uint64_t *n_records,
                         double *timing8, char *err, size_t errcap);   /* s: file read, staging waits, cov_ingest_end, total, buffers, block-header walk, cov_ingest_feed; [7] = where the DMA read the bytes (0 staging slots, 1 the mapped file, 2 mapped and registered up front) */
+/* SAM text to the device (cov_sam_*), from a regular file, a FIFO, a character device or standard input (path "-"): the stream is read
+ * with read() alone.  covh_sam_open reads up to the end of the header (the `@` lines in front of the first alignment line) and tells the
+ * format from the first bytes read: covh_sam_kind 0 = SAM text, 1 = BGZF magic (a BAM), 2 = not text (NUL bytes).  covh_sam_gpu_ingest
+ * (after cov_set_targets with the header's lengths) replays those bytes and reads on into COV_INGEST_SLOTS page-locked slots of one decode
+ * window each — a reader thread fills a slot while the previous one uploads — keeping lines whole: each piece is cut at its last '\n'
+ * and the rest is carried into the next.  Returns 0 = the records are in the session's store; 1 = irregular input (a header line behind
+ * the first alignment line): nothing appended, decode the file on the host if it can be read again; -1 = error (err names the line).
+ * tm (4 doubles, may be NULL): seconds in read(), waiting for slots, in cov_sam_feed, in total. */
+typedef struct covh_sam covh_sam;
+covh_sam *covh_sam_open(const char *path, char *err, size_t errcap);
+int covh_sam_kind(const covh_sam *h);
+int covh_sam_is_pipe(const covh_sam *h);
+uint32_t covh_sam_n_targets(const covh_sam *h);
+const char *covh_sam_target_name(const covh_sam *h, uint32_t i);
+uint64_t covh_sam_target_len(const covh_sam *h, uint32_t i);
+const char *covh_sam_header_text(const covh_sam *h);
+int covh_sam_gpu_ingest(covh_sam *h, int threads, cov_session *s, uint64_t *n_records, double *tm, char *err, size_t errcap);
+void covh_sam_close(covh_sam *h);
 
 /* ---- reader-stage PAIR filter (ReferenceSortedBamFilter::read pair branch, filter.rs:117-228, filter_out = true).
  * The single-read branch runs on the device (cov_config.filter_single); the pair branch needs read names, which never

@@ -151,7 +151,8 @@ typedef enum {
     COV_K_ESTIMATE = 6, /* CoverageEstimator::calculate_coverage of every contig (cov_set_estimators) */
     COV_K_GENOME = 7,   /* cov_set_genomes: contigs reduced into genomes, histograms merged, calculate_coverage of every genome */
     COV_K_GROUP = 8,    /* cov_group_records: order check, sort passes and gather of the last call, summed (not part of a finish) */
-    COV_K_COUNT = 9
+    COV_K_SAM = 9,      /* cov_sam_*: the decode kernels of the last SAM text ingest, summed over its windows (not part of a finish) */
+    COV_K_COUNT = 10
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -238,6 +239,36 @@ cov_status cov_ingest_end(cov_session *s, uint64_t *n_records);
 cov_status cov_ingest_abort(cov_session *s);
 cov_status cov_ingest_release(cov_session *s); /* frees the compressed / inflated buffers (kept between files otherwise) */
 cov_status cov_ingest_copy_inflated(cov_session *s, uint64_t offset, uint64_t n, void *out); /* test hook; single-window files only */
+/*
+ * SAM text ingest: what a mapper writes to its standard output (`bwa mem`, `minimap2 -a`), decoded on the device window by window into the
+ * same record store, from a file or from a pipe.  The host only reads bytes into page-locked slots and keeps lines whole; the device finds
+ * the lines and the tabs (one coalesced pass: a 64-bit mask of each per 64 bytes), numbers the lines by a scan, and decodes a line per lane
+ * (csrc/sam_parse_core.h is the arithmetic, field for field what the host's SAM reader produces).
+ *   cov_set_targets(s, ...)                         reference lengths, from the @SQ lines
+ *   cov_sam_begin(s, names_blob, name_off, n_names, expected_bytes)
+ *         reference name i = names_blob[name_off[i] .. name_off[i + 1])  (n_names + 1 offsets): RNAME / RNEXT -> tid through a hash table built
+ *         here, a hit confirmed by comparing the bytes; a duplicate name resolves to its first occurrence, an unknown one to -1.
+ *         expected_bytes: the text's size when known (sizes the record store once), 0 for a pipe (the store grows as records arrive).
+ *   loop: cov_sam_slot_wait(s, slot) -> fill the slot's buffer -> cov_sam_feed(s, slot, buf, n)
+ *         every piece holds WHOLE lines (cut it at its last '\n' and carry the rest into the next piece), at most cov_sam_window_bytes(s)
+ *         bytes (32 MiB; COVERM_KNOBS sam_window_bytes); only the last piece may end without '\n' — that last line is a record.  Header
+ *         lines (@) in front of the first alignment line and empty lines are skipped, so the text may be fed from its first byte and line
+ *         numbers in errors are the file's.  The upload is asynchronous (slot_wait tells when the buffer may be written again); the call
+ *         waits for this window's line and record counts and leaves its decode running beside the next upload.
+ *   cov_sam_end(s, &n_records)
+ * Device memory is two windows of text, their masks and per-line words, whatever the input's length.  cov_ingest_want_mates and
+ * cov_ingest_want_grouping apply as to the BGZF ingest (the name hash is the same function), the bounded record store spills as for
+ * cov_push_batch, and cov_ingest_abort gives an open SAM ingest up.  Errors are decided on the device for the first offending line in
+ * file order, 1-based line number in cov_last_error: COV_ERR_INVALID_ARG "malformed SAM line" (fewer than 11 fields), a CIGAR of more than
+ * 65535 operations, a line longer than the window; COV_ERR_INGEST_FALLBACK for a header line behind the first alignment line (decode that
+ * file on the host).  After an error nothing was appended and the session is ready for cov_push_batch.  COV_ERR_STATE: cov_sam_feed /
+ * cov_sam_end without cov_sam_begin, cov_sam_begin (or cov_ingest_begin) while an ingest is open.
+ */
+cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t *name_off, uint32_t n_names, uint64_t expected_bytes);
+uint64_t cov_sam_window_bytes(const cov_session *s);
+cov_status cov_sam_slot_wait(cov_session *s, int slot);
+cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64_t n_bytes);
+cov_status cov_sam_end(cov_session *s, uint64_t *n_records);
 /* ---- reader-stage PAIR filter on the device: ReferenceSortedBamFilter::read, pair branch (src/filter.rs:117-228, filter_out = true) +
  * read_pair_passes_filter (:281-336) over the records the device ingest put into the session's store.
  *   cov_ingest_want_mates(s, 1)      before cov_ingest_begin: the extraction also keeps next_refID and a 96-bit hash of each read name
@@ -277,6 +308,9 @@ cov_status cov_ingest_want_grouping(cov_session *s, int on);
 cov_status cov_group_records(cov_session *s, uint64_t *n_moved);
 /* Test hook: the session's own record store copied back into caller-sized host arrays (host == NULL: only the counts). */
 cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_records, uint64_t *n_cigar);
+/* Test hook: what an ingest with cov_ingest_want_mates kept beside the records — the mate's reference and the 96-bit read-name hash
+ * (csrc/name_hash_core.h), n_records entries each.  COV_ERR_STATE without want_mates. */
+cov_status cov_copy_mates(cov_session *s, int32_t *mtid, uint64_t *qh1, uint32_t *qh2);
 
 /* Multi-GPU, one process: after cov_finish on every session (one per device, same targets), ONE RCCL gather moves each
  * rank's per-contig result block (fixed size: 160 B per contig + counters) to the device of sessions[root] over xGMI and
