@@ -25,6 +25,7 @@
 #include <functional>
 #include <future>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <cerrno>
@@ -35,6 +36,7 @@
 #include <vector>
 
 #include "../../include/coverm_host.h"
+#include "cli_route.h"
 #include "knobs.h"
 
 namespace {
@@ -69,6 +71,30 @@ float parse_percentage(const char *v, const char *opt = "percentage") {   // cov
     return p;
 }
 
+// The reader-filter flags of contig, genome and filter (cli.rs) as given: the percentages still as text
+struct FilterArgs {
+    bool proper_pairs_only = false, exclude_supplementary = false, include_secondary = false;
+    uint32_t len_single = 0, len_pair = 0;
+    const char *pid_single = nullptr, *pct_single = nullptr, *pid_pair = nullptr, *pct_pair = nullptr;
+    int mapq = 255;
+};
+
+// Takes `k` (and its value, through val()) when it is one of those flags
+template <class Val> bool parse_filter_flag(const std::string &k, Val &&val, FilterArgs &fa) {
+    if (k == "--proper-pairs-only") fa.proper_pairs_only = true;
+    else if (k == "--exclude-supplementary") fa.exclude_supplementary = true;
+    else if (k == "--include-secondary") fa.include_secondary = true;
+    else if (k == "--min-read-aligned-length") fa.len_single = (uint32_t)parse_uint(k, val(), 0xffffffffull);
+    else if (k == "--min-read-percent-identity") fa.pid_single = val();
+    else if (k == "--min-read-aligned-percent") fa.pct_single = val();
+    else if (k == "--min-read-aligned-length-pair") fa.len_pair = (uint32_t)parse_uint(k, val(), 0xffffffffull);
+    else if (k == "--min-read-percent-identity-pair") fa.pid_pair = val();
+    else if (k == "--min-read-aligned-percent-pair") fa.pct_pair = val();
+    else if (k == "--min-mapq") fa.mapq = (int)parse_uint(k, val(), 255);
+    else return false;
+    return true;
+}
+
 struct Args {
     std::string mode;
     std::vector<std::string> bams, methods;
@@ -79,13 +105,12 @@ struct Args {
     std::string genome_fasta_directory, genome_fasta_list, genome_fasta_extension = "fna";
     bool have_fasta_files = false, have_fasta_directory = false, have_fasta_list = false, use_full_contig_names = false;
     bool have_gff_feature_type = false;
-    bool no_zeros = false, proper_pairs_only = false, exclude_supplementary = false, include_secondary = false;
+    bool no_zeros = false;
+    FilterArgs filter;
     bool single_genome = false, have_separator = false, no_stream = false;
     bool unsorted = false, verbose = false;      // --unsorted: the files need not be sorted by reference, records are grouped on the device (cov_group_records)
     char separator = '~';
-    uint32_t min_aligned_length = 0, min_aligned_length_pair = 0;
-    const char *min_pid = nullptr, *min_aligned_pct = nullptr, *min_pid_pair = nullptr, *min_aligned_pct_pair = nullptr;
-    int min_mapq = 255, threads = 1;
+    int threads = 1;
     std::vector<int> devices;
 };
 
@@ -104,6 +129,15 @@ struct Filter {   // FilterParameters, coverm.rs:1648-1657
         fp = fp0 || ((!fs || !improper) && mapq != 255);
     }
 };
+
+Filter resolve_filter(const FilterArgs &fa) {   // FilterParameters::generate_from_clap, coverm.rs:1659-1678
+    Filter f;
+    f.improper = !fa.proper_pairs_only; f.supp = !fa.exclude_supplementary; f.sec = fa.include_secondary;
+    f.len_single = fa.len_single; f.len_pair = fa.len_pair; f.mapq = fa.mapq;
+    f.pid_single = parse_percentage(fa.pid_single, "--min-read-percent-identity"); f.pct_single = parse_percentage(fa.pct_single, "--min-read-aligned-percent");
+    f.pid_pair = parse_percentage(fa.pid_pair, "--min-read-percent-identity-pair"); f.pct_pair = parse_percentage(fa.pct_pair, "--min-read-aligned-percent-pair");
+    return f;
+}
 
 // One BAM's results plus the header they refer to.
 struct Sample {
@@ -124,9 +158,12 @@ struct Sample {
 
 double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 bool timing_on() { return covh_timing_on() != 0; }
-// COVERM_NO_GPU_INGEST: every file through the CPU readers (tests compare the two paths); COVERM_PAIR_ON_HOST: the pair-mode reader filter on the host
+// COVERM_NO_GPU_INGEST: every file through the CPU readers (tests compare the two paths); COVERM_PAIR_ON_HOST: the pair-mode reader filter on the host;
+// COVERM_SAM_ON_HOST: a SAM file whole on the host; COVERM_GENES_DECODE_ON_HOST: --gff over the host's whole-file decode.  Facts of cli_route.h.
 bool no_gpu_ingest() { static const bool v = getenv("COVERM_NO_GPU_INGEST") != nullptr; return v; }
 bool pair_on_host() { static const bool v = getenv("COVERM_PAIR_ON_HOST") != nullptr; return v; }
+bool sam_on_host() { static const bool v = getenv("COVERM_SAM_ON_HOST") != nullptr; return v; }
+bool genes_decode_on_host() { static const bool v = getenv("COVERM_GENES_DECODE_ON_HOST") != nullptr; return v; }
 
 struct HeaderAhead { covh_bam_header *hd = nullptr; std::string err; };
 
@@ -158,7 +195,6 @@ bool input_is_pipe(const std::string &path) {
     struct stat sb;
     return stat(path.c_str(), &sb) == 0 && (S_ISFIFO(sb.st_mode) || S_ISCHR(sb.st_mode));
 }
-bool sam_on_host() { static const bool on = getenv("COVERM_SAM_ON_HOST") != nullptr; return on; }
 
 std::string stoit_of(const std::string &path) {   // file stem, bam_generator.rs:358-365
     if (path == "-") return "stdin";
@@ -286,324 +322,434 @@ void group_sample(Run &R, cov_session *s, const Sample &S) {
     }
 }
 
-// Decode + push + finish of one BAM (or one tid span of it) on one session.  Leaves the session finished.
-void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index, uint32_t span_count) {
-    const Args &a = R.a;
-    // pair-mode filtering (filter.rs:117-228) runs on the device over what the device ingest extracted (mate reference + read-name
-    // hash per record, cov_pair_filter_apply); only when that path declines the file does the whole file come to the host
-    const bool piped = input_is_pipe(S.path);
-    const bool bgzf = is_bgzf(S.path);
-    const bool pair_dev = R.fp && !a.no_stream && !R.per_gene && bgzf && !no_gpu_ingest() && !pair_on_host();
-    const bool stream = !a.no_stream && (!R.fp || pair_dev) && !R.per_gene && bgzf;
-    if (span_count > 1 && !stream) die("--devices with fewer BAM files than devices needs streamable input (BAM, no --gff)");
-    S.stoit = stoit_of(S.path); S.streamed = stream && !R.fp;
-    const double t0 = now();
-    std::vector<uint8_t> mask;
-    check(s, cov_reset(s));
-    if (stream && !no_gpu_ingest()) {
-        // ---- device ingest: the compressed file goes to HBM, the GPU inflates, finds the records and fills its own store
-        char err[512] = {0};
-        covh_bam_header *hd = nullptr;
-        {   // the first files' headers were read while the HIP runtime came up
-            std::unique_lock<std::mutex> lk(R.hdr_mutex);
-            auto it = R.hdr_ahead.find(S.path);
-            if (it != R.hdr_ahead.end()) {
-                std::future<HeaderAhead> fut = std::move(it->second);
-                R.hdr_ahead.erase(it);
-                lk.unlock();
-                HeaderAhead ha = fut.get();
-                hd = ha.hd;
-                if (!hd) snprintf(err, sizeof err, "%s", ha.err.c_str());
-            }
+// ---- one sample from its path into a finished session.  cli_route.h decides which reader takes it (and which one takes it next when
+// a device reader hands it back); what a reader does is written once below: open + header, prepare_session, feed, after_ingest.
+
+using cli_route::Decision;
+using cli_route::Route;
+using cli_route::RouteFacts;
+
+template <auto Free> struct FreeWith { template <class T> void operator()(T *p) const { Free(p); } };
+using BamHeader = std::unique_ptr<covh_bam_header, FreeWith<covh_bam_header_free>>;
+using BamStream = std::unique_ptr<covh_bam_stream, FreeWith<covh_bam_stream_close>>;
+using SamText = std::unique_ptr<covh_sam, FreeWith<covh_sam_close>>;
+using BamWhole = std::unique_ptr<covh_bam, FreeWith<covh_bam_close>>;
+struct OwnedBatch {      // a batch covh_batch_select filled
+    cov_batch b;
+    OwnedBatch() { memset(&b, 0, sizeof b); }
+    OwnedBatch(const OwnedBatch &) = delete;
+    OwnedBatch &operator=(const OwnedBatch &) = delete;
+    ~OwnedBatch() { if (b.tid) covh_batch_free(&b); }
+};
+
+RouteFacts route_facts(const Run &R, const std::string &path, uint32_t span_count) {
+    RouteFacts f;
+    f.bgzf = is_bgzf(path); f.piped = input_is_pipe(path); f.no_stream = R.a.no_stream; f.per_gene = R.per_gene; f.pair_filter = R.fp; f.span_count = span_count;
+    f.no_gpu_ingest = no_gpu_ingest(); f.pair_on_host = pair_on_host(); f.sam_on_host = sam_on_host(); f.genes_decode_on_host = genes_decode_on_host();
+    return f;
+}
+
+// The thresholds of the reader-stage pair filter, for the device's filter (cov_pair_filter) and the host's (covh_pair_filter)
+template <class PairFilter> PairFilter pair_thresholds(const Filter &f, bool fs) {
+    PairFilter pf; memset(&pf, 0, sizeof pf);
+    pf.filter_single = fs; pf.min_mapq = (uint8_t)f.mapq; pf.min_aligned_length_single = f.len_single;
+    pf.min_percent_identity_single = f.pid_single; pf.min_aligned_percent_single = f.pct_single;
+    pf.min_aligned_length_pair = f.len_pair; pf.min_percent_identity_pair = f.pid_pair; pf.min_aligned_percent_pair = f.pct_pair;
+    return pf;
+}
+
+// ---- open + header: one function per reader; each sets the sample's header and returns the handle that owns the reader
+BamHeader open_bam_header(Run &R, Sample &S) {
+    char err[512] = {0};
+    BamHeader hd;
+    {   // the first files' headers were read while the HIP runtime came up
+        std::unique_lock<std::mutex> lk(R.hdr_mutex);
+        auto it = R.hdr_ahead.find(S.path);
+        if (it != R.hdr_ahead.end()) {
+            std::future<HeaderAhead> fut = std::move(it->second);
+            R.hdr_ahead.erase(it);
+            lk.unlock();
+            HeaderAhead ha = fut.get();
+            hd.reset(ha.hd);
+            if (!hd && !ha.err.empty()) die(ha.err);
         }
-        if (!hd && !err[0]) hd = covh_bam_read_header(S.path.c_str(), err, sizeof err);
-        if (!hd) die(err);
-        struct HdFree { covh_bam_header *p; ~HdFree() { covh_bam_header_free(p); } } hdfree{hd};
-        set_header(S, covh_bam_header_n_targets(hd), [&](uint32_t t) { return covh_bam_header_target_name(hd, t); },
-                   [&](uint32_t t) { return covh_bam_header_target_len(hd, t); });
-        check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
-        S.t_open = now() - t0;
-        uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
-        check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
-        // (an assembly's statistics are 128 B x millions of contigs: the array is obtained and touched beside the ingest, not behind it)
-        std::future<void> stats_ahead;
-        if (S.tlen.size() >= 65536 && !R.dev_genome) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
-        struct StatsWait { std::future<void> &f; ~StatsWait() { if (f.valid()) f.get(); } } stats_wait{stats_ahead};
-        int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, span_index, span_count, &nrec, tm, err, sizeof err);
-        if (stats_ahead.valid()) stats_ahead.get();
-        if (rc == -2 && span_count > 1) throw SpanUnsorted(err);
-        if (rc < 0) die(err);
-        uint64_t pair_prim = 0; double t_pair = 0;
-        if (rc == 0) group_sample(R, s, S);
-        if (rc == 0 && R.fp) {     // the reader-stage pair filter, on the device
-            const double tp0 = now();
-            cov_pair_filter pf; memset(&pf, 0, sizeof pf);
-            pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
-            pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
-            pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
-            uint64_t nsel = 0;
-            const cov_status prc = cov_pair_filter_apply(s, &pf, &nsel, &pair_prim);
-            if (prc == COV_ERR_INGEST_FALLBACK) { rc = 1; snprintf(err, sizeof err, "%s", cov_last_error(s)); }
-            else check(s, prc);
-            t_pair = now() - tp0;
-            if (timing_on() && rc == 0) fprintf(stderr, "[coverm-amd] %s: pair filter on the device: %llu of %llu records selected, %.3fs\n", S.stoit.c_str(), (unsigned long long)nsel, (unsigned long long)nrec, t_pair);
-        }
-        if (rc == 0) {
-            S.n_records = nrec; S.device_ingest = true;
-            if (timing_on())
-                fprintf(stderr, "[coverm-amd] %s span %u/%u: device ingest: first upload after %.3fs, file read %.3fs, staging waits %.3fs, header walk %.3fs, feed calls %.3fs, inflate tail + parse %.3fs, total %.3fs, %llu records, bytes from %s\n",
-                        S.stoit.c_str(), span_index, span_count, tm[4], tm[0], tm[1], tm[5], tm[6], tm[2], tm[3], (unsigned long long)nrec,
-                        tm[7] == 2 ? "the mapped file (registered up front)" : tm[7] == 1 ? "the mapped file" : tm[7] == 3 ? "staging slots (copied from the mapping)" : "staging slots (pread)");
-            S.t_ingest = now() - t0;
-            cov_summary summ;
-            finish_sample(R, s, S, summ);
-            fetch_results(R, s, S, summ);
-            S.prim = R.fp ? pair_prim : summ.num_detected_primary_alignments;      // filter.rs:129-131 counts every primary record of the input
-            S.t_finish = now() - t0 - S.t_ingest;
-            return;
-        }
-        if (timing_on()) fprintf(stderr, "[coverm-amd] %s: %s\n", S.stoit.c_str(), err);
-        check(s, cov_reset(s));       // the CPU reader takes the file
-        if (R.fp && span_count > 1) die(std::string("--devices with fewer BAM files than devices and a pair-mode filter needs the device ingest, which declined this file: ") + err);
     }
-    if (stream && !R.fp) {
-        char err[512] = {0};
-        covh_bam_stream *st = covh_bam_stream_open(S.path.c_str(), threads, span_index, span_count, err, sizeof err);
-        if (!st) die(err);
-        struct Closer { covh_bam_stream *p; ~Closer() { covh_bam_stream_close(p); } } closer{st};
-        set_header(S, covh_bam_stream_n_targets(st), [&](uint32_t t) { return covh_bam_stream_target_name(st, t); },
-                   [&](uint32_t t) { return covh_bam_stream_target_len(st, t); });
-        check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
-        S.t_open = now() - t0;
-        cov_batch b;
-        int rc;
-        while ((rc = covh_bam_stream_next(st, &b)) == 1) check(s, cov_push_batch(s, &b));
-        if (rc == -2 && span_count > 1) throw SpanUnsorted(covh_bam_stream_error(st));
-        if (rc < 0) die(covh_bam_stream_error(st));
-        S.n_records = covh_bam_stream_n_records(st);
-        S.peak_bytes = covh_bam_stream_peak_bytes(st);
-        if (timing_on()) {
-            double t[5]; covh_bam_stream_timing(st, t);
-            fprintf(stderr, "[coverm-amd] %s span %u/%u: stream read %.3fs inflate %.3fs parse %.3fs (coordinator waits: inflate %.3fs parse %.3fs), %llu records, buffers %.0f MB\n",
-                    S.stoit.c_str(), span_index, span_count, t[0], t[1], t[2], t[3], t[4], (unsigned long long)S.n_records, S.peak_bytes / 1e6);
+    if (!hd) hd.reset(covh_bam_read_header(S.path.c_str(), err, sizeof err));
+    if (!hd) die(err);
+    set_header(S, covh_bam_header_n_targets(hd.get()), [&](uint32_t t) { return covh_bam_header_target_name(hd.get(), t); },
+               [&](uint32_t t) { return covh_bam_header_target_len(hd.get(), t); });
+    return hd;
+}
+
+BamStream open_bam_stream(Sample &S, int threads, uint32_t span_index, uint32_t span_count) {
+    char err[512] = {0};
+    BamStream st(covh_bam_stream_open(S.path.c_str(), threads, span_index, span_count, err, sizeof err));
+    if (!st) die(err);
+    set_header(S, covh_bam_stream_n_targets(st.get()), [&](uint32_t t) { return covh_bam_stream_target_name(st.get(), t); },
+               [&](uint32_t t) { return covh_bam_stream_target_len(st.get(), t); });
+    return st;
+}
+
+// (the header only when the bytes are text: covh_sam_kind says so)
+SamText open_sam(Run &R, Sample &S) {
+    char err[512] = {0};
+    SamText h;
+    {   // a pipe was opened before the sessions existed; ingest() runs in one thread per device: the map is shared, as hdr_ahead is
+        std::lock_guard<std::mutex> lk(R.hdr_mutex);
+        auto it = R.sam_ahead.find(S.path);
+        if (it != R.sam_ahead.end()) { h.reset(it->second); R.sam_ahead.erase(it); }
+    }
+    if (!h) h.reset(covh_sam_open(S.path.c_str(), err, sizeof err));
+    if (!h) die(err);
+    if (covh_sam_kind(h.get()) == 0)
+        set_header(S, covh_sam_n_targets(h.get()), [&](uint32_t t) { return covh_sam_target_name(h.get(), t); }, [&](uint32_t t) { return covh_sam_target_len(h.get(), t); });
+    return h;
+}
+
+BamWhole open_bam_whole(Run &R, Sample &S, int threads) {
+    char err[512] = {0};
+    BamWhole bam(covh_bam_open(S.path.c_str(), threads, R.fp ? 1 : 0, err, sizeof err));
+    if (!bam) die(err);
+    set_header(S, covh_bam_n_targets(bam.get()), [&](uint32_t t) { return covh_bam_target_name(bam.get(), t); }, [&](uint32_t t) { return covh_bam_target_len(bam.get(), t); });
+    return bam;
+}
+
+// The session takes the sample's references (and, for the contig-names genome scan, their genomes); a device reader is told what to keep.
+// `mask`: the genome table's participation mask when the caller has built the table already (the whole-file reader, before its host work).
+void prepare_session(Run &R, cov_session *s, Sample &S, double t0, bool device_reader, std::vector<uint8_t> mask = {}) {
+    check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
+    if (R.by_names) { if (mask.empty()) genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
+    S.t_open = now() - t0;
+    if (!device_reader) return;
+    check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
+    check(s, cov_ingest_want_grouping(s, R.a.unsorted ? 1 : 0));
+}
+
+// What a reader left behind: the reason when it hands the file back, else what the tail and the timing lines need
+struct Fed {
+    bool declined = false; std::string why;
+    uint64_t nrec = 0;
+    uint64_t prim = 0; bool have_prim = false;      // a pair-mode filter counts every primary record of the input itself (filter.rs:129-131)
+    double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0}; bool from_pipe = false;
+};
+
+// ---- feed, device ingest: the compressed file goes to HBM, the GPU inflates, finds the records and fills its own store
+Fed feed_device_bgzf(Run &R, cov_session *s, Sample &S, const covh_bam_header *hd, int threads, uint32_t span_index, uint32_t span_count) {
+    Fed fed; char err[512] = {0};
+    // (an assembly's statistics are 128 B x millions of contigs: the array is obtained and touched beside the ingest, not behind it;
+    // a std::async future joins in its destructor, so every way out of this function waits for the thread)
+    std::future<void> stats_ahead;
+    if (S.tlen.size() >= 65536 && !R.dev_genome && !R.per_gene) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
+    const int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, span_index, span_count, &fed.nrec, fed.tm, err, sizeof err);
+    if (stats_ahead.valid()) stats_ahead.get();
+    if (rc == -2 && span_count > 1) throw SpanUnsorted(err);
+    if (rc < 0) die(err);
+    if (rc) { fed.declined = true; fed.why = err; }
+    return fed;
+}
+
+// ---- feed, streamed CPU reader: windows of BGZF blocks inflated and parsed on the host, pushed batch by batch
+void feed_cpu_stream(cov_session *s, Sample &S, covh_bam_stream *st, uint32_t span_index, uint32_t span_count) {
+    cov_batch b;
+    int rc;
+    while ((rc = covh_bam_stream_next(st, &b)) == 1) check(s, cov_push_batch(s, &b));
+    if (rc == -2 && span_count > 1) throw SpanUnsorted(covh_bam_stream_error(st));
+    if (rc < 0) die(covh_bam_stream_error(st));
+    S.n_records = covh_bam_stream_n_records(st);
+    S.peak_bytes = covh_bam_stream_peak_bytes(st);
+    if (timing_on()) {
+        double t[5]; covh_bam_stream_timing(st, t);
+        fprintf(stderr, "[coverm-amd] %s span %u/%u: stream read %.3fs inflate %.3fs parse %.3fs (coordinator waits: inflate %.3fs parse %.3fs), %llu records, buffers %.0f MB\n",
+                S.stoit.c_str(), span_index, span_count, t[0], t[1], t[2], t[3], t[4], (unsigned long long)S.n_records, S.peak_bytes / 1e6);
+    }
+}
+
+// ---- feed, SAM text (a file or a pipe): decoded on the device window by window as it is read (cov_sam_*)
+Fed feed_device_sam(cov_session *s, covh_sam *h, int threads) {
+    Fed fed; char err[512] = {0};
+    fed.from_pipe = covh_sam_is_pipe(h) != 0;
+    const int rc = covh_sam_gpu_ingest(h, threads, s, &fed.nrec, fed.tm, err, sizeof err);
+    if (rc < 0) die(err);
+    if (rc) { fed.declined = true; fed.why = err; }
+    return fed;
+}
+
+// ---- whole file on the host: SAM text, files the device ingest declined, --no-stream.  `batch` ends as the records to push — the
+// file's, grouped by reference for --unsorted, selected by the host's pair filter — which the gene driver walks afterwards.
+struct WholeFile { BamWhole bam; OwnedBatch selected, grouped; };
+
+void select_on_host(Run &R, Sample &S, int threads, WholeFile &whole, cov_batch &batch, Fed &fed) {
+    const Args &a = R.a;
+    covh_bam *bam = whole.bam.get();
+    covh_bam_batch(bam, &batch);
+    S.n_records = batch.n_records;
+    const int32_t *mtid = covh_bam_mtid(bam); const uint32_t *qoff = covh_bam_qname_off(bam); const char *qnames = covh_bam_qnames(bam);
+    std::vector<int32_t> g_mtid; std::vector<uint32_t> g_qoff; std::string g_qnames;
+    if (a.unsorted && (R.fp || R.per_gene)) {
+        // the host's pair filter and the gene driver walk the whole-file arrays themselves: they see the sequence the device's grouping gives
+        uint64_t *order = nullptr, moved = 0;
+        if (covh_group_by_reference(batch.tid, batch.n_records, (uint32_t)S.tlen.size(), &order, &moved) != COV_OK) die("--unsorted: grouping the records on the host failed");
+        if (moved) {
+            const uint64_t n = batch.n_records;
+            const int src = covh_batch_select(&batch, order, n, threads, &whole.grouped.b);
+            if (src != COV_OK) { covh_free(order); die("--unsorted: grouping the records on the host failed"); }
+            if (R.fp && qoff) {
+                g_mtid.resize(n); g_qoff.resize(n + 1); g_qoff[0] = 0;
+                for (uint64_t j = 0; j < n; j++) { g_mtid[j] = mtid[order[j]]; g_qoff[j + 1] = g_qoff[j] + (qoff[order[j] + 1] - qoff[order[j]]); }
+                g_qnames.resize(g_qoff[n]);
+                for (uint64_t j = 0; j < n; j++) memcpy(&g_qnames[g_qoff[j]], qnames + qoff[order[j]], g_qoff[j + 1] - g_qoff[j]);
+                mtid = g_mtid.data(); qoff = g_qoff.data(); qnames = g_qnames.data();
+            }
+            batch = whole.grouped.b;
         }
-        group_sample(R, s, S);
-        S.t_ingest = now() - t0;
-        cov_summary summ;
-        finish_sample(R, s, S, summ);
-        fetch_results(R, s, S, summ);
-        S.prim = summ.num_detected_primary_alignments;
-        S.t_finish = now() - t0 - S.t_ingest;
+        covh_free(order);
+        if (a.verbose || timing_on()) fprintf(stderr, "[coverm-amd] %s: --unsorted: %llu records moved while grouping by reference on the host\n", S.stoit.c_str(), (unsigned long long)moved);
+    }
+    if (R.fp) {      // the reader-stage pair filter, on the host (Run::fp is only ever set when a filter is on: Filter::doing_filtering)
+        for (uint64_t i = 0; i < batch.n_records; i++) if (!(batch.flag[i] & 0x900)) fed.prim++;   // filter.rs:129-131
+        fed.have_prim = true;
+        const covh_pair_filter pf = pair_thresholds<covh_pair_filter>(R.f, R.fs);
+        uint64_t *order = nullptr, n_order = 0;
+        const int prc = covh_pair_mode_order(&batch, mtid, qoff, qnames, &pf, threads, &order, &n_order);
+        if (prc == COV_ERR_NM_MISSING) die("Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format");
+        if (prc != COV_OK) die(prc == COV_ERR_NM_BADTYPE ? "Unexpected data type of NM aux tag" : "pair filter failed");
+        const int src = covh_batch_select(&batch, order, n_order, threads, &whole.selected.b);
+        covh_free(order);
+        if (src != COV_OK) die("pair filter: selection failed");
+        batch = whole.selected.b;
+    }
+}
+
+// ---- behind the last record of every reader: --unsorted grouping; behind a device reader, the reader-stage pair filter (filter.rs:117-228)
+// on the device, over the mate reference + read-name hash the ingest kept per record.  It may hand the file back, as the ingest may.
+void after_ingest(Run &R, cov_session *s, const Sample &S, Route route, Fed &fed) {
+    group_sample(R, s, S);      // (nothing moves when the host grouped the arrays, or its pair filter selected from them)
+    if (!R.fp || (route != Route::DeviceBgzf && route != Route::DeviceSam)) return;
+    const double tp0 = now();
+    const cov_pair_filter pf = pair_thresholds<cov_pair_filter>(R.f, R.fs);
+    uint64_t nsel = 0;
+    const cov_status prc = cov_pair_filter_apply(s, &pf, &nsel, &fed.prim);
+    if (prc == COV_ERR_INGEST_FALLBACK) { fed.declined = true; fed.why = cov_last_error(s); return; }
+    check(s, prc);
+    fed.have_prim = true;
+    if (timing_on() && route == Route::DeviceBgzf)
+        fprintf(stderr, "[coverm-amd] %s: pair filter on the device: %llu of %llu records selected, %.3fs\n", S.stoit.c_str(), (unsigned long long)nsel, (unsigned long long)fed.nrec, now() - tp0);
+}
+
+void report_device_reader(cov_session *s, const Sample &S, Route route, const Fed &fed, uint32_t span_index, uint32_t span_count) {
+    const double *tm = fed.tm;
+    if (route == Route::DeviceBgzf) {
+        fprintf(stderr, "[coverm-amd] %s span %u/%u: device ingest: first upload after %.3fs, file read %.3fs, staging waits %.3fs, header walk %.3fs, feed calls %.3fs, inflate tail + parse %.3fs, total %.3fs, %llu records, bytes from %s\n",
+                S.stoit.c_str(), span_index, span_count, tm[4], tm[0], tm[1], tm[5], tm[6], tm[2], tm[3], (unsigned long long)fed.nrec,
+                tm[7] == 2 ? "the mapped file (registered up front)" : tm[7] == 1 ? "the mapped file" : tm[7] == 3 ? "staging slots (copied from the mapping)" : "staging slots (pread)");
         return;
     }
-    // ---- --gff over a BAM the device can ingest: the device inflates and parses (and applies a pair-mode filter), then the records
-    // the gene driver needs on the host (per-read vectors, genes.rs:182-344) come BACK from the session's store — 24 B per record
-    // + CIGAR words over PCIe instead of a whole-file decode on the host
-    char err[512] = {0};
-    cov_batch batch; memset(&batch, 0, sizeof batch);
-    struct HostRecords { std::vector<int32_t> tid, pos; std::vector<uint16_t> flag; std::vector<uint8_t> mapq, nmk; std::vector<uint32_t> nm, lseq, coff, cig; } hr;
-    bool have_records = false, prim_from_host = false;
-    // ---- SAM text (a file or a pipe): decoded on the device window by window as it is read (cov_sam_*); what follows the ingest — grouping,
-    // the pair filter, finish, or the records' way back for --gff — is what follows the BGZF ingest
-    const bool sam_dev = !bgzf && !a.no_stream && !sam_on_host() && span_count == 1 && !(R.fp && pair_on_host()) && (piped || !no_gpu_ingest());
-    if (!bgzf && piped && !sam_dev) die("a pipe ('-b -', a FIFO) is decoded on the device only: COVERM_SAM_ON_HOST / COVERM_PAIR_ON_HOST need a file");
-    if (sam_dev) {
-        covh_sam *h = nullptr;
-        {   // ingest() runs in one thread per device: the map is shared, as hdr_ahead is
-            std::lock_guard<std::mutex> lk(R.hdr_mutex);
-            auto it = R.sam_ahead.find(S.path);
-            if (it != R.sam_ahead.end()) { h = it->second; R.sam_ahead.erase(it); }
-        }
-        if (!h) h = covh_sam_open(S.path.c_str(), err, sizeof err);
-        if (!h) die(err);
-        struct SamClose { covh_sam *p; ~SamClose() { covh_sam_close(p); } } samclose{h};
-        int rc = covh_sam_kind(h) == 0 ? 0 : 1;
-        if (rc) snprintf(err, sizeof err, "%s", "the file is not text (NUL bytes in its first piece)");
-        uint64_t nrec = 0; double tm[4] = {0, 0, 0, 0};
-        if (rc == 0) {
-            set_header(S, covh_sam_n_targets(h), [&](uint32_t t) { return covh_sam_target_name(h, t); }, [&](uint32_t t) { return covh_sam_target_len(h, t); });
-            check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-            if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
-            S.t_open = now() - t0;
-            check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
-            check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
-            rc = covh_sam_gpu_ingest(h, threads, s, &nrec, tm, err, sizeof err);
-            if (rc < 0) die(err);
-        }
-        uint64_t pair_prim = 0;
-        if (rc == 0) group_sample(R, s, S);
-        if (rc == 0 && R.fp) {
-            cov_pair_filter pf; memset(&pf, 0, sizeof pf);
-            pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
-            pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
-            pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
-            uint64_t nsel = 0;
-            const cov_status prc = cov_pair_filter_apply(s, &pf, &nsel, &pair_prim);
-            if (prc == COV_ERR_INGEST_FALLBACK) { rc = 1; snprintf(err, sizeof err, "%s", cov_last_error(s)); }
-            else check(s, prc);
-        }
-        if (rc != 0) {
-            if (piped) die(S.stoit + ": " + err + " — a pipe cannot be read again: write the stream to a file");
-            if (a.verbose || timing_on()) fprintf(stderr, "[coverm-amd] %s: SAM text handed to the host route (whole file): %s\n", S.stoit.c_str(), err);
-            check(s, cov_reset(s));
-        } else {
-            S.n_records = nrec; S.device_ingest = true;
-            if (timing_on()) {
-                double ms = 0; uint32_t launches = 0;
-                (void)cov_kernel_ms(s, COV_K_SAM, &ms, &launches);
-                fprintf(stderr, "[coverm-amd] %s: device SAM decode from %s: read %.3fs, slot waits %.3fs, feed calls %.3fs, total %.3fs, %llu records, decode kernels %.3f ms\n",
-                        S.stoit.c_str(), covh_sam_is_pipe(h) ? "a pipe" : "the file", tm[0], tm[1], tm[2], tm[3], (unsigned long long)nrec, ms);
-            }
-            if (!R.per_gene) {
-                S.t_ingest = now() - t0;
-                cov_summary summ;
-                finish_sample(R, s, S, summ);
-                fetch_results(R, s, S, summ);
-                S.prim = R.fp ? pair_prim : summ.num_detected_primary_alignments;
-                S.t_finish = now() - t0 - S.t_ingest;
-                return;
-            }
-            if (R.fp) { S.prim = pair_prim; prim_from_host = true; }
-            uint64_t n = 0, nc = 0;
-            check(s, cov_copy_records(s, nullptr, &n, &nc));
-            hr.tid.resize(n); hr.pos.resize(n); hr.flag.resize(n); hr.mapq.resize(n); hr.nmk.resize(n); hr.nm.resize(n); hr.lseq.resize(n);
-            hr.coff.resize(n + 1); hr.cig.resize(nc + 1);
-            batch.tid = hr.tid.data(); batch.pos = hr.pos.data(); batch.flag = hr.flag.data(); batch.mapq = hr.mapq.data(); batch.nm = hr.nm.data();
-            batch.nm_kind = hr.nmk.data(); batch.l_seq = hr.lseq.data(); batch.cigar_off = hr.coff.data(); batch.cigar = hr.cig.data(); batch.n_records = n;
-            check(s, cov_copy_records(s, &batch, nullptr, nullptr));
-            if (n == 0) hr.coff[0] = 0;
-            have_records = true;
-        }
+    double ms = 0; uint32_t launches = 0;
+    (void)cov_kernel_ms(s, COV_K_SAM, &ms, &launches);
+    fprintf(stderr, "[coverm-amd] %s: device SAM decode from %s: read %.3fs, slot waits %.3fs, feed calls %.3fs, total %.3fs, %llu records, decode kernels %.3f ms\n",
+            S.stoit.c_str(), fed.from_pipe ? "a pipe" : "the file", tm[0], tm[1], tm[2], tm[3], (unsigned long long)fed.nrec, ms);
+}
+
+// ---- --gff behind a device reader: the records the gene driver needs on the host (per-read vectors, genes.rs:182-344) come BACK from the
+// session's store — 24 B per record + CIGAR words over PCIe instead of a whole-file decode on the host
+struct HostRecords { std::vector<int32_t> tid, pos; std::vector<uint16_t> flag; std::vector<uint8_t> mapq, nmk; std::vector<uint32_t> nm, lseq, coff, cig; };
+
+void records_back(cov_session *s, HostRecords &hr, cov_batch &batch) {
+    uint64_t n = 0, nc = 0;
+    check(s, cov_copy_records(s, nullptr, &n, &nc));
+    hr.tid.resize(n); hr.pos.resize(n); hr.flag.resize(n); hr.mapq.resize(n); hr.nmk.resize(n); hr.nm.resize(n); hr.lseq.resize(n);
+    hr.coff.resize(n + 1); hr.cig.resize(nc + 1);
+    batch.tid = hr.tid.data(); batch.pos = hr.pos.data(); batch.flag = hr.flag.data(); batch.mapq = hr.mapq.data(); batch.nm = hr.nm.data();
+    batch.nm_kind = hr.nmk.data(); batch.l_seq = hr.lseq.data(); batch.cigar_off = hr.coff.data(); batch.cigar = hr.cig.data(); batch.n_records = n;
+    check(s, cov_copy_records(s, &batch, nullptr, nullptr));
+    if (n == 0) hr.coff[0] = 0;
+}
+
+// genes.rs:182-344: per-gene reductions over this sample's depth, while the session holds it
+void gene_coverage(Run &R, cov_session *s, Sample &S, const cov_batch &batch) {
+    const Args &a = R.a;
+    std::lock_guard<std::mutex> lk(R.taker_mutex);
+    const covh_header gh = S.header();
+    covh_genome_namer nm; memset(&nm, 0, sizeof nm);
+    std::vector<const char *> gn;
+    for (auto &g : R.genomes) gn.push_back(g.c_str());
+    if (!R.contig) {
+        nm.mode = a.single_genome ? 1 : a.have_separator ? 2 : 3;
+        nm.separator = (uint8_t)a.separator;
+        nm.genome_of_tid = S.genome_of_tid.data(); nm.genome_names = gn.data();
     }
-    if (R.per_gene && bgzf && !a.no_stream && span_count == 1 && !no_gpu_ingest() && !getenv("COVERM_GENES_DECODE_ON_HOST") && !pair_on_host()) {
-        covh_bam_header *hd = covh_bam_read_header(S.path.c_str(), err, sizeof err);
-        if (!hd) die(err);
-        struct HdFree { covh_bam_header *p; ~HdFree() { covh_bam_header_free(p); } } hdfree{hd};
-        set_header(S, covh_bam_header_n_targets(hd), [&](uint32_t t) { return covh_bam_header_target_name(hd, t); },
-                   [&](uint32_t t) { return covh_bam_header_target_len(hd, t); });
-        check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
-        if (R.by_names) { genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
-        check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
-        check(s, cov_ingest_want_grouping(s, a.unsorted ? 1 : 0));
-        uint64_t nrec = 0; double tm[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, 0, 1, &nrec, tm, err, sizeof err);
-        if (rc < 0) die(err);
-        S.n_records = nrec;
-        if (rc == 0) group_sample(R, s, S);
-        if (rc == 0 && R.fp) {
-            cov_pair_filter pf; memset(&pf, 0, sizeof pf);
-            pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
-            pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
-            pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
-            uint64_t nsel = 0, prim = 0;
-            const cov_status prc = cov_pair_filter_apply(s, &pf, &nsel, &prim);
-            if (prc == COV_ERR_INGEST_FALLBACK) rc = 1;
-            else { check(s, prc); S.prim = prim; prim_from_host = true; }
+    auto depth_cb = [](void *ctx, uint32_t tid, int32_t *out) -> int { return (int)cov_copy_depth((cov_session *)ctx, tid, out); };
+    const int grc = covh_gene_coverage(&gh, R.genes, &nm, S.stoit.c_str(), &batch, &R.cfg, getenv("COVERM_GENES_ON_HOST") ? nullptr : s, depth_cb, s,
+                                       S.prim, R.taker, R.est.data(), R.est.size(), !a.no_zeros, &S.gene_rm);
+    if (grc == COV_ERR_HIP || grc == COV_ERR_STATE) die(cov_last_error(s));
+    if (grc != COV_OK) die(covh_last_error());
+}
+
+// Decode + push + finish of one BAM (or one tid span of it) on one session.  Leaves the session finished.
+void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index, uint32_t span_count) {
+    const RouteFacts facts = route_facts(R, S.path, span_count);
+    Decision d = cli_route::first_route(facts);
+    S.stoit = stoit_of(S.path);
+    const double t0 = now();
+    WholeFile whole; HostRecords hr;
+    cov_batch batch; memset(&batch, 0, sizeof batch);      // the sample's records on the host, for the gene driver
+    Fed fed;
+    for (;;) {
+        if (d.refused()) die(d.refusal);
+        check(s, cov_reset(s));
+        fed = Fed(); S.streamed = d.route == Route::CpuStream;
+        switch (d.route) {
+        case Route::DeviceBgzf: {
+            const BamHeader hd = open_bam_header(R, S);
+            prepare_session(R, s, S, t0, true);
+            fed = feed_device_bgzf(R, s, S, hd.get(), threads, span_index, span_count);
+            break;
         }
-        if (rc == 0) {
-            uint64_t n = 0, nc = 0;
-            check(s, cov_copy_records(s, nullptr, &n, &nc));
-            hr.tid.resize(n); hr.pos.resize(n); hr.flag.resize(n); hr.mapq.resize(n); hr.nmk.resize(n); hr.nm.resize(n); hr.lseq.resize(n);
-            hr.coff.resize(n + 1); hr.cig.resize(nc + 1);
-            batch.tid = hr.tid.data(); batch.pos = hr.pos.data(); batch.flag = hr.flag.data(); batch.mapq = hr.mapq.data(); batch.nm = hr.nm.data();
-            batch.nm_kind = hr.nmk.data(); batch.l_seq = hr.lseq.data(); batch.cigar_off = hr.coff.data(); batch.cigar = hr.cig.data(); batch.n_records = n;
-            check(s, cov_copy_records(s, &batch, nullptr, nullptr));
-            if (n == 0) hr.coff[0] = 0;
-            have_records = true; S.device_ingest = true;
-            if (timing_on()) fprintf(stderr, "[coverm-amd] %s: --gff over the device ingest: %llu records came back from the store\n", S.stoit.c_str(), (unsigned long long)n);
-        } else {
-            if (timing_on()) fprintf(stderr, "[coverm-amd] %s: %s\n", S.stoit.c_str(), err[0] ? err : cov_last_error(s));
-            check(s, cov_reset(s)); S.prim = 0; prim_from_host = false;
+        case Route::CpuStream: {
+            const BamStream st = open_bam_stream(S, threads, span_index, span_count);
+            prepare_session(R, s, S, t0, false);
+            feed_cpu_stream(s, S, st.get(), span_index, span_count);
+            break;
         }
+        case Route::DeviceSam: {
+            const SamText h = open_sam(R, S);
+            if (covh_sam_kind(h.get()) != 0) { fed.declined = true; fed.why = "the file is not text (NUL bytes in its first piece)"; break; }
+            prepare_session(R, s, S, t0, true);
+            fed = feed_device_sam(s, h.get(), threads);
+            break;
+        }
+        case Route::HostWhole: {
+            whole.bam = open_bam_whole(R, S, threads);
+            std::vector<uint8_t> mask;
+            if (R.by_names) genome_table(R, S, mask);      // (its refusal comes before those of the host's pair filter)
+            select_on_host(R, S, threads, whole, batch, fed);
+            prepare_session(R, s, S, t0, false, std::move(mask));
+            check(s, cov_push_batch(s, &batch));
+            break;
+        }
+        }
+        if (!fed.declined) after_ingest(R, s, S, d.route, fed);
+        if (!fed.declined) break;
+        // the reader handed the file back: the next one takes it, on the session as cov_reset leaves it
+        const bool sam = d.route == Route::DeviceSam;
+        if (!sam && timing_on()) fprintf(stderr, "[coverm-amd] %s: %s\n", S.stoit.c_str(), fed.why.c_str());
+        d = cli_route::after_decline(d.route, facts, S.stoit, fed.why);
+        if (sam && !d.refused() && (R.a.verbose || timing_on()))
+            fprintf(stderr, "[coverm-amd] %s: SAM text handed to the host route (whole file): %s\n", S.stoit.c_str(), fed.why.c_str());
     }
-    // ---- whole file on the host: SAM text, files the device ingest declined, --no-stream
-    covh_bam *bam = nullptr;
-    struct Closer { covh_bam *&p; ~Closer() { if (p) covh_bam_close(p); } } closer{bam};
-    cov_batch selected; memset(&selected, 0, sizeof selected);
-    struct Freer { cov_batch *b; ~Freer() { if (b->tid) covh_batch_free(b); } } freer{&selected};
-    cov_batch grouped; memset(&grouped, 0, sizeof grouped);
-    Freer freer_grouped{&grouped};
-    std::vector<int32_t> g_mtid; std::vector<uint32_t> g_qoff; std::string g_qnames;
-    if (!have_records) {
-        bam = covh_bam_open(S.path.c_str(), threads, R.fp ? 1 : 0, err, sizeof err);
-        if (!bam) die(err);
-        set_header(S, covh_bam_n_targets(bam), [&](uint32_t t) { return covh_bam_target_name(bam, t); }, [&](uint32_t t) { return covh_bam_target_len(bam, t); });
-        if (R.by_names) genome_table(R, S, mask);
-        covh_bam_batch(bam, &batch);
-        S.n_records = batch.n_records;
-        const int32_t *mtid = covh_bam_mtid(bam); const uint32_t *qoff = covh_bam_qname_off(bam); const char *qnames = covh_bam_qnames(bam);
-        const bool host_pair = R.f.doing_filtering() && !(R.fs && !R.fp);
-        if (a.unsorted && (host_pair || R.per_gene)) {
-            // the host's pair filter and the gene driver walk the whole-file arrays themselves: they see the sequence the device's grouping gives
-            uint64_t *order = nullptr, moved = 0;
-            if (covh_group_by_reference(batch.tid, batch.n_records, (uint32_t)S.tlen.size(), &order, &moved) != COV_OK) die("--unsorted: grouping the records on the host failed");
-            if (moved) {
-                const uint64_t n = batch.n_records;
-                const int src = covh_batch_select(&batch, order, n, threads, &grouped);
-                if (src != COV_OK) { covh_free(order); die("--unsorted: grouping the records on the host failed"); }
-                if (host_pair && qoff) {
-                    g_mtid.resize(n); g_qoff.resize(n + 1); g_qoff[0] = 0;
-                    for (uint64_t j = 0; j < n; j++) { g_mtid[j] = mtid[order[j]]; g_qoff[j + 1] = g_qoff[j] + (qoff[order[j] + 1] - qoff[order[j]]); }
-                    g_qnames.resize(g_qoff[n]);
-                    for (uint64_t j = 0; j < n; j++) memcpy(&g_qnames[g_qoff[j]], qnames + qoff[order[j]], g_qoff[j + 1] - g_qoff[j]);
-                    mtid = g_mtid.data(); qoff = g_qoff.data(); qnames = g_qnames.data();
-                }
-                batch = grouped;
-            }
-            covh_free(order);
-            if (a.verbose || timing_on()) fprintf(stderr, "[coverm-amd] %s: --unsorted: %llu records moved while grouping by reference on the host\n", S.stoit.c_str(), (unsigned long long)moved);
+    if (d.route == Route::DeviceBgzf || d.route == Route::DeviceSam) {
+        S.n_records = fed.nrec; S.device_ingest = true;
+        if (timing_on()) report_device_reader(s, S, d.route, fed, span_index, span_count);
+        if (R.per_gene) {
+            records_back(s, hr, batch);
+            if (timing_on() && d.route == Route::DeviceBgzf)
+                fprintf(stderr, "[coverm-amd] %s: --gff over the device ingest: %llu records came back from the store\n", S.stoit.c_str(), (unsigned long long)batch.n_records);
         }
-        if (host_pair) {
-            for (uint64_t i = 0; i < batch.n_records; i++) if (!(batch.flag[i] & 0x900)) S.prim++;   // filter.rs:129-131
-            prim_from_host = true;
-            covh_pair_filter pf; memset(&pf, 0, sizeof pf);
-            pf.filter_single = R.fs; pf.min_mapq = (uint8_t)R.f.mapq; pf.min_aligned_length_single = R.f.len_single;
-            pf.min_percent_identity_single = R.f.pid_single; pf.min_aligned_percent_single = R.f.pct_single;
-            pf.min_aligned_length_pair = R.f.len_pair; pf.min_percent_identity_pair = R.f.pid_pair; pf.min_aligned_percent_pair = R.f.pct_pair;
-            uint64_t *order = nullptr, n_order = 0;
-            const int prc = covh_pair_mode_order(&batch, mtid, qoff, qnames, &pf, threads, &order, &n_order);
-            if (prc == COV_ERR_NM_MISSING) die("Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format");
-            if (prc != COV_OK) die(prc == COV_ERR_NM_BADTYPE ? "Unexpected data type of NM aux tag" : "pair filter failed");
-            const int src = covh_batch_select(&batch, order, n_order, threads, &selected);
-            covh_free(order);
-            if (src != COV_OK) die("pair filter: selection failed");
-            batch = selected;
-        }
-    }
-    const uint32_t nt = (uint32_t)S.tlen.size();
-    S.t_open = now() - t0;
-    if (!have_records) {
-        check(s, cov_set_targets(s, nt, S.tlen.data()));
-        if (R.by_names) set_genomes_or_mask(R, s, S, mask);
-        check(s, cov_push_batch(s, &batch));
-        group_sample(R, s, S);      // (nothing moves when the host grouped the arrays above, or its pair filter selected from them)
     }
     S.t_ingest = now() - t0;
     cov_summary summ;
     finish_sample(R, s, S, summ);
     fetch_results(R, s, S, summ);
-    if (!prim_from_host) S.prim = summ.num_detected_primary_alignments;
-    if (R.per_gene) {   // genes.rs:182-344: per-gene reductions over this sample's depth, while the session holds it
-        std::lock_guard<std::mutex> lk(R.taker_mutex);
-        const covh_header gh = S.header();
-        covh_genome_namer nm; memset(&nm, 0, sizeof nm);
-        std::vector<const char *> gn;
-        for (auto &g : R.genomes) gn.push_back(g.c_str());
-        if (!R.contig) {
-            nm.mode = a.single_genome ? 1 : a.have_separator ? 2 : 3;
-            nm.separator = (uint8_t)a.separator;
-            nm.genome_of_tid = S.genome_of_tid.data(); nm.genome_names = gn.data();
-        }
-        auto depth_cb = [](void *ctx, uint32_t tid, int32_t *out) -> int { return (int)cov_copy_depth((cov_session *)ctx, tid, out); };
-        const int grc = covh_gene_coverage(&gh, R.genes, &nm, S.stoit.c_str(), &batch, &R.cfg, getenv("COVERM_GENES_ON_HOST") ? nullptr : s, depth_cb, s,
-                                           S.prim, R.taker, R.est.data(), R.est.size(), !a.no_zeros, &S.gene_rm);
-        if (grc == COV_ERR_HIP || grc == COV_ERR_STATE) die(cov_last_error(s));
-        if (grc != COV_OK) die(covh_last_error());
-    }
+    S.prim = fed.have_prim ? fed.prim : summ.num_detected_primary_alignments;
+    if (R.per_gene) gene_coverage(R, s, S, batch);
     S.t_finish = now() - t0 - S.t_ingest;
+}
+
+// --genome-definition: a genome name and a contig name per line, into R.genomes / R.c2g
+void read_genome_definition(Run &R) {
+    const Args &a = R.a;
+    if (a.genome_definition.empty()) die("genome mode over BAM files needs --separator, --single-genome or --genome-definition");
+    FILE *fh = fopen(a.genome_definition.c_str(), "r");
+    if (!fh) die("cannot open " + a.genome_definition);
+    struct FClose { FILE *f; ~FClose() { fclose(f); } } fclose_{fh};
+    std::vector<char> linebuf(1 << 16);
+    char *line = linebuf.data();
+    std::unordered_map<std::string, int32_t> gi;
+    auto is_ws = [](unsigned char ch) { return ch == ' ' || (ch >= 9 && ch <= 13); };
+    while (fgets(line, (int)linebuf.size(), fh)) {   // read_genome_definition_file, genome_parsing.rs:71-141
+        std::string l(line);
+        if (!l.empty() && l.back() == '\n') l.pop_back();
+        if (!l.empty() && l.back() == '\r') l.pop_back();
+        const size_t t = l.find('\t');
+        if (t == std::string::npos || l.find('\t', t + 1) != std::string::npos)   // blank lines included (:116-124)
+            die("The line \"" + l + "\" in the genome definition file is not a genome name and contig name separated by a tab");
+        std::string g = l.substr(0, t);
+        { size_t x = 0, y = g.size(); while (x < y && is_ws((unsigned char)g[x])) x++; while (y > x && is_ws((unsigned char)g[y - 1])) y--; g = g.substr(x, y - x); }
+        size_t x = t + 1;
+        while (x < l.size() && is_ws((unsigned char)l[x])) x++;
+        size_t y = x;
+        while (y < l.size() && !is_ws((unsigned char)l[y])) y++;
+        if (x == y) die("Failed to split contig name by whitespace in genome definition file");
+        const std::string c = l.substr(x, y - x);                                  // first token: comments after it are dropped
+        auto it = gi.find(g);
+        if (it == gi.end()) { it = gi.emplace(g, (int32_t)R.genomes.size()).first; R.genomes.push_back(g); }
+        auto cit = R.c2g.find(c);
+        if (cit != R.c2g.end() && cit->second != it->second) die("The contig name '" + c + "' was assigned to multiple genomes");
+        if (cit == R.c2g.end()) R.c2g[c] = it->second;
+    }
+}
+
+// COVERM_CLI_TIMING: the resident set of the process and its largest mappings
+void report_resident_set() {
+    // where the resident set comes from (VmHWM = peak; RssShmem counts page-locked / device-visible mappings of the HIP runtime)
+    if (FILE *ps = fopen("/proc/self/status", "r")) {
+        char ln[256];
+        while (fgets(ln, sizeof ln, ps))
+            if (!strncmp(ln, "VmHWM", 5) || !strncmp(ln, "VmRSS", 5) || !strncmp(ln, "RssAnon", 7) || !strncmp(ln, "RssFile", 7) || !strncmp(ln, "RssShmem", 8)) {
+                ln[strcspn(ln, "\n")] = 0;
+                fprintf(stderr, "[coverm-amd] %s\n", ln);
+            }
+        fclose(ps);
+    }
+    // ... and its eight largest mappings (what the kernel has to take apart when the process ends)
+    if (FILE *sm = fopen("/proc/self/smaps", "r")) {
+        struct M { unsigned long long rss_kb, size_kb; std::string what; };
+        std::vector<M> ms;
+        char ln[512]; std::string cur; unsigned long long size_kb = 0;
+        while (fgets(ln, sizeof ln, sm)) {
+            unsigned long long a, b2, v;
+            if (sscanf(ln, "%llx-%llx ", &a, &b2) == 2 && strchr(ln, '-') && strchr(ln, '-') < ln + 17) {
+                ln[strcspn(ln, "\n")] = 0;
+                const char *path = strchr(ln, '/'); const char *br = strchr(ln, '[');
+                cur = path ? path : br ? br : "(anonymous)"; size_kb = (b2 - a) >> 10;
+            } else if (sscanf(ln, "Rss: %llu kB", &v) == 1) ms.push_back({v, size_kb, cur});
+        }
+        fclose(sm);
+        std::sort(ms.begin(), ms.end(), [](const M &x, const M &y) { return x.rss_kb > y.rss_kb; });
+        for (size_t i = 0; i < ms.size() && i < 8; i++)
+            fprintf(stderr, "[coverm-amd] mapping %zu: %llu MB resident of %llu MB, %s\n", i, ms[i].rss_kb >> 10, ms[i].size_kb >> 10, ms[i].what.c_str());
+    }
+}
+
+// Span mode: the per-contig result blocks of one file's spans meet on the first device through one RCCL gather (cov_gather) and become one sample
+void merge_spans(Run &R, std::vector<cov_session *> &sess, const std::vector<Sample> &part, Sample &S) {
+    const size_t nd = part.size();
+    const std::vector<covh_estimator> &est = R.est;
+    S.stoit = part[0].stoit; S.names_blob = part[0].names_blob; S.name_off = part[0].name_off; S.tlen = part[0].tlen;
+    S.genome_of_tid = part[0].genome_of_tid; S.streamed = true;
+    const uint32_t nt = (uint32_t)S.tlen.size();
+    check(sess[0], cov_gather(sess.data(), (uint32_t)nd, 0));
+    S.stats.assign(nt, cov_contig_stats{});
+    if (R.dev_est) S.estimates.assign((size_t)nt * est.size(), 0.0f);
+    std::vector<cov_contig_stats> tmp(nt);
+    for (size_t d = 0; d < nd; d++) {
+        cov_summary summ;
+        check(sess[0], cov_gathered(sess[0], (uint32_t)d, tmp.data(), &summ));
+        S.prim += summ.num_detected_primary_alignments; S.n_records += summ.n_records;
+        S.peak_bytes = std::max(S.peak_bytes, part[d].peak_bytes);
+        S.t_ingest = std::max(S.t_ingest, part[d].t_ingest); S.t_finish = std::max(S.t_finish, part[d].t_finish);
+        for (uint32_t t = 0; t < nt; t++) {
+            if (tmp[t].n_pass == 0) continue;
+            if (S.stats[t].n_pass != 0) die("internal error: contig " + S.target_name(t) + " was seen by two spans");
+            S.stats[t] = tmp[t];
+            if (R.dev_est) {                // the floats stay with the rank that evaluated them, like the histogram bins
+                std::copy(part[d].estimates.begin() + (size_t)t * est.size(), part[d].estimates.begin() + (size_t)(t + 1) * est.size(), S.estimates.begin() + (size_t)t * est.size());
+            } else if (R.want & COV_WANT_HIST) {   // histogram bins stay with the rank that built them: re-based into one array
+                S.stats[t].hist_off = S.hist.size();
+                S.hist.insert(S.hist.end(), part[d].hist.begin() + tmp[t].hist_off, part[d].hist.begin() + tmp[t].hist_off + tmp[t].hist_len);
+            }
+        }
+    }
 }
 
 // `coverm filter` (bin/coverm.rs:408-472): every input BAM through ReferenceSortedBamFilter into its output BAM.  Host code in the
@@ -611,9 +757,8 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
 // are FilterParameters::generate_from_clap's (coverm.rs:1659-1678); filter_out = !--inverse.
 int run_filter(int argc, char **argv) {
     std::vector<std::string> in, out;
-    Filter f;
-    bool inverse = false, proper_pairs_only = false, exclude_supplementary = false, include_secondary = false;
-    const char *pid = nullptr, *pct = nullptr, *pid_pair = nullptr, *pct_pair = nullptr;
+    FilterArgs fa;
+    bool inverse = false;
     int threads = 1;
     auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && argv[i + 1][0] != '-') dst.push_back(argv[++i]); };
     for (int i = 2; i < argc; i++) {
@@ -622,16 +767,7 @@ int run_filter(int argc, char **argv) {
         if (k == "-b" || k == "--bam-files") collect(i, in);
         else if (k == "-o" || k == "--output-bam-files") collect(i, out);
         else if (k == "--inverse") inverse = true;
-        else if (k == "--proper-pairs-only") proper_pairs_only = true;
-        else if (k == "--exclude-supplementary") exclude_supplementary = true;
-        else if (k == "--include-secondary") include_secondary = true;
-        else if (k == "--min-read-aligned-length") f.len_single = (uint32_t)parse_uint(k, val(), 0xffffffffull);
-        else if (k == "--min-read-percent-identity") pid = val();
-        else if (k == "--min-read-aligned-percent") pct = val();
-        else if (k == "--min-read-aligned-length-pair") f.len_pair = (uint32_t)parse_uint(k, val(), 0xffffffffull);
-        else if (k == "--min-read-percent-identity-pair") pid_pair = val();
-        else if (k == "--min-read-aligned-percent-pair") pct_pair = val();
-        else if (k == "--min-mapq") f.mapq = (int)parse_uint(k, val(), 255);
+        else if (parse_filter_flag(k, val, fa)) {}
         else if (k == "-t" || k == "--threads") threads = (int)parse_uint(k, val(), 65535);
         else if (k == "-v" || k == "--verbose" || k == "-q" || k == "--quiet") {}
         else if (k == "--unsorted") die("filter does not take --unsorted: it streams its input in bounded memory and copies records byte for byte, in the input's order (sort the file by reference first)");
@@ -639,15 +775,10 @@ int run_filter(int argc, char **argv) {
     }
     if (in.empty()) die("--bam-files is required");
     if (in.size() != out.size()) die("The number of input BAM files must be the same as the number output");     // coverm.rs:422-425
-    f.improper = !proper_pairs_only; f.supp = !exclude_supplementary; f.sec = include_secondary;
-    f.pid_single = parse_percentage(pid, "--min-read-percent-identity"); f.pct_single = parse_percentage(pct, "--min-read-aligned-percent");
-    f.pid_pair = parse_percentage(pid_pair, "--min-read-percent-identity-pair"); f.pct_pair = parse_percentage(pct_pair, "--min-read-aligned-percent-pair");
+    const Filter f = resolve_filter(fa);
     bool fs = false, fp = false;
     f.mode(fs, fp);
-    covh_pair_filter pf; memset(&pf, 0, sizeof pf);
-    pf.filter_single = fs; pf.min_mapq = (uint8_t)f.mapq; pf.min_aligned_length_single = f.len_single; pf.min_percent_identity_single = f.pid_single;
-    pf.min_aligned_percent_single = f.pct_single; pf.min_aligned_length_pair = f.len_pair; pf.min_percent_identity_pair = f.pid_pair;
-    pf.min_aligned_percent_pair = f.pct_pair;
+    const covh_pair_filter pf = pair_thresholds<covh_pair_filter>(f, fs);
     for (size_t k = 0; k < in.size(); k++) {
         char err[512] = {0};
         uint64_t n_in = 0, n_out = 0;
@@ -696,16 +827,7 @@ int run_cli(int argc, char **argv) {
         else if (k == "--output-format") a.output_format = val();
         else if (k == "-o" || k == "--output-file") a.output_file = val();
         else if (k == "--no-zeros") a.no_zeros = true;
-        else if (k == "--proper-pairs-only") a.proper_pairs_only = true;
-        else if (k == "--exclude-supplementary") a.exclude_supplementary = true;
-        else if (k == "--include-secondary") a.include_secondary = true;
-        else if (k == "--min-read-aligned-length") a.min_aligned_length = (uint32_t)parse_uint(k, val(), 0xffffffffull);
-        else if (k == "--min-read-percent-identity") a.min_pid = val();
-        else if (k == "--min-read-aligned-percent") a.min_aligned_pct = val();
-        else if (k == "--min-read-aligned-length-pair") a.min_aligned_length_pair = (uint32_t)parse_uint(k, val(), 0xffffffffull);
-        else if (k == "--min-read-percent-identity-pair") a.min_pid_pair = val();
-        else if (k == "--min-read-aligned-percent-pair") a.min_aligned_pct_pair = val();
-        else if (k == "--min-mapq") a.min_mapq = (int)parse_uint(k, val(), 255);
+        else if (parse_filter_flag(k, val, a.filter)) {}
         else if (k == "-s" || k == "--separator") { a.separator = val()[0]; a.have_separator = true; }
         else if (k == "--single-genome") a.single_genome = true;
         else if (k == "--genome-definition") a.genome_definition = val();
@@ -792,10 +914,7 @@ int run_cli(int argc, char **argv) {
         e.exclude_mismatches = 0; e.trim_min = t0; e.trim_max = t1; est.push_back(e);
     };
     Filter &f = R.f;
-    f.improper = !a.proper_pairs_only; f.supp = !a.exclude_supplementary; f.sec = a.include_secondary;
-    f.len_single = a.min_aligned_length; f.pid_single = parse_percentage(a.min_pid, "--min-read-percent-identity"); f.pct_single = parse_percentage(a.min_aligned_pct, "--min-read-aligned-percent");
-    f.mapq = a.min_mapq; f.len_pair = a.min_aligned_length_pair; f.pid_pair = parse_percentage(a.min_pid_pair, "--min-read-percent-identity-pair");
-    f.pct_pair = parse_percentage(a.min_aligned_pct_pair, "--min-read-aligned-percent-pair");
+    f = resolve_filter(a.filter);
     const bool metabat = a.methods.size() == 1 && a.methods[0] == "metabat";
     for (auto &m : a.methods) if (m == "metabat" && a.methods.size() > 1) die("Cannot specify the metabat method with any other coverage methods");
     if (metabat) {
@@ -860,37 +979,7 @@ int run_cli(int argc, char **argv) {
     std::vector<std::string> &genomes = R.genomes;
     R.by_names = !contig && !a.have_separator && !a.single_genome;
     const bool fasta_genomes = R.by_names && a.genome_definition.empty() && (a.have_fasta_files || a.have_fasta_directory || a.have_fasta_list);
-    if (R.by_names && !fasta_genomes) {
-        if (a.genome_definition.empty()) die("genome mode over BAM files needs --separator, --single-genome or --genome-definition");
-        FILE *fh = fopen(a.genome_definition.c_str(), "r");
-        if (!fh) die("cannot open " + a.genome_definition);
-        struct FClose { FILE *f; ~FClose() { fclose(f); } } fclose_{fh};
-        std::vector<char> linebuf(1 << 16);
-        char *line = linebuf.data();
-        std::unordered_map<std::string, int32_t> gi;
-        auto is_ws = [](unsigned char ch) { return ch == ' ' || (ch >= 9 && ch <= 13); };
-        while (fgets(line, (int)linebuf.size(), fh)) {   // read_genome_definition_file, genome_parsing.rs:71-141
-            std::string l(line);
-            if (!l.empty() && l.back() == '\n') l.pop_back();
-            if (!l.empty() && l.back() == '\r') l.pop_back();
-            const size_t t = l.find('\t');
-            if (t == std::string::npos || l.find('\t', t + 1) != std::string::npos)   // blank lines included (:116-124)
-                die("The line \"" + l + "\" in the genome definition file is not a genome name and contig name separated by a tab");
-            std::string g = l.substr(0, t);
-            { size_t x = 0, y = g.size(); while (x < y && is_ws((unsigned char)g[x])) x++; while (y > x && is_ws((unsigned char)g[y - 1])) y--; g = g.substr(x, y - x); }
-            size_t x = t + 1;
-            while (x < l.size() && is_ws((unsigned char)l[x])) x++;
-            size_t y = x;
-            while (y < l.size() && !is_ws((unsigned char)l[y])) y++;
-            if (x == y) die("Failed to split contig name by whitespace in genome definition file");
-            const std::string c = l.substr(x, y - x);                                  // first token: comments after it are dropped
-            auto it = gi.find(g);
-            if (it == gi.end()) { it = gi.emplace(g, (int32_t)genomes.size()).first; genomes.push_back(g); }
-            auto cit = R.c2g.find(c);
-            if (cit != R.c2g.end() && cit->second != it->second) die("The contig name '" + c + "' was assigned to multiple genomes");
-            if (cit == R.c2g.end()) R.c2g[c] = it->second;
-        }
-    }
+    if (R.by_names && !fasta_genomes) read_genome_definition(R);
 
     // ---- sessions: one per device, brought up in parallel
     R.want = covh_wants(est.data(), est.size());
@@ -1033,65 +1122,11 @@ int run_cli(int argc, char **argv) {
                 ingest(R, sess[0], samples[bi], a.threads, 0, 1);
                 continue;
             }
-            Sample &S = samples[bi];
-            S.stoit = part[0].stoit; S.names_blob = part[0].names_blob; S.name_off = part[0].name_off; S.tlen = part[0].tlen;
-            S.genome_of_tid = part[0].genome_of_tid; S.streamed = true;
-            const uint32_t nt = (uint32_t)S.tlen.size();
-            check(sess[0], cov_gather(sess.data(), (uint32_t)nd, 0));
-            S.stats.assign(nt, cov_contig_stats{});
-            if (R.dev_est) S.estimates.assign((size_t)nt * est.size(), 0.0f);
-            std::vector<cov_contig_stats> tmp(nt);
-            for (size_t d = 0; d < nd; d++) {
-                cov_summary summ;
-                check(sess[0], cov_gathered(sess[0], (uint32_t)d, tmp.data(), &summ));
-                S.prim += summ.num_detected_primary_alignments; S.n_records += summ.n_records;
-                S.peak_bytes = std::max(S.peak_bytes, part[d].peak_bytes);
-                S.t_ingest = std::max(S.t_ingest, part[d].t_ingest); S.t_finish = std::max(S.t_finish, part[d].t_finish);
-                for (uint32_t t = 0; t < nt; t++) {
-                    if (tmp[t].n_pass == 0) continue;
-                    if (S.stats[t].n_pass != 0) die("internal error: contig " + S.target_name(t) + " was seen by two spans");
-                    S.stats[t] = tmp[t];
-                    if (R.dev_est) {                // the floats stay with the rank that evaluated them, like the histogram bins
-                        std::copy(part[d].estimates.begin() + (size_t)t * est.size(), part[d].estimates.begin() + (size_t)(t + 1) * est.size(), S.estimates.begin() + (size_t)t * est.size());
-                    } else if (R.want & COV_WANT_HIST) {   // histogram bins stay with the rank that built them: re-based into one array
-                        S.stats[t].hist_off = S.hist.size();
-                        S.hist.insert(S.hist.end(), part[d].hist.begin() + tmp[t].hist_off, part[d].hist.begin() + tmp[t].hist_off + tmp[t].hist_len);
-                    }
-                }
-            }
+            merge_spans(R, sess, part, samples[bi]);
         }
     }
     const double t_ingested = now();
-    if (timing) {
-        // where the resident set comes from (VmHWM = peak; RssShmem counts page-locked / device-visible mappings of the HIP runtime)
-        if (FILE *ps = fopen("/proc/self/status", "r")) {
-            char ln[256];
-            while (fgets(ln, sizeof ln, ps))
-                if (!strncmp(ln, "VmHWM", 5) || !strncmp(ln, "VmRSS", 5) || !strncmp(ln, "RssAnon", 7) || !strncmp(ln, "RssFile", 7) || !strncmp(ln, "RssShmem", 8)) {
-                    ln[strcspn(ln, "\n")] = 0;
-                    fprintf(stderr, "[coverm-amd] %s\n", ln);
-                }
-            fclose(ps);
-        }
-        // ... and its eight largest mappings (what the kernel has to take apart when the process ends)
-        if (FILE *sm = fopen("/proc/self/smaps", "r")) {
-            struct M { unsigned long long rss_kb, size_kb; std::string what; };
-            std::vector<M> ms;
-            char ln[512]; std::string cur; unsigned long long size_kb = 0;
-            while (fgets(ln, sizeof ln, sm)) {
-                unsigned long long a, b2, v;
-                if (sscanf(ln, "%llx-%llx ", &a, &b2) == 2 && strchr(ln, '-') && strchr(ln, '-') < ln + 17) {
-                    ln[strcspn(ln, "\n")] = 0;
-                    const char *path = strchr(ln, '/'); const char *br = strchr(ln, '[');
-                    cur = path ? path : br ? br : "(anonymous)"; size_kb = (b2 - a) >> 10;
-                } else if (sscanf(ln, "Rss: %llu kB", &v) == 1) ms.push_back({v, size_kb, cur});
-            }
-            fclose(sm);
-            std::sort(ms.begin(), ms.end(), [](const M &x, const M &y) { return x.rss_kb > y.rss_kb; });
-            for (size_t i = 0; i < ms.size() && i < 8; i++)
-                fprintf(stderr, "[coverm-amd] mapping %zu: %llu MB resident of %llu MB, %s\n", i, ms[i].rss_kb >> 10, ms[i].size_kb >> 10, ms[i].what.c_str());
-        }
-    }
+    if (timing) report_resident_set();
     if (timing)
         for (auto &S : samples)
             fprintf(stderr, "[coverm-amd] sample %s: %s, open %.3fs, ingest (decode+push) %.3fs, finish+fetch %.3fs, %llu records, reader buffers %.0f MB\n", S.stoit.c_str(),
