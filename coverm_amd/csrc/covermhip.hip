@@ -5,6 +5,7 @@
 #include "pileup_kernels.hip.h"
 #include "prep_lean.hip.h"
 #include "genome_kernels.hip.h"
+#include "sep_kernels.hip.h"
 #include "ingest_kernels.hip.h"
 #include "group_kernels.hip.h"
 #include "sam_kernels.hip.h"
@@ -44,6 +45,8 @@ static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
 static_assert(sizeof(cov_genome_stats) == 24 && sizeof(cov_genome_stats) == sizeof(covk::DevGenomeStats) && offsetof(cov_genome_stats, genome_len) == offsetof(covk::DevGenomeStats, genome_len) &&
               offsetof(cov_genome_stats, any_nonzero) == offsetof(covk::DevGenomeStats, any_nonzero), "cov_genome_stats mirrors the device struct");
+static_assert(sizeof(cov_genome_entry) == 24 && offsetof(cov_genome_entry, first_tid) == 8 && offsetof(cov_genome_entry, gid) == 12 && offsetof(cov_genome_entry, n_contigs_seen) == 16 &&
+              offsetof(cov_genome_entry, any_nonzero) == 20 && sizeof(covk::SepEntry) == 8, "cov_genome_entry layout (numpy mirror in coverm_amd/native.py)");
 static_assert(sizeof(cov_estimator) == sizeof(covk::DevEstimator) && offsetof(cov_estimator, contig_end_exclusion) == offsetof(covk::DevEstimator, excl) &&
               offsetof(cov_estimator, trim_max) == offsetof(covk::DevEstimator, trim_max) && COV_EST_MAX == covk::EST_MAX && COV_EST_ANIR == covk::EST_ANIR, "cov_estimator mirrors the device struct");
 
@@ -140,6 +143,13 @@ struct cov_session {
     DevBuf<DevGenome> d_genomes;
     DevBuf<u64> d_ghist, d_ghist_top;
     DevBuf<uint8_t> d_gout; uint8_t *h_gout = nullptr; size_t h_gout_cap = 0;
+    // cov_set_genome_runs: gid[] / blk[] of the header; the table entry -> targets is built per finish (sep_kernels.hip.h) into the arrays of
+    // cov_set_genomes above, which the two modes never hold at once.  The fetched block: [cov_genome_stats x n][floats x n x est.n][SepEntry x n],
+    // the counts of the finish in the last 16 bytes of h_gout.  n_genomes = the entries of the last finish.
+    bool have_runs = false;
+    uint32_t n_gids = 0, sep_ent_cap = 0, sep_seg_cap = 0;
+    DevBuf<int32_t> d_sgid; DevBuf<u32> d_sblk, d_sent_pos, d_stop_last1, d_stop_first, d_scounts; DevBuf<uint8_t> d_scode;
+    DevBuf<u64> d_stop_cnt, d_stop_seg; DevBuf<SepEntry> d_sent;
     // results of the device pipeline live in ONE block [DevGlobal][DevContig x n_targets] (d_res): one DMA brings them to
     // the host, and cov_gather sends the same block over RCCL.  d_glob / d_ctg are views into it (never freed themselves).
     DevBuf<uint8_t> d_res;
@@ -299,7 +309,7 @@ size_t result_block_bytes(u32 n_targets) { return sizeof(DevGlobal) + (size_t)st
 // it on a helper thread (the ingest or the pushes pass meanwhile); cov_finish takes what the helper got, or allocates as before.
 static size_t result_host_bytes(const cov_session *s, u32 nT) {
     // (with a target mask no per-contig floats come back — the entries are genomes — so the block does not grow with the estimators)
-    return result_block_bytes(nT) + (size_t)std::max<u32>(nT, 1) * (s->have_mask ? 1u : std::max<u32>(s->est.n, 1u)) * sizeof(float);
+    return result_block_bytes(nT) + (size_t)std::max<u32>(nT, 1) * ((s->have_mask || s->have_runs) ? 1u : std::max<u32>(s->est.n, 1u)) * sizeof(float);
 }
 static void result_host_take(cov_session *s) {
     if (!s->h_res_prep.valid()) return;
@@ -604,6 +614,8 @@ void cov_destroy(cov_session *s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     s->d_tlen.release(); s->d_tile_contig.release(); s->d_tile_start.release(); s->d_mask.release();
     s->d_grow.release(); s->d_gtids.release(); s->d_gseg_genome.release(); s->d_gseg_start.release(); s->d_genomes.release(); s->d_ghist.release(); s->d_ghist_top.release(); s->d_order.release();
+    s->d_sgid.release(); s->d_sblk.release(); s->d_sent_pos.release(); s->d_stop_last1.release(); s->d_stop_first.release(); s->d_scounts.release(); s->d_scode.release();
+    s->d_stop_cnt.release(); s->d_stop_seg.release(); s->d_sent.release();
     s->d_gout.release(); if (s->h_gout) (void)hipHostFree(s->h_gout); s->h_gout = nullptr;
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
     s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
@@ -662,7 +674,7 @@ static void genomes_off(cov_session *s) {
     if (s->have_genomes && (s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY))
         for (uint32_t k = 0; k < s->est.n; k++)
             if (s->est.e[k].kind == COV_EST_ANIR) { s->est = EstParams{}; s->est_valid = false; break; }
-    s->have_genomes = false; s->gen_valid = false;
+    s->have_genomes = false; s->have_runs = false; s->gen_valid = false;
 }
 cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *target_len) {
     if (!s || (!target_len && n_targets)) return COV_ERR_INVALID_ARG;
@@ -763,6 +775,7 @@ cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_
     for (u32 t = 0; t < nT; t++) if (genome_of_tid[t] >= 0) tids[cur[genome_of_tid[t]]++] = t;
     for (uint32_t g = 0; g < n_genomes; g++)
         for (u32 i = row[g]; i < row[g + 1]; i += GENOME_SEG) { seg_genome.push_back(g); seg_start.push_back(i); }
+    s->have_runs = false;
     const cov_status m = set_target_mask_(s, mask.data());
     if (m != COV_OK) return m;
     const size_t n_seg = seg_genome.size();
@@ -788,6 +801,50 @@ cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_
     }
     s->n_genomes = n_genomes; s->n_gseg = (uint32_t)n_seg;
     s->have_genomes = true;
+    return COV_OK;
+}
+
+// The header's part of the separator scan: gid[] and blk[] (first tid of each maximal run of equal gid), and every buffer the per-finish
+// table and its results can need — an entry starts in a run of its own, so the runs bound the entries — so that no finish allocates a
+// k_sep_* or per-entry buffer (the merged histogram, sized by the records, still grows with the sample as for cov_set_genomes).
+cov_status cov_set_genome_runs(cov_session *s, const int32_t *gid_of_tid, uint32_t n_gids) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (!gid_of_tid || n_gids == 0) return cov_set_target_mask(s, nullptr);
+    const u32 nT = s->n_targets;
+    std::vector<u32> blk(std::max<u32>(nT, 1u));
+    u32 n_runs = 0;
+    for (u32 t = 0; t < nT; t++) {
+        if (gid_of_tid[t] < 0 || (uint32_t)gid_of_tid[t] >= n_gids) { s->err = "cov_set_genome_runs: genome id outside [0, n_gids)"; return COV_ERR_INVALID_ARG; }
+        if (t != 0 && gid_of_tid[t] == gid_of_tid[t - 1]) blk[t] = blk[t - 1]; else { blk[t] = t; n_runs++; }
+    }
+    genomes_off(s);
+    const cov_status m = set_target_mask_(s, nullptr);
+    if (m != COV_OK) return m;
+    hipStream_t st = s->stream;
+    const size_t nT1 = std::max<size_t>(nT, 1), ent_cap = std::max<u32>(n_runs, 1u), seg_cap = ent_cap + nT / GENOME_SEG + 1, nb = (nT1 + SEP_TILE - 1) / SEP_TILE;
+    HIPCHK(s->d_sgid.reserve(nT1, st)); HIPCHK(s->d_sblk.reserve(nT1, st)); HIPCHK(s->d_scode.reserve(nT1, st)); HIPCHK(s->d_sent_pos.reserve(nT1, st));
+    HIPCHK(s->d_gtids.reserve(nT1, st)); HIPCHK(s->d_grow.reserve(ent_cap + 1, st)); HIPCHK(s->d_sent.reserve(ent_cap, st));
+    HIPCHK(s->d_gseg_genome.reserve(seg_cap, st)); HIPCHK(s->d_gseg_start.reserve(seg_cap, st));
+    HIPCHK(s->d_stop_last1.reserve(nb, st)); HIPCHK(s->d_stop_first.reserve(nb, st)); HIPCHK(s->d_stop_cnt.reserve(nb, st));
+    HIPCHK(s->d_stop_seg.reserve((ent_cap + SEP_TILE - 1) / SEP_TILE, st)); HIPCHK(s->d_scounts.reserve(SEP_N_COUNTS, st));
+    HIPCHK(s->d_genomes.reserve(ent_cap, st)); HIPCHK(s->d_order.reserve((nT1 + 1023) / 1024 + 2, st));
+    HIPCHK(s->d_ghist_top.reserve((ent_cap + 1023u) / 1024u + 1, st));
+    const size_t per = sizeof(cov_genome_stats) + COV_EST_MAX * sizeof(float) + sizeof(SepEntry), need = ent_cap * per + 16;
+    HIPCHK(s->d_gout.reserve(ent_cap * per, st));
+    if (nT) {
+        HIPCHK(hipMemcpyAsync(s->d_sgid.p, gid_of_tid, (size_t)nT * 4, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->d_sblk.p, blk.data(), (size_t)nT * 4, hipMemcpyHostToDevice, st));
+    }
+    HIPCHK(hipStreamSynchronize(st));
+    if (need > s->h_gout_cap) {
+        if (s->h_gout) (void)hipHostFree(s->h_gout);
+        s->h_gout = nullptr; s->h_gout_cap = 0;
+        HIPCHK(hipHostMalloc((void **)&s->h_gout, need, hipHostMallocDefault));
+        s->h_gout_cap = need;
+    }
+    s->finished = false;
+    s->n_gids = n_gids; s->sep_ent_cap = (uint32_t)ent_cap; s->sep_seg_cap = (uint32_t)seg_cap; s->n_genomes = 0;
+    s->have_runs = true;
     return COV_OK;
 }
 
@@ -1251,7 +1308,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     }
     // (with a target mask the entries are genomes — aggregated below when cov_set_genomes gave their table, else by the caller: masked-out
     // contigs have no bins in the arena, and nobody may fetch per-contig floats — no k_estimate launch, no floats in the copy)
-    const size_t block = result_block_bytes(nT), nf = s->have_mask ? 0 : (size_t)nT * s->est.n;
+    const size_t block = result_block_bytes(nT), nf = (s->have_mask || s->have_runs) ? 0 : (size_t)nT * s->est.n;
     {
         result_host_take(s);
         const size_t need = lean ? sizeof(DevGlobal) + sizeof(DevContig) : result_host_bytes(s, nT);      // (lean: DevGlobal + the order word)
@@ -1279,19 +1336,44 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     }
     // genome entries (cov_set_genomes): reduce the contigs' accumulators over each genome's row, merge their histograms, evaluate.  Not
     // after a spill: the contigs that left the store are on the host, the caller aggregates there.
-    const bool genomes = s->have_genomes && s->est.n != 0 && !s->spill.active && !s->in_spill;
-    if (lean && !genomes) { s->err = "cov_finish_genomes: cov_set_genomes and cov_set_estimators first, and no spill of the bounded record store (cov_finish then)"; return COV_ERR_STATE; }
-    if (genomes) {
-        const u32 nG = s->n_genomes, n_seg = s->n_gseg;
+    const bool runs = s->have_runs && s->est.n != 0 && !s->spill.active && !s->in_spill;
+    const bool genomes = runs || (s->have_genomes && s->est.n != 0 && !s->spill.active && !s->in_spill);
+    if (lean && !genomes) { s->err = "cov_finish_genomes: cov_set_genomes or cov_set_genome_runs, and cov_set_estimators, first, and no spill of the bounded record store (cov_finish then)"; return COV_ERR_STATE; }
+    u32 sep_counts[SEP_N_COUNTS] = {0, 0, 0, 0};
+    if (runs) {
+        // separator / single-genome entries: which targets form an entry depends on where the reads fell — the table of this finish
+        // (sep_kernels.hip.h), then its three counts: the launches below are sized by them
+        const u32 nb = (std::max(nT, 1u) + SEP_TILE - 1u) / SEP_TILE, eb = (s->sep_ent_cap + SEP_TILE - 1u) / SEP_TILE, cap = s->sep_ent_cap;
+        time_begin(s, COV_K_SEP);
+        hipLaunchKernelGGL(k_sep_obs_top, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_stop_last1.p, s->d_stop_first.p);
+        hipLaunchKernelGGL(k_sep_flags, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p,
+                           (const u32 *)s->d_stop_last1.p, (const u32 *)s->d_stop_first.p, s->d_scode.p, s->d_stop_cnt.p);
+        hipLaunchKernelGGL(k_sep_compact, dim3(nb), dim3(SEP_TILE), 0, st, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p, (const uint8_t *)s->d_scode.p,
+                           (const u64 *)s->d_stop_cnt.p, s->d_gtids.p, s->d_sent_pos.p, s->d_sent.p, cap, s->d_scounts.p, s->d_glob.p);
+        hipLaunchKernelGGL(k_sep_rows, dim3((std::max(nT, 1u) + 255u) / 256u), dim3(256), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_sent_pos.p, s->d_grow.p, cap);
+        hipLaunchKernelGGL(k_sep_seg_sum, dim3(eb), dim3(SEP_TILE), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_grow.p, s->d_stop_seg.p);
+        hipLaunchKernelGGL(k_sep_seg_write, dim3(eb), dim3(SEP_TILE), 0, st, s->d_scounts.p, (const u32 *)s->d_grow.p, (const u64 *)s->d_stop_seg.p, s->d_gseg_genome.p,
+                           s->d_gseg_start.p, s->sep_seg_cap);
+        time_end(s, COV_K_SEP);
+        HIPCHK(hipGetLastError());
+        uint8_t *hc = s->h_gout + s->h_gout_cap - 16;
+        HIPCHK(hipMemcpyAsync(hc, s->d_scounts.p, SEP_N_COUNTS * sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        memcpy(sep_counts, hc, sizeof sep_counts);
+        s->ev_fresh = -1;      // (the wait is not the next group's time)
+        s->n_genomes = sep_counts[SEP_N_ENTRIES]; s->n_gseg = sep_counts[SEP_N_SEG];
+    }
+    if (genomes && s->n_genomes != 0) {
+        const u32 nG = s->n_genomes, n_seg = s->n_gseg, sep = runs ? 1u : 0u;
         GenomeTable gt{s->d_grow.p, s->d_gtids.p, s->d_gseg_genome.p, s->d_gseg_start.p, nG, n_seg};
         const u64 excl = s->cfg.contig_end_exclusion;
         const u64 ghist_cap = (u64)R + nT + 1;      // the genomes' bins are at most the contigs' (every genome bin is some contig's bin)
         if (want_hist) HIPCHK(s->d_ghist.reserve((size_t)ghist_cap, st));
         time_begin(s, COV_K_GENOME);
         hipLaunchKernelGGL(k_genome_init, dim3((nG + 255u) / 256u), dim3(256), 0, st, s->d_genomes.p, nG);
-        if (n_seg) hipLaunchKernelGGL(k_genome_reduce, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl, gt, s->d_genomes.p);
-        if (want_id && !(s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY))
-            hipLaunchKernelGGL(k_genome_identity, dim3(nG), dim3(64), 0, st, (const DevContig *)s->d_ctg.p, gt, s->d_genomes.p);
+        if (n_seg) hipLaunchKernelGGL(k_genome_reduce, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl, gt, s->d_genomes.p, sep);
+        if (want_id && !(s->cfg.want & (runs ? COV_WANT_IDENTITY_NONSUPP_ONLY : COV_WANT_IDENTITY_PRIMARY_ONLY)))
+            hipLaunchKernelGGL(k_genome_identity, dim3(nG), dim3(64), 0, st, (const DevContig *)s->d_ctg.p, gt, s->d_genomes.p, sep);
         if (want_hist) {
             const u32 gb = (nG + 1023u) / 1024u;
             u64 *total = s->d_ghist_top.p + gb;
@@ -1311,7 +1393,8 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
         time_end(s, COV_K_GENOME);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(s->h_gout, s->d_gout.p, (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float)), hipMemcpyDeviceToHost, st));
-    }
+        if (runs) HIPCHK(hipMemcpyAsync(s->h_gout + (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float)), s->d_sent.p, (size_t)nG * sizeof(SepEntry), hipMemcpyDeviceToHost, st));
+    }      // (runs and no target with a considered record: no entry, nothing to reduce)
     if (lean) {
         // the order rule of convert_results on the device: the first considered record of a seen contig must not lie before the last one of
         // any seen contig in front of it (contig.rs:129-132); the verdict is one word behind DevGlobal
@@ -1368,7 +1451,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     s->last_chist_total = 0;
     if (want_hist) for (u32 c = 0; c < nT; c++) s->last_chist_total += stats[c].hist_len;      // (the host laid the compact histogram out: convert_results)
     s->hist_compacted = compacted;
-    s->est_valid = s->est.n != 0 && !s->have_mask;
+    s->est_valid = s->est.n != 0 && !s->have_mask && !s->have_runs;
     s->gen_valid = genomes;
     s->finished = true;
     return COV_OK;
@@ -1423,7 +1506,7 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
         if ((int64_t)c == cstar || !st[c].n_pass) continue;
         if (S.have[c]) { s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)"; return COV_ERR_UNSORTED; }
         S.stats[c] = st[c]; S.ctg[c] = s->h_ctg[c]; S.have[c] = 1;
-        if (s->est.n && !s->have_mask) {
+        if (s->est.n && !s->have_mask && !s->have_runs) {
             if (s->spill_est.size() != (size_t)nT * s->est.n) s->spill_est.assign((size_t)nT * s->est.n, 0.0f);
             memcpy(&s->spill_est[(size_t)c * s->est.n], s->h_estf + (size_t)c * s->est.n, s->est.n * sizeof(float));
         }
@@ -2839,7 +2922,7 @@ cov_status cov_set_estimators(cov_session *s, const cov_estimator *est, uint32_t
 static cov_status genome_fetch_ready(cov_session *s, const char *what) {
     if (!s) return COV_ERR_INVALID_ARG;
     if (s->spill.active) { s->err = std::string(what) + ": part of the sample's contigs left the bounded record store: aggregate cov_finish's per-contig results on the host"; return COV_ERR_STATE; }
-    if (!s->finished || !s->gen_valid) { s->err = std::string(what) + ": cov_set_genomes and cov_set_estimators, then cov_finish"; return COV_ERR_STATE; }
+    if (!s->finished || !s->gen_valid) { s->err = std::string(what) + ": cov_set_genomes or cov_set_genome_runs, and cov_set_estimators, then cov_finish"; return COV_ERR_STATE; }
     return COV_OK;
 }
 cov_status cov_fetch_genome_estimates(cov_session *s, float *out) {
@@ -2858,9 +2941,32 @@ cov_status cov_fetch_genome_stats(cov_session *s, cov_genome_stats *out) {
     return COV_OK;
 }
 
+cov_status cov_genome_entry_count(cov_session *s, uint32_t *n_entries) {
+    const cov_status r = genome_fetch_ready(s, "cov_genome_entry_count");
+    if (r != COV_OK) return r;
+    if (!s->have_runs) { s->err = "cov_genome_entry_count: cov_set_genome_runs first"; return COV_ERR_STATE; }
+    if (!n_entries) return COV_ERR_INVALID_ARG;
+    *n_entries = s->n_genomes;
+    return COV_OK;
+}
+cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out) {
+    const cov_status r = genome_fetch_ready(s, "cov_fetch_genome_entries");
+    if (r != COV_OK) return r;
+    if (!s->have_runs) { s->err = "cov_fetch_genome_entries: cov_set_genome_runs first"; return COV_ERR_STATE; }
+    const size_t n = s->n_genomes;
+    if (n && !out) return COV_ERR_INVALID_ARG;
+    const cov_genome_stats *gs = reinterpret_cast<const cov_genome_stats *>(s->h_gout);
+    const SepEntry *se = reinterpret_cast<const SepEntry *>(s->h_gout + n * (sizeof(cov_genome_stats) + s->est.n * sizeof(float)));
+    for (size_t e = 0; e < n; e++) {
+        out[e].reads = gs[e].reads_in_genome; out[e].first_tid = se[e].first_tid; out[e].gid = se[e].gid;
+        out[e].n_contigs_seen = gs[e].n_contigs_seen; out[e].any_nonzero = gs[e].any_nonzero;
+    }
+    return COV_OK;
+}
+
 cov_status cov_fetch_estimates(cov_session *s, float *out) {
     if (!s || !s->finished || !s->est_valid) { if (s) s->err = "cov_fetch_estimates: cov_set_estimators, then cov_finish"; return COV_ERR_STATE; }
-    if (s->have_mask) { s->err = "cov_fetch_estimates: with a target mask the entries are genomes: aggregate on the host"; return COV_ERR_STATE; }
+    if (s->have_mask || s->have_runs) { s->err = "cov_fetch_estimates: with a target mask or genome runs the entries are genomes: aggregate on the host"; return COV_ERR_STATE; }
     const size_t nf = (size_t)s->n_targets * s->est.n;
     if (nf && !out) return COV_ERR_INVALID_ARG;
     if (nf) memcpy(out, s->h_estf, nf * sizeof(float));

@@ -17,7 +17,7 @@ constexpr u32 GENOME_SEG = 256;
 
 // Per-genome accumulators (128 B): what EntryAcc holds after the add_contig of every seen contig, plus the unobserved lengths.
 struct DevGenome {
-    u64 reads;                       // sum of n_pass (genome.rs:173-174): the entry's num_mapped_reads
+    u64 reads;                       // sum of n_pass (genome.rs:173-174; n_nonsupp for separator entries): the entry's num_mapped_reads
     u64 sum_nm, sum_indel;
     u64 sum_d, sum_d2, cov_win, cov_full;
     u64 win_len, full_len, proc_win; // over the contigs with a considered record
@@ -49,8 +49,10 @@ __global__ __launch_bounds__(256) void k_genome_init(DevGenome *__restrict__ G, 
 }
 
 // One wave per segment: the integer part of EntryAcc::add_contig over the segment's contigs, then one set of atomics per segment.
+// `sep`: entries of the separator / single-genome scan (sep_kernels.hip.h) count a contig's reads as genome.rs:677-682 does (considered and
+// not supplementary), the contig-names scan every considered record (genome.rs:173-174).
 __global__ __launch_bounds__(256) void k_genome_reduce(const DevContig *__restrict__ ctg, const u32 *__restrict__ tlen, u64 excl, GenomeTable T,
-                                                       DevGenome *__restrict__ G) {
+                                                       DevGenome *__restrict__ G, u32 sep) {
     const u32 sg = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (sg >= T.n_seg) return;
     const u32 g = T.seg_genome[sg], lo = T.seg_start[sg], hi = min(lo + GENOME_SEG, T.row[g + 1]);
@@ -65,7 +67,7 @@ __global__ __launch_bounds__(256) void k_genome_reduce(const DevContig *__restri
             continue;
         }
         n_seen++;
-        reads += C->n_pass; sum_nm += C->sum_nm; sum_indel += C->sum_indel;
+        reads += sep ? C->n_nonsupp : C->n_pass; sum_nm += C->sum_nm; sum_indel += C->sum_indel;
         full_len += L; cov_full += C->cov_full;
         if (2 * excl < L) {                                    // estimators.rs:386-392, 436-445
             const u64 wl = L - 2 * excl;
@@ -93,17 +95,18 @@ __global__ __launch_bounds__(256) void k_genome_reduce(const DevContig *__restri
 // sum_identity_nonsupp of a genome: a strict chain of rounded f64 additions in ascending tid order (EntryAcc::add_contig, genome.rs:220-223).
 // One wave per genome, as k_identity: 64 values per load (the next 64 are fetched while the chain of this batch runs), every lane replays
 // the same 64 dependent adds from lane broadcasts.  A contig without a considered record holds +0.0, which leaves the sum's bits alone.
-__global__ __launch_bounds__(64) void k_genome_identity(const DevContig *__restrict__ ctg, GenomeTable T, DevGenome *__restrict__ G) {
+// `sep`: the separator scan adds the primary-read sum (genome.rs:724-727).
+__global__ __launch_bounds__(64) void k_genome_identity(const DevContig *__restrict__ ctg, GenomeTable T, DevGenome *__restrict__ G, u32 sep) {
     const u32 g = blockIdx.x;
     if (g >= T.n_genomes) return;
     const u32 lo = T.row[g], hi = T.row[g + 1];
     double acc = 0.0;
     u32 i = lo + (u32)lane_id();
-    double x = i < hi ? ctg[T.tids[i]].id_nonsupp : 0.0;
+    double x = i < hi ? (sep ? ctg[T.tids[i]].id_primary : ctg[T.tids[i]].id_nonsupp) : 0.0;
     for (u32 b = lo; b < hi; b += 64u) {
         const double cur = x;
         i += 64u;
-        x = i < hi ? ctg[T.tids[i]].id_nonsupp : 0.0;
+        x = i < hi ? (sep ? ctg[T.tids[i]].id_primary : ctg[T.tids[i]].id_nonsupp) : 0.0;
 #pragma unroll 16
         for (int k = 0; k < 64; k++) acc += __shfl(cur, k);
     }

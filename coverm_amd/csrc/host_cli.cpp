@@ -149,6 +149,9 @@ struct Sample {
     std::vector<float> estimates;      // calculate_coverage of every contig, evaluated on the device (Run::dev_est): n_targets x estimators
     // Run::dev_genome: the genomes aggregated and evaluated on the device — n_genomes x estimators floats and one cov_genome_stats per genome
     std::vector<float> genome_estimates; std::vector<cov_genome_stats> genome_stats; bool genome_dev = false, any_seen = false;
+    // Run::dev_sep: the entries of the separator / single-genome scan from the device (their floats in genome_estimates); sep_set: this
+    // sample's header went to the device (every name holds the separator), sep_dev: its results came back (no spill, some contig observed)
+    std::vector<cov_genome_entry> sep_entries; bool sep_set = false, sep_dev = false;
     uint64_t prim = 0, n_records = 0;
     covh_reads_mapped gene_rm{0, 0};
     double t_open = 0, t_ingest = 0, t_finish = 0; uint64_t peak_bytes = 0; bool streamed = false, device_ingest = false;
@@ -178,6 +181,10 @@ struct Run {
     bool dev_est = false;      // `coverm contig` with estimators the device evaluates (cov_set_estimators): no per-contig finalisation, no histogram fetch on the host
     // contig-names genome scan with estimators the device evaluates (cov_set_genomes): no host pass over the contigs, no histogram fetch
     bool dev_genome = false;
+    // separator / single-genome scan with estimators the device evaluates (cov_set_genome_runs): the same, per entry of the scan.  The
+    // genome ids of a header are built once and kept for the samples that share it.
+    bool dev_sep = false;
+    std::mutex sep_mutex; std::string sep_names; std::vector<uint32_t> sep_name_off; std::vector<int32_t> sep_gid; uint32_t sep_n_gids = 0; bool sep_cached = false;
     uint32_t want = 0;
     cov_config cfg{};
     std::vector<std::string> genomes;
@@ -229,6 +236,31 @@ void set_genomes_or_mask(Run &R, cov_session *s, const Sample &S, const std::vec
     check(s, cov_set_genomes(s, S.genome_of_tid.data(), (uint32_t)R.genomes.size()));
     check(s, cov_set_estimators(s, reinterpret_cast<const cov_estimator *>(R.est.data()), (uint32_t)R.est.size()));
     if (timing_on()) fprintf(stderr, "[coverm-amd] %s: genome table to the device (cov_set_genomes) %.4fs\n", S.stoit.c_str(), now() - t0);
+}
+
+// The separator / single-genome scan on the device (Run::dev_sep): the genome ids of the sample's header, when every name holds the
+// separator (a header with a name that does not stays with the host scan, which raises its error only for the names it touches).
+void set_genome_runs(Run &R, cov_session *s, Sample &S) {
+    const double t0 = now();
+    S.sep_set = false;
+    uint32_t n_gids;
+    {
+        // (the ids are handed over under the lock — the call only reads them —, so a sample takes no copy of a table of millions; the
+        // offsets are compared first: two headers of equal offsets and different names are rare, two of different offsets are told at once)
+        std::lock_guard<std::mutex> lk(R.sep_mutex);
+        if (!R.sep_cached || R.sep_name_off != S.name_off || R.sep_names != S.names_blob) {
+            const covh_header h = S.header();
+            R.sep_gid.assign(S.tlen.size(), 0);
+            R.sep_n_gids = covh_genome_separator_ids(&h, (uint8_t)R.a.separator, R.a.single_genome ? 1 : 0, R.sep_gid.data());
+            R.sep_names = S.names_blob; R.sep_name_off = S.name_off; R.sep_cached = true;
+        }
+        n_gids = R.sep_n_gids;
+        if (n_gids == 0 || S.tlen.empty()) return;
+        check(s, cov_set_genome_runs(s, R.sep_gid.data(), n_gids));
+    }
+    check(s, cov_set_estimators(s, reinterpret_cast<const cov_estimator *>(R.est.data()), (uint32_t)R.est.size()));
+    S.sep_set = true;
+    if (timing_on()) fprintf(stderr, "[coverm-amd] %s: genome ids to the device (cov_set_genome_runs) %u ids, %.4fs\n", S.stoit.c_str(), n_gids, now() - t0);
 }
 
 // Genomes from FASTA files (-f / -d -x / --genome-fasta-list; genome_parsing.rs:10-70) into R.genomes / R.c2g, the table
@@ -295,7 +327,22 @@ void fetch_results(Run &R, cov_session *s, Sample &S, const cov_summary &summ) {
                     S.genome_estimates.size() * sizeof(float) + S.genome_stats.size() * sizeof(cov_genome_stats));
         return;
     }
-    // (Run::dev_genome after a spill of the bounded record store: finished contigs are on the host, and so is the aggregation)
+    if (S.sep_set && cov_store_spills(s) == 0) {
+        uint32_t ne = 0;
+        check(s, cov_genome_entry_count(s, &ne));
+        if (ne == 0) { S.stats.assign(S.tlen.size(), cov_contig_stats{}); S.hist.clear(); }      // no contig observed: nothing to aggregate, the host scan prints its zero rows
+        else {
+            S.sep_entries.resize(ne); S.genome_estimates.resize((size_t)ne * R.est.size());
+            check(s, cov_fetch_genome_entries(s, S.sep_entries.data()));
+            check(s, cov_fetch_genome_estimates(s, S.genome_estimates.data()));
+            S.sep_dev = true;
+        }
+        if (timing_on())
+            fprintf(stderr, "[coverm-amd] %s: separator entries from the device (cov_set_genome_runs): %u entries x %zu estimators, %zu bytes\n", S.stoit.c_str(), ne, R.est.size(),
+                    S.genome_estimates.size() * sizeof(float) + S.sep_entries.size() * sizeof(cov_genome_entry));
+        return;
+    }
+    // (Run::dev_genome / dev_sep after a spill of the bounded record store: finished contigs are on the host, and so is the aggregation)
     if (R.want & COV_WANT_HIST) {
         S.hist.resize(summ.hist_total); check(s, cov_fetch_hist(s, S.hist.data()));
         if (timing_on()) fprintf(stderr, "[coverm-amd] %s: histogram fetch: %llu bins, %llu bytes\n", S.stoit.c_str(), (unsigned long long)summ.hist_total, (unsigned long long)summ.hist_total * 8ull);
@@ -305,7 +352,7 @@ void fetch_results(Run &R, cov_session *s, Sample &S, const cov_summary &summ) {
 // cov_finish of one sample.  Run::dev_genome: the genome results are all the host takes, so the per-contig block stays on the device
 // (cov_finish_genomes) — unless the bounded record store spilled: finished contigs are on the host then, and so is the aggregation.
 void finish_sample(Run &R, cov_session *s, Sample &S, cov_summary &summ) {
-    if (R.dev_genome && cov_store_spills(s) == 0) { check(s, cov_finish_genomes(s, &summ)); return; }
+    if ((R.dev_genome || S.sep_set) && cov_store_spills(s) == 0) { check(s, cov_finish_genomes(s, &summ)); return; }
     S.stats.resize(S.tlen.size());
     check(s, cov_finish(s, S.stats.data(), &summ));
 }
@@ -419,6 +466,7 @@ BamWhole open_bam_whole(Run &R, Sample &S, int threads) {
 void prepare_session(Run &R, cov_session *s, Sample &S, double t0, bool device_reader, std::vector<uint8_t> mask = {}) {
     check(s, cov_set_targets(s, (uint32_t)S.tlen.size(), S.tlen.data()));
     if (R.by_names) { if (mask.empty()) genome_table(R, S, mask); set_genomes_or_mask(R, s, S, mask); }
+    if (R.dev_sep) set_genome_runs(R, s, S);
     S.t_open = now() - t0;
     if (!device_reader) return;
     check(s, cov_ingest_want_mates(s, R.fp ? 1 : 0));
@@ -439,7 +487,7 @@ Fed feed_device_bgzf(Run &R, cov_session *s, Sample &S, const covh_bam_header *h
     // (an assembly's statistics are 128 B x millions of contigs: the array is obtained and touched beside the ingest, not behind it;
     // a std::async future joins in its destructor, so every way out of this function waits for the thread)
     std::future<void> stats_ahead;
-    if (S.tlen.size() >= 65536 && !R.dev_genome && !R.per_gene) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
+    if (S.tlen.size() >= 65536 && !R.dev_genome && !S.sep_set && !R.per_gene) stats_ahead = std::async(std::launch::async, [&S] { S.stats.resize(S.tlen.size()); });
     const int rc = covh_bam_gpu_ingest_span(S.path.c_str(), threads, s, hd, 1, span_index, span_count, &fed.nrec, fed.tm, err, sizeof err);
     if (stats_ahead.valid()) stats_ahead.get();
     if (rc == -2 && span_count > 1) throw SpanUnsorted(err);
@@ -1057,6 +1105,10 @@ int run_cli(int argc, char **argv) {
         bool ok = R.by_names && !R.per_gene && !(nd > 1 && nb < nd) && !getenv("COVERM_HOST_ESTIMATES") && !est.empty() && est.size() <= COV_EST_MAX;
         for (const covh_estimator &e : est) ok = ok && e.kind != COVH_TPM && e.kind != COVH_PILEUP_COUNTS;
         R.dev_genome = ok;
+        // ... and for the separator / single-genome scan (one entry per run of observed contigs of a genome, cov_set_genome_runs)
+        bool sep = !contig && (a.have_separator || a.single_genome) && !R.per_gene && !(nd > 1 && nb < nd) && !getenv("COVERM_HOST_ESTIMATES") && !est.empty() && est.size() <= COV_EST_MAX;
+        for (const covh_estimator &e : est) sep = sep && e.kind != COVH_TPM && e.kind != COVH_PILEUP_COUNTS;
+        R.dev_sep = sep;
     }
     const double t_sessions = now();
     covh_bam_set_pinned(1);
@@ -1143,6 +1195,9 @@ int run_cli(int argc, char **argv) {
         int rc;
         const float *ef = S.estimates.empty() ? nullptr : S.estimates.data();
         if (contig) rc = covh_contig_coverage_estimated(&hdr, &hs, 1, taker, est.data(), est.size(), !a.no_zeros, &rm[bi], R.dev_est ? &ef : nullptr);
+        else if (S.sep_dev)
+            rc = covh_genome_coverage_separator_estimated(&hdr, S.stoit.c_str(), S.prim, (uint8_t)(a.single_genome ? '0' : a.separator), a.single_genome, taker, !a.no_zeros, est.data(),
+                                                          est.size(), S.sep_entries.data(), S.sep_entries.size(), S.genome_estimates.data(), &rm[bi]);
         else if (a.have_separator || a.single_genome)
             rc = covh_genome_coverage_separator(&hdr, &hs, 1, (uint8_t)(a.single_genome ? '0' : a.separator), taker, !a.no_zeros, est.data(), est.size(),
                                                 a.single_genome, &rm[bi]);

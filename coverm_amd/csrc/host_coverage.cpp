@@ -3,6 +3,7 @@
 // Pure C++17, no HIP: this is where the reference's Rust `calculate_coverage` / takers / printers sit.
 #include "../../include/coverm_host.h"
 #include "knobs.h"
+#include "sep_entry_core.h"
 
 #include <algorithm>
 #include <mutex>
@@ -17,6 +18,7 @@
 #include <string>
 #include <thread>
 #include <string_view>
+#include <unordered_map>
 #include <vector>
 
 typedef uint64_t u64;
@@ -866,6 +868,100 @@ int covh_genome_coverage_separator(const covh_header *h, const covh_sample *samp
         }
         if (rm_out) { rm_out[si].num_mapped_reads = mapped_total; rm_out[si].num_reads = S.num_detected_primary_alignments; }
     }
+    return COV_OK;
+}
+
+uint32_t covh_genome_separator_ids(const covh_header *h, uint8_t split_char, int single_genome, int32_t *gid_of_tid) {
+    if (single_genome) { for (u32 t = 0; t < h->n_targets; t++) gid_of_tid[t] = 0; return 1; }
+    std::unordered_map<std::string_view, int32_t> ids;
+    std::string_view prev;
+    for (u32 t = 0; t < h->n_targets; t++) {
+        const std::string_view n = target_name(h, t);
+        const size_t p = n.find((char)split_char);
+        if (p == std::string_view::npos) return 0;
+        const std::string_view g = n.substr(0, p);
+        gid_of_tid[t] = (t != 0 && g == prev) ? gid_of_tid[t - 1] : ids.emplace(g, (int32_t)ids.size()).first->second;
+        prev = g;
+    }
+    return (uint32_t)ids.size();
+}
+
+int covh_genome_separator_entries(const covh_header *h, const covh_sample *sample, const int32_t *gid_of_tid, const covh_estimator *est,
+                                  size_t n_est, cov_genome_entry *entries, float *estimates, size_t *n_entries) {
+    if (!check_excl(est, n_est)) { g_err = "estimators disagree on contig_end_exclusion"; return COV_ERR_INVALID_ARG; }
+    const u64 excl = session_excl(est, n_est);
+    const u32 n = h->n_targets;
+    std::vector<uint8_t> obs(n);
+    for (u32 t = 0; t < n; t++) obs[t] = sample->stats[t].n_pass != 0;
+    std::vector<u32> blk(n), prev1(n), next(n), row((size_t)n + 1), tids(n), first(n);
+    std::vector<int32_t> egid(n);
+    const u32 ne = sepc::entries_cpu(gid_of_tid, obs.data(), n, blk.data(), prev1.data(), next.data(), row.data(), tids.data(), first.data(), egid.data());
+    EntryAcc acc;
+    std::vector<u64> unobs;
+    for (u32 e = 0; e < ne; e++) {
+        acc.reset(); unobs.clear();
+        cov_genome_entry &o = entries[e];
+        o.reads = 0; o.first_tid = first[e]; o.gid = egid[e]; o.n_contigs_seen = 0; o.any_nonzero = 0;
+        for (u32 i = row[e]; i < row[e + 1]; i++) {
+            const u32 t = tids[i];
+            const cov_contig_stats &s = sample->stats[t];
+            if (!obs[t]) { unobs.push_back(h->target_len[t]); continue; }
+            acc.add_contig(s, h->target_len[t], excl, s.n_nonsupp, s.sum_identity_primary, sample->hist);      // host_coverage.cpp: add_last_contig
+            o.reads += s.n_nonsupp; o.n_contigs_seen++;
+        }
+        for (size_t k = 0; k < n_est; k++) {
+            const float c = calculate(est[k], acc, unobs.data(), unobs.size());
+            estimates[(size_t)e * n_est + k] = c;
+            if (c > 0.0f) o.any_nonzero = 1;
+        }
+    }
+    *n_entries = ne;
+    return COV_OK;
+}
+
+// covh_genome_coverage_separator's control flow over entries that exist already: print_last_genomes at every change of entry and at the
+// end, zero_genomes2 in front of the first entry, between two entries and behind the last one.  zero_genomes2 walks down from the
+// entry's first_tid instead of its first observed target: the targets between the two carry the entry's own name, which it passes over.
+int covh_genome_coverage_separator_estimated(const covh_header *h, const char *stoit_name, uint64_t num_detected_primary_alignments,
+                                             uint8_t split_char, int single_genome, covh_taker *taker, int print_zero,
+                                             const covh_estimator *est, size_t n_est, const cov_genome_entry *entries, size_t n_entries,
+                                             const float *estimates, covh_reads_mapped *rm_out) {
+    if (!check_excl(est, n_est)) { g_err = "estimators disagree on contig_end_exclusion"; return COV_ERR_INVALID_ARG; }
+    for (size_t k = 0; k < n_est; k++)
+        if (est[k].kind == COVH_PILEUP_COUNTS || est[k].kind == COVH_TPM) { g_err = "covh_genome_coverage_separator_estimated: coverage histogram and TPM are evaluated on the host"; return COV_ERR_INVALID_ARG; }
+    if (n_entries == 0 || !entries || (n_est && !estimates)) { g_err = "covh_genome_coverage_separator_estimated: no entries (a sample without an observed target runs covh_genome_coverage_separator)"; return COV_ERR_INVALID_ARG; }
+    taker->start_stoit(stoit_name);
+    SepCtx cx{h, split_char, single_genome != 0};
+    static const char g1[] = "genome1";
+    u64 mapped_total = 0;
+    std::optional<std::string_view> last_genome;
+    for (size_t e = 0; e <= n_entries; e++) {
+        std::string_view current_genome;
+        if (e < n_entries) {
+            if (entries[e].first_tid >= h->n_targets) { g_err = "covh_genome_coverage_separator_estimated: first_tid outside the header"; return COV_ERR_INVALID_ARG; }
+            if (!cx.single) current_genome = cx.genome(entries[e].first_tid);
+        }
+        if (e != 0) {      // print_last_genomes of entry e - 1
+            const cov_genome_entry &E = entries[e - 1];
+            const float *c = estimates + (e - 1) * n_est;
+            bool positive = false;
+            for (size_t k = 0; k < n_est; k++) positive |= c[k] > 0.0f;
+            if (print_zero || positive) {
+                taker->start_entry(E.first_tid, cx.single ? std::string_view(g1, 7) : *last_genome);
+                for (size_t k = 0; k < n_est; k++) {
+                    if (c[k] > 0.0f) taker->add_single_coverage(c[k]);
+                    else print_zero_coverage(est[k], *taker, 9);
+                }
+                taker->finish_entry();
+            }
+            if (positive) mapped_total += E.reads;
+        }
+        if (print_zero && !cx.single)
+            zero_genomes2(cx, last_genome, current_genome, e < n_entries ? entries[e].first_tid : h->n_targets - 1, est, n_est, *taker);
+        if (cx.err) { g_err = "Contig name does not contain split symbol, so cannot determine which genome it belongs to"; return COV_ERR_INVALID_ARG; }
+        last_genome = current_genome;
+    }
+    if (rm_out) { rm_out->num_mapped_reads = mapped_total; rm_out->num_reads = num_detected_primary_alignments; }
     return COV_OK;
 }
 

@@ -131,6 +131,7 @@ class Session:
         self._check(self._lib.cov_set_targets(self._h, len(tl), tl.ctypes.data if len(tl) else None))
         self.n_targets = len(tl)
         self.target_len = tl
+        self._runs = False                         # (cov_set_targets and cov_set_target_mask turn genomes and runs off)
         if mask is not None:
             m = np.ascontiguousarray(mask, dtype=np.uint8)
             assert len(m) == len(tl)
@@ -194,6 +195,7 @@ class Session:
         """cov_set_genomes (after set_targets): genome_of_tid[t] = genome of target t, -1 = outside every genome.  Implies the target mask;
         with estimators set, every finish then also aggregates the contigs into genomes and evaluates the estimators per genome on the
         device.  None / n_genomes = 0 turns it off."""
+        self._runs = False
         if genome_of_tid is None or n_genomes == 0:
             self._n_genomes = 0
             self._check(self._lib.cov_set_genomes(self._h, None, C.c_uint32(0)))
@@ -203,6 +205,33 @@ class Session:
         self._n_genomes = int(n_genomes)
         self._check(self._lib.cov_set_genomes(self._h, g.ctypes.data if len(g) else None, C.c_uint32(n_genomes)))
 
+    def set_genome_runs(self, gid_of_tid, n_gids: int):
+        """cov_set_genome_runs (after set_targets): gid_of_tid[t] >= 0 = dense id of target t's genome (the name's prefix before the
+        separator; all 0 in single-genome mode).  With estimators set, every finish then builds the entries of the separator /
+        single-genome scan on the device and evaluates the estimators per entry: genome_entries(), genome_estimates().  Sets no mask
+        and turns set_genomes off; None / n_gids = 0 turns it off."""
+        self._n_genomes = 0
+        if gid_of_tid is None or n_gids == 0:
+            self._runs = False
+            self._check(self._lib.cov_set_genome_runs(self._h, None, C.c_uint32(0)))
+            return
+        g = np.ascontiguousarray(gid_of_tid, dtype=np.int32)
+        assert len(g) == self.n_targets
+        self._check(self._lib.cov_set_genome_runs(self._h, g.ctypes.data if len(g) else None, C.c_uint32(n_gids)))
+        self._runs = True
+
+    def genome_entry_count(self) -> int:
+        """cov_genome_entry_count: entries of the last finish (set_genome_runs)."""
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_genome_entry_count(self._h, C.byref(n)))
+        return n.value
+
+    def genome_entries(self):
+        """cov_fetch_genome_entries: one native.GENOME_ENTRY_DTYPE entry per entry of the scan, in the order it prints them."""
+        out = np.zeros(self.genome_entry_count(), dtype=native.GENOME_ENTRY_DTYPE)
+        self._check(self._lib.cov_fetch_genome_entries(self._h, out.ctypes.data if out.size else None))
+        return out
+
     def finish_genomes(self):
         """cov_finish_genomes: the pipeline and its verdicts without the per-contig statistics (genomes and estimators set)."""
         summ = CovSummary()
@@ -211,8 +240,9 @@ class Session:
         return summ
 
     def genome_estimates(self):
-        """cov_fetch_genome_estimates: n_genomes x n_estimators f32 of the last finish."""
-        out = np.empty((getattr(self, "_n_genomes", 0), getattr(self, "_n_est", 0)), dtype=np.float32)
+        """cov_fetch_genome_estimates: n_genomes (set_genomes) or n_entries (set_genome_runs) x n_estimators f32 of the last finish."""
+        n = self.genome_entry_count() if getattr(self, "_runs", False) else getattr(self, "_n_genomes", 0)
+        out = np.empty((n, getattr(self, "_n_est", 0)), dtype=np.float32)
         self._check(self._lib.cov_fetch_genome_estimates(self._h, out.ctypes.data if out.size else None))
         return out
 
@@ -237,6 +267,13 @@ class Session:
         n = C.c_uint64(0)
         self._check(self._lib.cov_group_records(self._h, C.byref(n)))
         return int(n.value)
+
+    def sep_kernel_ms(self):
+        """(ms, launches) of the kernels that built the separator entries' table in the last finish (COV_K_SEP, set_genome_runs)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_SEP, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
 
     def group_kernel_ms(self):
         """(ms, launches) of the last group_records (COV_K_GROUP)."""

@@ -377,6 +377,54 @@ def mosdepth_genome_coverage(names, target_len, samples, split_char: str, covera
     return _finish(rc, rm, len(samples))
 
 
+def genome_separator_ids(names, target_len, split_char: str, single_genome: bool):
+    """covh_genome_separator_ids: (gid_of_tid int32, n_gids) for Session.set_genome_runs; n_gids = 0 when a name lacks the separator."""
+    h, k1 = _header(names, target_len)
+    gid = np.zeros(len(names), np.int32)
+    L = _lib()
+    L.covh_genome_separator_ids.restype = C.c_uint32
+    L.covh_genome_separator_ids.argtypes = [C.c_void_p, C.c_uint8, C.c_int, C.c_void_p]
+    n = L.covh_genome_separator_ids(C.byref(h), ord(split_char), int(bool(single_genome)), gid.ctypes.data if len(gid) else None)
+    return gid, int(n)
+
+
+def genome_separator_entries(names, target_len, sample: SampleResult, gid_of_tid, coverage_estimators):
+    """covh_genome_separator_entries: (entries native.GENOME_ENTRY_DTYPE, floats n_entries x n_estimators) of one sample, aggregated on
+    the host from its per-contig statistics."""
+    h, k1 = _header(names, target_len)
+    sa, k2 = _samples([sample])
+    g = np.ascontiguousarray(gid_of_tid, np.int32)
+    n, ne = len(names), len(coverage_estimators)
+    ent = np.zeros(max(1, n), native.GENOME_ENTRY_DTYPE)
+    flat = np.zeros(max(1, n * ne), np.float32)
+    cnt = C.c_size_t(0)
+    L = _lib()
+    L.covh_genome_separator_entries.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    rc = L.covh_genome_separator_entries(C.byref(h), sa, g.ctypes.data if n else None, _est_array(coverage_estimators), ne, ent.ctypes.data, flat.ctypes.data, C.byref(cnt))
+    if rc != 0:
+        raise HostError(rc, L.covh_last_error().decode())
+    return ent[:cnt.value].copy(), flat[:cnt.value * ne].reshape(cnt.value, ne).copy()
+
+
+def genome_coverage_separator_estimated(names, target_len, stoit_name: str, num_detected_primary_alignments: int, split_char: str,
+                                        single_genome: bool, coverage_taker: CoverageTaker, print_zero_coverage_genomes: bool,
+                                        coverage_estimators, entries, estimates) -> ReadsMapped:
+    """The separator / single-genome scan of one sample whose entries were aggregated and evaluated already: `entries` =
+    Session.genome_entries(), `estimates` = Session.genome_estimates()."""
+    h, k1 = _header(names, target_len)
+    en = np.ascontiguousarray(entries)
+    e = np.ascontiguousarray(estimates, np.float32)
+    assert en.dtype == native.GENOME_ENTRY_DTYPE and e.size == len(en) * len(coverage_estimators)
+    rm = (_ReadsMapped * 1)()
+    L = _lib()
+    L.covh_genome_coverage_separator_estimated.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint8, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t,
+                                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+    rc = L.covh_genome_coverage_separator_estimated(C.byref(h), stoit_name.encode(), num_detected_primary_alignments, ord(split_char), int(bool(single_genome)),
+                                                    coverage_taker._h, int(print_zero_coverage_genomes), _est_array(coverage_estimators), len(coverage_estimators),
+                                                    en.ctypes.data if len(en) else None, len(en), e.ctypes.data if e.size else None, rm)
+    return _finish(rc, rm, 1)[0]
+
+
 def print_headers(taker: CoverageTaker, printer: int, entry_type: str, headers: List[str]):
     hs = (C.c_char_p * max(1, len(headers)))(*[x.encode() for x in headers])
     _lib().covh_print_headers(taker._h, C.c_int(printer), entry_type.encode(), hs, C.c_size_t(len(headers)))

@@ -135,6 +135,25 @@ int covh_genome_coverage_separator(const covh_header *h, const covh_sample *samp
                                    uint8_t split_char, covh_taker *taker, int print_zero_coverage_genomes,
                                    const covh_estimator *est, size_t n_est, int single_genome,
                                    covh_reads_mapped *reads_mapped_out);
+/* The separator / single-genome scan's genome ids of a header (cov_set_genome_runs' gid_of_tid): dense ids of the names' prefixes before
+ * split_char in order of first appearance, all 0 for single_genome.  Returns the number of ids, or 0 when some name does not contain
+ * split_char (the scan raises "Contig name does not contain split symbol" only for the names it touches: such a header stays with
+ * covh_genome_coverage_separator). */
+uint32_t covh_genome_separator_ids(const covh_header *h, uint8_t split_char, int single_genome, int32_t *gid_of_tid);
+/* The entries of ONE sample's separator scan aggregated on the host from per-contig statistics: the table entry -> targets by
+ * csrc/sep_entry_core.h's CPU emulation, EntryAcc::add_contig over each entry's observed targets in ascending order and
+ * calculate_coverage with its unobserved lengths — what covh_genome_coverage_separator computes and what cov_fetch_genome_entries /
+ * cov_fetch_genome_estimates return from the device, bit for bit.  entries: room for n_targets, estimates: n_targets x n_est. */
+int covh_genome_separator_entries(const covh_header *h, const covh_sample *sample, const int32_t *gid_of_tid, const covh_estimator *est,
+                                  size_t n_est, cov_genome_entry *entries, float *estimates, size_t *n_entries);
+/* The separator / single-genome scan of ONE sample with its entries aggregated and evaluated already (cov_set_genome_runs, or
+ * covh_genome_separator_entries): n_entries > 0 entries (a sample without an observed target runs covh_genome_coverage_separator:
+ * nothing to aggregate) and n_entries x n_est floats.  What is left is genome.rs:419-797's control flow: start_entry(first_tid, name),
+ * the zero rows of the genomes between two entries, --no-zeros, ReadsMapped.  Every name of the header contains split_char. */
+int covh_genome_coverage_separator_estimated(const covh_header *h, const char *stoit_name, uint64_t num_detected_primary_alignments,
+                                             uint8_t split_char, int single_genome, covh_taker *taker, int print_zero_coverage_genomes,
+                                             const covh_estimator *est, size_t n_est, const cov_genome_entry *entries, size_t n_entries,
+                                             const float *estimates, covh_reads_mapped *reads_mapped_out);
 const char *covh_last_error(void);
 
 /* CoveragePrinter (coverage_printer.rs).  printer: 0 streamed, 1 sparse cached, 2 dense cached, 3 MetaBAT.

@@ -152,7 +152,8 @@ typedef enum {
     COV_K_GENOME = 7,   /* cov_set_genomes: contigs reduced into genomes, histograms merged, calculate_coverage of every genome */
     COV_K_GROUP = 8,    /* cov_group_records: order check, sort passes and gather of the last call, summed (not part of a finish) */
     COV_K_SAM = 9,      /* cov_sam_*: the decode kernels of the last SAM text ingest, summed over its windows (not part of a finish) */
-    COV_K_COUNT = 10
+    COV_K_SEP = 10,     /* cov_set_genome_runs: the table entry -> targets of the finish (scans, compaction, segments), in front of COV_K_GENOME */
+    COV_K_COUNT = 11
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -398,6 +399,29 @@ cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_
 cov_status cov_finish_genomes(cov_session *s, cov_summary *summary);
 cov_status cov_fetch_genome_estimates(cov_session *s, float *out);          /* after cov_finish: n_genomes * n_est floats */
 cov_status cov_fetch_genome_stats(cov_session *s, cov_genome_stats *out);   /* after cov_finish: n_genomes entries */
+
+/* ---- the separator / single-genome scan on the device (mosdepth_genome_coverage, genome.rs:419-929): one entry per run of observed
+ * targets of one genome.  cov_set_genome_runs after cov_set_targets: gid_of_tid[t] >= 0 is the dense id of target t's genome (the part
+ * of its name before the separator; all 0 for --single-genome), n_gids the number of ids.  It sets no mask.  NULL or n_gids = 0 turns it
+ * off; so do cov_set_targets, cov_set_target_mask and cov_set_genomes — and cov_set_genome_runs turns cov_set_genomes (and its mask) off.
+ * Which targets form an entry, and which targets without a considered record count as its unobserved lengths, depends on where the
+ * sample's reads fall: with runs and estimators set, cov_finish / cov_finish_genomes build the table entry -> targets on the device
+ * behind the per-contig pass (the rule: csrc/sep_entry_core.h), then reduce, merge and evaluate over it as for cov_set_genomes, with the
+ * reads counted as genome.rs:677-682 counts them (considered and not supplementary) and ANIr over the primary-read identity sum
+ * (genome.rs:724-727).  cov_fetch_estimates returns COV_ERR_STATE (the entries are genomes).
+ * cov_genome_entry_count: entries of the last finish (0 when no target had a considered record).  cov_fetch_genome_entries: one
+ * cov_genome_entry each, in the order the scan prints them; cov_fetch_genome_estimates: n_entries x n_est floats, bit for bit what
+ * coverm_host.h's covh_genome_coverage_separator computes.  After a spill of the bounded record store all of them return COV_ERR_STATE. */
+typedef struct {
+    uint64_t reads;            /* sum of n_nonsupp over the entry's observed targets (genome.rs:677-682) */
+    uint32_t first_tid;        /* first target of the run of the genome's names the entry starts in (start_entry's index) */
+    int32_t gid;               /* gid_of_tid of its targets */
+    uint32_t n_contigs_seen;   /* targets with a considered record */
+    uint32_t any_nonzero;      /* some estimator's value is > 0 */
+} cov_genome_entry;
+cov_status cov_set_genome_runs(cov_session *s, const int32_t *gid_of_tid, uint32_t n_gids);
+cov_status cov_genome_entry_count(cov_session *s, uint32_t *n_entries);
+cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
 
 /* ---- bounded record store.  The reference holds one contig at a time and flushes it when the tid changes (contig.rs:128-155), so a
  * sample may be arbitrarily large.  The session's record store keeps as many contigs as fit under a cap (2^31 records / 2^31 CIGAR
