@@ -30,6 +30,8 @@
 #include "../../include/covermhip.h"
 #include "roctx_ranges.h"
 #include "knobs.h"
+#include "record_store.h"
+#include "store_plan_core.h"
 
 using namespace covk;
 
@@ -62,29 +64,6 @@ namespace {
             return COV_ERR_HIP;                                                               \
         }                                                                                     \
     } while (0)
-
-template <typename T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;  // elements
-    hipError_t reserve(size_t n, hipStream_t st, size_t keep = 0) {
-        if (n <= cap) return hipSuccess;
-        size_t nc = std::max(n, cap + cap / 2);
-        T *q = nullptr;
-        hipError_t e = hipMalloc(&q, nc * sizeof(T));
-        if (e != hipSuccess) return e;
-        if (keep && p) {
-            e = hipMemcpyAsync(q, p, keep * sizeof(T), hipMemcpyDeviceToDevice, st);
-            if (e != hipSuccess) return e;
-            e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return e;
-        }
-        if (p) (void)hipFree(p);
-        p = q; cap = nc;
-        return hipSuccess;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
 
 std::string g_create_error;
 
@@ -159,20 +138,12 @@ struct cov_session {
     // cov_gather (root session): every rank's block, device and page-locked host copies
     DevBuf<uint8_t> d_gather; uint8_t *h_gather = nullptr; size_t h_gather_cap = 0; uint32_t gather_n = 0; size_t gather_block = 0;
 
-    // record store (owned) or adopted device batch
-    DevBuf<int32_t> s_tid, s_pos;
-    DevBuf<uint16_t> s_flag;
-    DevBuf<uint8_t> s_mapq, s_nmk;
-    DevBuf<u32> s_nm, s_lseq, s_coff, s_cig;
-    // mates of the records the device ingest extracted (cov_ingest_want_mates): next_refID + read-name hash, for cov_pair_filter_apply
-    DevBuf<int32_t> s_mtid; DevBuf<u64> s_qh1; DevBuf<u32> s_qh2;
-    bool want_mates = false;
+    RecordStore store;               // record store (owned, record_store.h) or adopted device batch
+    bool want_mates = false;         // cov_ingest_want_mates: the ingest keeps the mate columns, for cov_pair_filter_apply
     bool want_grouping = false;      // cov_ingest_want_grouping: cov_group_records will follow, so decreasing keys are no reason to hand a file back
     bool ing_was_span = false;       // records of a cov_ingest_span rank are in the store: cov_group_records refuses
     float grp_ms[4] = {};            // the last cov_group_records: whole call on the stream, order check, sort passes, gather
     uint32_t grp_launches = 0;
-    uint64_t mates_valid = 0;        // the mate columns describe records [0, mates_valid) of the store
-    uint64_t n_records = 0, n_cigar = 0;
     bool adopted = false;
     cov_batch adopted_batch{};
     uint64_t adopted_ncig = 0;
@@ -199,7 +170,6 @@ struct cov_session {
     std::vector<uint64_t> merged_hist;      // histogram of the last cov_finish when it merged spilled contigs (cov_fetch_hist serves it)
     bool merged_valid = false;
     uint64_t merged_records = 0;            // records of the whole sample after a merging finish (cov_gather sends it)
-    DevBuf<uint8_t> d_spill_tmp;
     uint64_t ing_rec_spilled = 0;           // records of the running ingest that already left the store
     uint64_t spill_retry_at = 0;            // after a spill that could move nothing: no further attempt below this many records
 
@@ -299,7 +269,7 @@ struct cov_session {
     uint32_t k_launches[COV_K_COUNT] = {};
 };
 
-cov_status spill_store(cov_session *s, bool &progress);      // bounded record store (defined behind finish_once)
+static cov_status spill_store(cov_session *s, bool &progress);      // bounded record store (defined behind finish_once)
 
 namespace {
 
@@ -337,12 +307,9 @@ Records records_of(const cov_session *s) {
         const cov_batch &b = s->adopted_batch;
         r.tid = b.tid; r.pos = b.pos; r.flag = b.flag; r.mapq = b.mapq; r.nm = b.nm; r.nm_kind = b.nm_kind;
         r.l_seq = b.l_seq; r.cigar_off = b.cigar_off; r.cigar = b.cigar;
-    } else {
-        r.tid = s->s_tid.p; r.pos = s->s_pos.p; r.flag = s->s_flag.p; r.mapq = s->s_mapq.p; r.nm = s->s_nm.p;
-        r.nm_kind = s->s_nmk.p; r.l_seq = s->s_lseq.p; r.cigar_off = s->s_coff.p; r.cigar = s->s_cig.p;
-    }
-    r.n = (u32)s->n_records;
-    r.cigar_end = s->adopted ? s->adopted_cig_end : (u32)s->n_cigar;
+    } else s->store.view(r);
+    r.n = (u32)s->store.n_records;
+    r.cigar_end = s->adopted ? s->adopted_cig_end : (u32)s->store.n_cigar;
     return r;
 }
 
@@ -372,41 +339,37 @@ cov_status append(cov_session *s, const cov_batch *b, bool from_device) {
         off0 = b->cigar_off[0]; offn = b->cigar_off[n];
     }
     const uint64_t ncig = (uint64_t)offn - off0;
-    if (s->n_records && (s->n_records + n > s->cap_records || s->n_cigar + ncig > s->cap_cigar) && s->n_records >= s->spill_retry_at) {
+    if (s->store.n_records && (s->store.n_records + n > s->cap_records || s->store.n_cigar + ncig > s->cap_cigar) && s->store.n_records >= s->spill_retry_at) {
         // bounded store: the contigs that are complete leave for the host, the contig in flight moves to the front (contig.rs:128-155)
         bool progress = false;
         const cov_status sp = spill_store(s, progress);
         if (sp != COV_OK) return sp;
         // one reference already fills the store: a spill is a whole pass over it that moves nothing — not again before the store has doubled
-        s->spill_retry_at = progress ? 0 : 2 * s->n_records;
+        s->spill_retry_at = progress ? 0 : 2 * s->store.n_records;
     }
-    if (s->n_records + n >= 0xfffffff0ull) { s->err = "more than 2^32 records of one reference (or of one batch) in the record store"; return COV_ERR_INVALID_ARG; }
-    if (s->n_cigar + ncig >= 0xfffffff0ull) { s->err = "more than 2^32 CIGAR words of one reference (or of one batch) in the record store"; return COV_ERR_INVALID_ARG; }
-    const uint64_t R = s->n_records, N = R + n;
-    hipStream_t st = s->stream;
-    HIPCHK(s->s_tid.reserve(N, st, R)); HIPCHK(s->s_pos.reserve(N, st, R)); HIPCHK(s->s_flag.reserve(N, st, R));
-    HIPCHK(s->s_mapq.reserve(N, st, R)); HIPCHK(s->s_nmk.reserve(N, st, R)); HIPCHK(s->s_nm.reserve(N, st, R));
-    HIPCHK(s->s_lseq.reserve(N, st, R)); HIPCHK(s->s_coff.reserve(N + 1, st, R + 1));
-    HIPCHK(s->s_cig.reserve(s->n_cigar + ncig + 1, st, s->n_cigar));
-    HIPCHK(hipMemcpyAsync(s->s_tid.p + R, b->tid, n * 4, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_pos.p + R, b->pos, n * 4, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_flag.p + R, b->flag, n * 2, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_mapq.p + R, b->mapq, n, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_nmk.p + R, b->nm_kind, n, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_nm.p + R, b->nm, n * 4, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_lseq.p + R, b->l_seq, n * 4, kind, st));
-    HIPCHK(hipMemcpyAsync(s->s_coff.p + R, b->cigar_off, (n + 1) * 4, kind, st));
-    if (ncig) HIPCHK(hipMemcpyAsync(s->s_cig.p + s->n_cigar, b->cigar + off0, ncig * 4, kind, st));
-    if (off0 != (u32)s->n_cigar) {
+    if (s->store.n_records + n >= 0xfffffff0ull) { s->err = "more than 2^32 records of one reference (or of one batch) in the record store"; return COV_ERR_INVALID_ARG; }
+    if (s->store.n_cigar + ncig >= 0xfffffff0ull) { s->err = "more than 2^32 CIGAR words of one reference (or of one batch) in the record store"; return COV_ERR_INVALID_ARG; }
+    RecordStore &S = s->store;
+    const uint64_t R = S.n_records, N = R + n; hipStream_t st = s->stream;
+    HIPCHK(S.reserve(N, S.n_cigar + ncig + 1, st, R, S.n_cigar, false));
+    HIPCHK(S.copy_in(*b, n, off0, ncig, kind, st));
+    if (off0 != (u32)S.n_cigar) {
         const u32 cnt = (u32)(n + 1);
-        hipLaunchKernelGGL(k_rebase_offsets, dim3((cnt + 255) / 256), dim3(256), 0, st, s->s_coff.p + R, cnt, off0,
-                           (u32)s->n_cigar);
+        hipLaunchKernelGGL(k_rebase_offsets, dim3((cnt + 255) / 256), dim3(256), 0, st, S.cigar_off.p + R, cnt, off0, (u32)S.n_cigar);
         HIPCHK(hipGetLastError());
     }
-    s->n_records = N; s->n_cigar += ncig;
+    S.n_records = N; S.n_cigar += ncig;
     s->finished = false;
     if (!from_device) HIPCHK(hipStreamSynchronize(st));   // contract: host arrays are free to change on return
     return COV_OK;
+}
+
+// An adopted device batch becomes the content of the owned store (before anything else is written behind it).
+cov_status materialise_adopted(cov_session *s) {
+    if (!s->adopted) return COV_OK;
+    const cov_batch ab = s->adopted_batch;
+    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0;
+    return append(s, &ab, true);
 }
 
 void timing_events(cov_session *s) {
@@ -655,10 +618,7 @@ void cov_destroy(cov_session *s) {
     s->h_res = nullptr; s->h_res_cap = 0; s->h_ctg = nullptr;
     if (s->h_chist) (void)hipHostFree(s->h_chist);
     s->h_chist = nullptr; s->h_chist_cap = 0;
-    s->h_estf = nullptr; s->d_spill_tmp.release();
-    s->s_tid.release(); s->s_pos.release(); s->s_flag.release(); s->s_mapq.release(); s->s_nmk.release();
-    s->s_nm.release(); s->s_lseq.release(); s->s_coff.release(); s->s_cig.release();
-    s->s_mtid.release(); s->s_qh1.release(); s->s_qh2.release();
+    s->h_estf = nullptr; s->store.release();
     s->d_runs.release(); s->d_part.release(); s->d_prep_args.release(); s->d_gen_list.release(); s->d_hist_top.release(); s->d_ident.release(); s->d_identp.release(); s->d_idch.release();
     if (s->ev_prep_done) (void)hipEventDestroy(s->ev_prep_done);
     if (s->ev_side_done) (void)hipEventDestroy(s->ev_side_done); s->d_arena.release(); s->d_chist.release(); s->d_depth.release();
@@ -852,37 +812,27 @@ cov_status cov_push_batch(cov_session *s, const cov_batch *b) {
     if (!s || !b) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
     if (s->ing_active) { const cov_status a = cov_ingest_abort(s); if (a != COV_OK) return a; }   // an ingest left open: its queued work may still write the store
-    if (s->adopted) {  // materialise the adopted device batch into the owned store first
-        cov_batch ab = s->adopted_batch;
-        s->adopted = false; s->n_records = 0; s->n_cigar = 0;
-        cov_status st = append(s, &ab, true);
-        if (st) return st;
-    }
+    { const cov_status st = materialise_adopted(s); if (st) return st; }
     return append(s, b, false);
 }
 
 cov_status cov_push_batch_device(cov_session *s, const cov_batch *b) {
     if (!s || !b) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
-    if (s->n_records == 0 && !s->adopted) {
+    if (s->store.n_records == 0 && !s->adopted) {
         if (b->n_records >= 0xfffffff0ull) { s->err = "more than 2^32 records in one session"; return COV_ERR_INVALID_ARG; }
         u32 o0 = 0, o1 = 0;
         if (b->n_records) {
             HIPCHK(hipMemcpy(&o0, b->cigar_off, 4, hipMemcpyDeviceToHost));
             HIPCHK(hipMemcpy(&o1, b->cigar_off + b->n_records, 4, hipMemcpyDeviceToHost));
         }
-        s->adopted = true; s->adopted_batch = *b; s->n_records = b->n_records;
+        s->adopted = true; s->adopted_batch = *b; s->store.n_records = b->n_records;
         s->adopted_ncig = (uint64_t)o1 - o0;
         s->adopted_cig_end = o1;
         s->finished = false;
         return COV_OK;
     }
-    if (s->adopted) {
-        cov_batch ab = s->adopted_batch;
-        s->adopted = false; s->n_records = 0; s->n_cigar = 0;
-        cov_status st = append(s, &ab, true);
-        if (st) return st;
-    }
+    { const cov_status st = materialise_adopted(s); if (st) return st; }
     return append(s, b, true);
 }
 
@@ -916,7 +866,7 @@ cov_status cov_reset(cov_session *s) {
         if (a != COV_OK && !(spilled && a == COV_ERR_STATE)) return a;
         if (a != COV_OK) s->err.clear();
     }
-    s->adopted = false; s->n_records = 0; s->n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->mates_valid = 0; s->ing_was_span = false;
+    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->store.mates_valid = 0; s->ing_was_span = false;
     s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing_rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
@@ -1110,7 +1060,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     timing_events(s);
     hipStream_t st = s->stream;
     const u32 nT = s->n_targets;
-    const u32 R = (u32)s->n_records;
+    const u32 R = (u32)s->store.n_records;
     const bool want_hist = s->cfg.want & COV_WANT_HIST, want_id = s->cfg.want & COV_WANT_IDENTITY;
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
     bool compacted = false;      // the compact histogram was built by this pass (else: by the first cov_fetch_hist)
@@ -1121,7 +1071,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     // k_prep geometry: 4096 records per workgroup for short reads (k_prep_lean: each of the four waves walks 16 steps of 64 consecutive records;
     // k_prep7s: 16 passes of 256); one step / pass when CIGARs are long, where the work per record is large and records are few (long-read
     // mappings), so that every CU gets workgroups
-    const uint64_t ncig_all = s->adopted ? s->adopted_ncig : s->n_cigar;
+    const uint64_t ncig_all = s->adopted ? s->adopted_ncig : s->store.n_cigar;
     const bool long_cigars = R && ncig_all / R >= 16;
     const int prep_kernel = s->prep_kernel;
     const int prep_passes = long_cigars ? 1 : 2 * PREP_PASSES, prep_b = 1;
@@ -1139,7 +1089,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     ti.tile_first = s->d_tile_first.p; ti.tcnt = s->d_tcnt.p; ti.fov = s->d_fov.p; ti.shift = s->tile_shift; ti.n_tiles = s->n_tiles;
     CxIdx cx{};
     {
-        const uint64_t ncig_now = s->adopted ? s->adopted_ncig : s->n_cigar;
+        const uint64_t ncig_now = s->adopted ? s->adopted_ncig : s->store.n_cigar;
         HIPCHK(s->d_cx_list.reserve((size_t)(ncig_now / CX_MIN_OPS) + 64, st));
         cx.list = s->d_cx_list.p; cx.list_cap = (u32)std::min<uint64_t>(ncig_now / CX_MIN_OPS + 64, 0xffffffffull);
         cx.cnt = s->d_cx_cnt.p; cx.cur = s->d_cx_cur.p; cx.cscan = s->d_cx_scan.p; cx.ctop = s->d_cx_top.p;
@@ -1435,7 +1385,7 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
 
     // algorithmic bytes: each record's SoA fields and CIGAR words are needed once; results written once
     {
-        const uint64_t ncig = s->adopted ? s->adopted_ncig : s->n_cigar;
+        const uint64_t ncig = s->adopted ? s->adopted_ncig : s->store.n_cigar;
         s->algo_bytes = (uint64_t)R * 24 + ncig * 4 + (uint64_t)nT * sizeof(DevContig);
     }
 
@@ -1461,27 +1411,14 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
 // ---- bounded record store: spill and merge (see cov_session::spill)
 static cov_status fetch_chunk_hist(cov_session *s, uint64_t *hist);
 
-extern "C++" {
-namespace {
-template <typename T>
-cov_status move_front(cov_session *s, T *p, size_t from, size_t n) {
-    if (!n || !from) return COV_OK;
-    hipStream_t st = s->stream;
-    if (n <= from) { HIPCHK(hipMemcpyAsync(p, p + from, n * sizeof(T), hipMemcpyDeviceToDevice, st)); return COV_OK; }      // disjoint
-    HIPCHK(s->d_spill_tmp.reserve(n * sizeof(T), st));
-    HIPCHK(hipMemcpyAsync(s->d_spill_tmp.p, p + from, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    HIPCHK(hipMemcpyAsync(p, s->d_spill_tmp.p, n * sizeof(T), hipMemcpyDeviceToDevice, st));
-    return COV_OK;
-}
-
 // Runs the pipeline over the store, keeps every contig but the one in flight, moves the records from that contig's first considered
 // record onwards to the front.  The contig in flight = the last considered contig (after the order check: the highest tid with a
 // considered record); every considered record behind its first one is its own (anything else would have failed the order check),
 // so the contigs in front of it are complete — the reference would have flushed them at the tid change (contig.rs:128-155).
 // progress = false: nothing could leave (one contig fills the store, or the store is an adopted batch / carries mate columns).
-cov_status spill_store_impl(cov_session *s, bool &progress) {
+static cov_status spill_store(cov_session *s, bool &progress) {
     progress = false;
-    if (s->adopted || s->n_records == 0 || s->want_mates || s->n_targets == 0) return COV_OK;
+    if (s->adopted || s->store.n_records == 0 || s->want_mates || s->n_targets == 0) return COV_OK;
     covr::Range rr("bounded store: spill");
     const u32 nT = s->n_targets;
     const bool want_hist = s->cfg.want & COV_WANT_HIST;
@@ -1492,7 +1429,7 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
     cov_status rc = finish_store(s, st.data(), &sm);
     s->in_spill = false; s->lean_finish = lean_was;
     if (rc != COV_OK) return rc;
-    const u64 R = s->n_records;
+    const u64 R = s->store.n_records;
     cov_session::Spill &S = s->spill;
     int64_t cstar = -1; u64 best = 0;
     for (u32 c = 0; c < nT; c++)
@@ -1517,14 +1454,14 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
     }
     hipStream_t q = s->stream;
     u64 prim_keep = 0;
-    u32 c0 = (u32)s->n_cigar;
+    u32 c0 = (u32)s->store.n_cigar;
     if (keep_from < R) {
         unsigned long long *ctr = reinterpret_cast<unsigned long long *>(&s->d_glob.p->pad2[1]);
         HIPCHK(hipMemsetAsync(ctr, 0, 8, q));
-        hipLaunchKernelGGL(k_count_primary, dim3((u32)std::min<u64>((R - keep_from + 255) / 256, (u64)s->n_cus * 8)), dim3(256), 0, q, (const uint16_t *)s->s_flag.p, (u32)keep_from, (u32)R, ctr);
+        hipLaunchKernelGGL(k_count_primary, dim3((u32)std::min<u64>((R - keep_from + 255) / 256, (u64)s->n_cus * 8)), dim3(256), 0, q, (const uint16_t *)s->store.flag.p, (u32)keep_from, (u32)R, ctr);
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(&prim_keep, ctr, 8, hipMemcpyDeviceToHost, q));
-        HIPCHK(hipMemcpyAsync(&c0, s->s_coff.p + keep_from, 4, hipMemcpyDeviceToHost, q));
+        HIPCHK(hipMemcpyAsync(&c0, s->store.cigar_off.p + keep_from, 4, hipMemcpyDeviceToHost, q));
         HIPCHK(hipStreamSynchronize(q));
     }
     S.prim += sm.num_detected_primary_alignments - prim_keep;
@@ -1532,18 +1469,14 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
     S.records += keep_from;
     if (cstar > S.inflight) S.inflight = cstar;
     S.count++;
-    const u64 n_keep = R - keep_from, cig_keep = s->n_cigar - c0;
-    cov_status m = COV_OK;
-    if ((m = move_front(s, s->s_tid.p, keep_from, n_keep)) || (m = move_front(s, s->s_pos.p, keep_from, n_keep)) || (m = move_front(s, s->s_flag.p, keep_from, n_keep)) ||
-        (m = move_front(s, s->s_mapq.p, keep_from, n_keep)) || (m = move_front(s, s->s_nmk.p, keep_from, n_keep)) || (m = move_front(s, s->s_nm.p, keep_from, n_keep)) ||
-        (m = move_front(s, s->s_lseq.p, keep_from, n_keep)) || (m = move_front(s, s->s_coff.p, keep_from, n_keep + 1)) || (m = move_front(s, s->s_cig.p, c0, cig_keep)))
-        return m;
+    const u64 n_keep = R - keep_from, cig_keep = s->store.n_cigar - c0;
+    HIPCHK(s->store.move_front(keep_from, c0, q));
     if (n_keep && c0) {
-        hipLaunchKernelGGL(k_rebase_offsets, dim3((u32)((n_keep + 1 + 255) / 256)), dim3(256), 0, q, s->s_coff.p, (u32)(n_keep + 1), c0, 0u);
+        hipLaunchKernelGGL(k_rebase_offsets, dim3((u32)((n_keep + 1 + 255) / 256)), dim3(256), 0, q, s->store.cigar_off.p, (u32)(n_keep + 1), c0, 0u);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipStreamSynchronize(q));
-    s->n_records = n_keep; s->n_cigar = cig_keep;
+    s->store.n_records = n_keep; s->store.n_cigar = cig_keep;
     s->finished = false; s->depth_all_valid = false;
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] bounded store: spill %u, %llu records left the store (%llu stay: contig %lld in flight), %llu since the sample began\n", S.count,
@@ -1551,9 +1484,6 @@ cov_status spill_store_impl(cov_session *s, bool &progress) {
     progress = true;
     return COV_OK;
 }
-}  // namespace
-cov_status spill_store(cov_session *s, bool &progress) { return spill_store_impl(s, progress); }
-}  // extern "C++"
 
 // cov_finish after one or more spills: `stats` / `summary` hold the pass over what the store still held; the contigs that left
 // earlier come back from the host, the histogram is re-based into one array (cov_fetch_hist serves it), and the device's result
@@ -1602,12 +1532,8 @@ cov_status cov_reserve(cov_session *s, uint64_t n_records, uint64_t n_cigar) {
     if (!s) return COV_ERR_INVALID_ARG;
     if (n_records >= 0xfffffff0ull || n_cigar >= 0xfffffff0ull) { s->err = "more than 2^32 records in one session"; return COV_ERR_INVALID_ARG; }
     HIPCHK(hipSetDevice(s->cfg.device));
-    hipStream_t st = s->stream;
-    const uint64_t R = s->adopted ? 0 : s->n_records, C = s->adopted ? 0 : s->n_cigar;
-    HIPCHK(s->s_tid.reserve(n_records, st, R)); HIPCHK(s->s_pos.reserve(n_records, st, R)); HIPCHK(s->s_flag.reserve(n_records, st, R));
-    HIPCHK(s->s_mapq.reserve(n_records, st, R)); HIPCHK(s->s_nmk.reserve(n_records, st, R)); HIPCHK(s->s_nm.reserve(n_records, st, R));
-    HIPCHK(s->s_lseq.reserve(n_records, st, R)); HIPCHK(s->s_coff.reserve(n_records + 1, st, R ? R + 1 : 0));
-    HIPCHK(s->s_cig.reserve(n_cigar + 1, st, C));
+    const uint64_t R = s->adopted ? 0 : s->store.n_records, C = s->adopted ? 0 : s->store.n_cigar;
+    HIPCHK(s->store.reserve(n_records, n_cigar + 1, s->stream, R, C, false));
     return COV_OK;
 }
 
@@ -1658,7 +1584,7 @@ cov_status cov_gather(cov_session *const *sessions, uint32_t n, uint32_t root) {
     }
     for (u32 i = 0; i < n; i++) {   // the record count of each rank travels in its block (a padding word of DevGlobal)
         HIPCHK(hipSetDevice(devs[i]));
-        const u64 nr = sessions[i]->merged_valid ? sessions[i]->merged_records : sessions[i]->n_records;
+        const u64 nr = sessions[i]->merged_valid ? sessions[i]->merged_records : sessions[i]->store.n_records;
         HIPCHK(hipMemcpyAsync(&sessions[i]->d_glob.p->pad2[0], &nr, 8, hipMemcpyHostToDevice, sessions[i]->stream));
         HIPCHK(hipStreamSynchronize(sessions[i]->stream));
     }
@@ -1754,12 +1680,7 @@ cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t 
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(ingest_prep_wait(s));
     if (!s->ing_copy) HIPCHK(ingest_prepare_(s));
-    if (s->adopted) {  // materialise an adopted device batch into the owned store first
-        cov_batch ab = s->adopted_batch;
-        s->adopted = false; s->n_records = 0; s->n_cigar = 0;
-        cov_status a = append(s, &ab, true);
-        if (a) return a;
-    }
+    { const cov_status a = materialise_adopted(s); if (a) return a; }
     HIPCHK(hipStreamSynchronize(s->stream));     // the record store is about to be written from the parse stream
     s->ing_batch = 0; s->ing_extracted = 0; s->ing_rec_total = s->ing_cig_total = 0; s->ing_fail = 0; s->ing_rec_spilled = 0;
     s->ing_K = choose_inflate_kernel(s);      // (also sets the kernel's dynamic-LDS limit on this session's device)
@@ -1800,10 +1721,51 @@ cov_status cov_ingest_span(cov_session *s, int64_t key_lo, int64_t key_hi, int s
     return COV_OK;
 }
 
+// One window of a running ingest, BGZF or SAM text — nrec records, ncig CIGAR words — asks for room behind what the store holds and what the
+// ingest has extracted so far (ing_rec_total / ing_cig_total: in the columns, not committed before the ingest ends).  `wr`: the stream that
+// writes the store in this ingest; scale > 0: the first of several windows, the whole file being `scale` times this one (store_plan_core.h).
+// Bounded store: if the window would pass a cap, what has been extracted becomes the store's content, the pipeline runs over it, the complete
+// contigs leave for the host and the contig in flight moves to the front; this window's records follow it.  past_limit: the window does not
+// fit 32-bit indices (the caller's to report); room: the columns take its records from R and its CIGAR words from Cg on.
+struct PartTimer { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); ~PartTimer() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } };
+struct Admitted { u64 R = 0, Cg = 0; bool past_limit = false, room = false; };
+static cov_status admit_window(cov_session *s, u64 nrec, u64 ncig, hipStream_t wr, double scale, Admitted &a) {
+    RecordStore &S = s->store;
+    a = Admitted{};
+    u64 R = S.n_records + s->ing_rec_total, Cg = S.n_cigar + s->ing_cig_total;
+    if (nrec && stplan::spill_first(R == 0, s->want_mates, s->ing_fail != 0, R + nrec > s->cap_records, Cg + ncig > s->cap_cigar)) {
+        if (wr != s->stream) HIPCHK(hipStreamSynchronize(wr));
+        HIPCHK(S.seal(R, Cg, s->stream));
+        s->ing_rec_spilled += s->ing_rec_total; s->ing_rec_total = 0; s->ing_cig_total = 0;
+        bool progress = false; const cov_status sp = spill_store(s, progress);
+        if (sp != COV_OK) return sp;
+        R = S.n_records; Cg = S.n_cigar;
+    }
+    a.R = R; a.Cg = Cg; a.past_limit = !s->ing_fail && (stplan::past_limit(R, nrec) || stplan::past_limit(Cg, ncig));
+    if (s->ing_fail || a.past_limit || !nrec) return COV_OK;
+    const u64 Nn = scale > 0 ? stplan::first_window_size(R, nrec, 0, scale, s->cap_records) : R + nrec;
+    const u64 Cn = scale > 0 ? stplan::first_window_size(Cg, ncig, 1, scale, s->cap_cigar) : Cg + ncig + 1;
+    PartTimer alloc{s->ing_s_alloc};
+    HIPCHK(S.reserve(Nn, Cn, wr, R, Cg, s->want_mates));
+    a.room = true;
+    return COV_OK;
+}
+
+// The end of an ingest: what it extracted becomes the store's content.
+static cov_status ingest_commit(cov_session *s) {
+    if (!s->ing_rec_total) return COV_OK;
+    RecordStore &S = s->store;
+    const u64 Nn = S.n_records + s->ing_rec_total;
+    const bool mates_cover = s->want_mates && S.mates_valid == S.n_records;      // the columns cover the whole store as long as every file came through here
+    HIPCHK(S.seal(Nn, S.n_cigar + s->ing_cig_total, s->stream));
+    if (mates_cover) S.mates_valid = Nn;
+    s->finished = false;
+    return COV_OK;
+}
+
 // Records of the windows whose boundaries are verified go into the store: all windows up to `must_upto` (waiting for their
 // k_bam_verify if need be), later ones only if their result is already here.
 static cov_status ingest_drain_(cov_session *s, int64_t must_upto);
-struct PartTimer { double &acc; std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now(); ~PartTimer() { acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); } };
 static cov_status ingest_drain(cov_session *s, int64_t must_upto) { PartTimer t{s->ing_s_part[0]}; covr::Range rr("ingest: verify + extract windows"); return ingest_drain_(s, must_upto); }
 static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
     hipStream_t ps = s->ing_ext;     // the host has seen the window's verification finish: nothing on the device to wait for
@@ -1818,46 +1780,16 @@ static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
         const bool span = s->ing_key_lo > 0 || s->ing_key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end;
         if (!span && (!s->want_mates || s->want_grouping)) st &= ~64u;       // whole file: cov_finish reports disorder in file order, beside the other per-record errors
         if (st && !s->ing_fail) { s->ing_fail = st; s->ing_fail_dbg[0] = res[4]; s->ing_fail_dbg[1] = res[5]; s->ing_fail_dbg[2] = res[6]; }
-        u64 R = s->n_records + s->ing_rec_total, Cg = s->n_cigar + s->ing_cig_total;
-        if (!s->ing_fail && nrec && R && !s->want_mates && (R + nrec > s->cap_records || Cg + ncig > s->cap_cigar)) {
-            // bounded store: what has been extracted so far becomes the store's content, the pipeline runs over it, the complete contigs
-            // leave for the host and the contig in flight moves to the front; this window's records follow it
-            HIPCHK(hipStreamSynchronize(ps));
-            const u32 end_off = (u32)Cg;
-            HIPCHK(hipMemcpyAsync(s->s_coff.p + R, &end_off, sizeof end_off, hipMemcpyHostToDevice, s->stream));
-            HIPCHK(hipStreamSynchronize(s->stream));
-            s->n_records = R; s->n_cigar = Cg;
-            s->ing_rec_spilled += s->ing_rec_total; s->ing_rec_total = 0; s->ing_cig_total = 0;
-            bool progress = false;
-            const cov_status sp = spill_store(s, progress);
-            if (sp != COV_OK) return sp;
-            R = s->n_records; Cg = s->n_cigar;
-        }
-        if (!s->ing_fail && (R + nrec >= 0xfffffff0ull || Cg + ncig >= 0xfffffff0ull)) s->ing_fail = 16u;
-        if (!s->ing_fail && nrec) {
-            u64 Nn = R + nrec, Cn = Cg + ncig + 1;
-            // first of several windows (it ends in front of the span's end): size the store for the whole file at once.  (Not "several
-            // windows launched so far": with a fast inflate kernel window 0 is verified before window 1 is launched, the store was then
-            // sized for one window, and every later window grew it — allocate, copy, drain the device, free: 0.8 s of stalls at 100 M reads,
-            // profiles/r04_timeline_store_regrowth.txt.)
-            if (w == 0 && s->ing_win[0].comp_end && s->ing_win[0].comp_end + 65536u < s->ing_span_hi) {
-                const double scale = (double)(s->ing_span_hi - s->ing_span_lo) / (double)std::max<u64>(1, s->ing_win[0].comp_end - std::min<u64>(s->ing_win[0].comp_end, s->ing_span_lo)) * 1.1;
-                Nn = std::max<u64>(Nn, R + (u64)((double)nrec * scale) + 1024); Cn = std::max<u64>(Cn, Cg + (u64)((double)ncig * scale) + 1024);
-                // (never beyond the store's cap: what would lie behind it is spilled before it is written)
-                Nn = std::max<u64>(R + nrec, std::min<u64>(Nn, std::min<u64>(s->cap_records + 1024, 0xfffffff0ull)));
-                Cn = std::max<u64>(Cg + ncig + 1, std::min<u64>(Cn, std::min<u64>(s->cap_cigar + 1024, 0xfffffff0ull)));
-            }
-            const auto ta0 = std::chrono::steady_clock::now();
-            HIPCHK(s->s_tid.reserve(Nn, ps, R)); HIPCHK(s->s_pos.reserve(Nn, ps, R)); HIPCHK(s->s_flag.reserve(Nn, ps, R));
-            HIPCHK(s->s_mapq.reserve(Nn, ps, R)); HIPCHK(s->s_nmk.reserve(Nn, ps, R)); HIPCHK(s->s_nm.reserve(Nn, ps, R));
-            HIPCHK(s->s_lseq.reserve(Nn, ps, R)); HIPCHK(s->s_coff.reserve(Nn + 1, ps, R + 1));
-            HIPCHK(s->s_cig.reserve(Cn, ps, Cg));
-            if (s->want_mates) { HIPCHK(s->s_mtid.reserve(Nn, ps, R)); HIPCHK(s->s_qh1.reserve(Nn, ps, R)); HIPCHK(s->s_qh2.reserve(Nn, ps, R)); }
-            s->ing_s_alloc += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta0).count();
+        // first of several windows (it ends in front of the span's end; not "several launched so far": window 0 may be verified before window 1 is launched)
+        double scale = 0;
+        if (w == 0 && s->ing_win[0].comp_end && s->ing_win[0].comp_end + 65536u < s->ing_span_hi)
+            scale = (double)(s->ing_span_hi - s->ing_span_lo) / (double)std::max<u64>(1, s->ing_win[0].comp_end - std::min<u64>(s->ing_win[0].comp_end, s->ing_span_lo)) * 1.1;
+        Admitted a; { const cov_status ad = admit_window(s, nrec, ncig, ps, scale, a); if (ad != COV_OK) return ad; }
+        if (a.past_limit) s->ing_fail = 16u;
+        if (a.room) {
             covi::RecStore RS{};
-            if (s->want_mates) { RS.mtid = s->s_mtid.p; RS.qh1 = s->s_qh1.p; RS.qh2 = s->s_qh2.p; }
-            RS.tid = s->s_tid.p; RS.pos = s->s_pos.p; RS.flag = s->s_flag.p; RS.mapq = s->s_mapq.p; RS.nm_kind = s->s_nmk.p; RS.nm = s->s_nm.p;
-            RS.l_seq = s->s_lseq.p; RS.cigar_off = s->s_coff.p; RS.cigar = s->s_cig.p; RS.rec0 = R; RS.cig0 = Cg;
+            s->store.view(RS); RS.rec0 = a.R; RS.cig0 = a.Cg;
+            if (s->want_mates) s->store.view_mates(RS);
             covi::BamScan S{};
             S.u = s->g_win[w % 3u].p; S.N = s->ing_win[q].N; S.p0 = s->g_result.p + 6; S.seg_bytes = 32768; S.n_seg = s->ing_win[q].n_seg;
             S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = 0; S.key_lo = s->ing_key_lo; S.key_hi = s->ing_key_hi; S.search_first = 0;
@@ -2156,15 +2088,7 @@ static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out) {
         const bool seen_beyond = ((glob[7] >> 63) && (long long)(u32)glob[7] >= s->ing_key_hi) || (s->ing_tail_key != ~0ull && (long long)s->ing_tail_key >= s->ing_key_hi);
         if (!seen_beyond) { s->err = "device ingest: the bytes fed for this span end before a record of the next span (handing the span to the CPU reader)"; return COV_ERR_INGEST_FALLBACK; }
     }
-    if (s->ing_rec_total) {
-        const u64 Nn = s->n_records + s->ing_rec_total, Cn = s->n_cigar + s->ing_cig_total;
-        const u32 end_off = (u32)Cn;
-        HIPCHK(hipMemcpyAsync(s->s_coff.p + Nn, &end_off, sizeof end_off, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->want_mates && s->mates_valid == s->n_records) s->mates_valid = Nn;     // the columns cover the whole store as long as every file came through here
-        s->n_records = Nn; s->n_cigar = Cn;
-        s->finished = false;
-    }
+    { const cov_status c = ingest_commit(s); if (c != COV_OK) return c; }
     if (n_records_out) *n_records_out = s->ing_rec_total;
     return COV_OK;
 }
@@ -2194,12 +2118,7 @@ cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t 
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(ingest_prep_wait(s));
     if (!s->ing_copy) HIPCHK(ingest_prepare_(s));
-    if (s->adopted) {  // materialise an adopted device batch into the owned store first
-        cov_batch ab = s->adopted_batch;
-        s->adopted = false; s->n_records = 0; s->n_cigar = 0;
-        cov_status a = append(s, &ab, true);
-        if (a) return a;
-    }
+    { const cov_status a = materialise_adopted(s); if (a) return a; }
     hipStream_t st = s->stream;
     HIPCHK(hipStreamSynchronize(st));
     u64 W = 32ull << 20;
@@ -2304,40 +2223,17 @@ cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64
     }
     if (nrec) s->sam_seen_record = true;
     s->sam_lines += n_lines; s->sam_bytes += n_bytes;
-    u64 R = s->n_records + s->ing_rec_total, Cg = s->n_cigar + s->ing_cig_total;
-    if (nrec && R && !s->want_mates && (R + nrec > s->cap_records || Cg + ncig > s->cap_cigar)) {
-        // bounded store, as ingest_drain does it: what has been decoded so far becomes the store's content, the complete contigs leave
-        // for the host, the contig in flight moves to the front; this window's records follow it
-        const u32 end_off = (u32)Cg;
-        HIPCHK(hipMemcpyAsync(s->s_coff.p + R, &end_off, sizeof end_off, hipMemcpyHostToDevice, st));
-        HIPCHK(hipStreamSynchronize(st));
-        s->n_records = R; s->n_cigar = Cg;
-        s->ing_rec_spilled += s->ing_rec_total; s->ing_rec_total = 0; s->ing_cig_total = 0;
-        bool progress = false;
-        const cov_status sp = spill_store(s, progress);
-        if (sp != COV_OK) return sp;
-        R = s->n_records; Cg = s->n_cigar;
-    }
-    if (R + nrec >= 0xfffffff0ull || Cg + ncig >= 0xfffffff0ull) {
+    // first of several windows of a file whose size is known: the store is sized once
+    const double scale = s->sam_k == 0 && s->sam_expected > n_bytes ? (double)s->sam_expected / (double)n_bytes * 1.1 : 0;
+    Admitted a; { const cov_status ad = admit_window(s, nrec, ncig, st, scale, a); if (ad != COV_OK) return ad; }
+    if (a.past_limit) {
         (void)cov_ingest_abort(s);
         s->err = "more than 2^32 records or CIGAR words of one reference in the record store"; return COV_ERR_INVALID_ARG;
     }
-    if (nrec) {
-        u64 Nn = R + nrec, Cn = Cg + ncig + 1;
-        if (s->sam_k == 0 && s->sam_expected > n_bytes) {      // first of several windows of a file whose size is known: size the store once
-            const double scale = (double)s->sam_expected / (double)n_bytes * 1.1;
-            Nn = std::max<u64>(Nn, std::min<u64>(R + (u64)((double)nrec * scale) + 1024, std::min<u64>(s->cap_records + 1024, 0xfffffff0ull)));
-            Cn = std::max<u64>(Cn, std::min<u64>(Cg + (u64)((double)ncig * scale) + 1024, std::min<u64>(s->cap_cigar + 1024, 0xfffffff0ull)));
-        }
-        HIPCHK(s->s_tid.reserve(Nn, st, R)); HIPCHK(s->s_pos.reserve(Nn, st, R)); HIPCHK(s->s_flag.reserve(Nn, st, R));
-        HIPCHK(s->s_mapq.reserve(Nn, st, R)); HIPCHK(s->s_nmk.reserve(Nn, st, R)); HIPCHK(s->s_nm.reserve(Nn, st, R));
-        HIPCHK(s->s_lseq.reserve(Nn, st, R)); HIPCHK(s->s_coff.reserve(Nn + 1, st, R + 1));
-        HIPCHK(s->s_cig.reserve(Cn, st, Cg));
-        if (s->want_mates) { HIPCHK(s->s_mtid.reserve(Nn, st, R)); HIPCHK(s->s_qh1.reserve(Nn, st, R)); HIPCHK(s->s_qh2.reserve(Nn, st, R)); }
+    if (a.room) {
         covs::Out O{};
-        O.tid = s->s_tid.p; O.pos = s->s_pos.p; O.flag = s->s_flag.p; O.mapq = s->s_mapq.p; O.nm_kind = s->s_nmk.p; O.nm = s->s_nm.p;
-        O.l_seq = s->s_lseq.p; O.cigar_off = s->s_coff.p; O.cigar = s->s_cig.p; O.rec0 = R; O.cig0 = Cg;
-        if (s->want_mates) { O.mtid = s->s_mtid.p; O.qh1 = s->s_qh1.p; O.qh2 = s->s_qh2.p; }
+        s->store.view(O); O.rec0 = a.R; O.cig0 = a.Cg;
+        if (s->want_mates) s->store.view_mates(O);
         HIPCHK(hipEventRecord(s->sam_ev[2], st));
         hipLaunchKernelGGL(covs::k_sam_decode, dim3((n_lines + 255u) / 256u), dim3(256), 0, st, L, (const u32 *)s->m_cnt.p, (const u32 *)s->m_rec_idx.p, (const u32 *)s->m_cig_idx.p, s->m_names, O);
         HIPCHK(hipGetLastError());
@@ -2362,15 +2258,7 @@ cov_status cov_sam_end(cov_session *s, uint64_t *n_records_out) {
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] sam: device SAM decode: %llu bytes in %u windows of %llu, %llu lines, %llu records, kernels %.3f ms\n", (unsigned long long)s->sam_bytes, s->sam_k,
                 (unsigned long long)s->sam_window, (unsigned long long)s->sam_lines, (unsigned long long)(s->ing_rec_total + s->ing_rec_spilled), s->sam_ms);
-    if (s->ing_rec_total) {
-        const u64 Nn = s->n_records + s->ing_rec_total, Cn = s->n_cigar + s->ing_cig_total;
-        const u32 end_off = (u32)Cn;
-        HIPCHK(hipMemcpyAsync(s->s_coff.p + Nn, &end_off, sizeof end_off, hipMemcpyHostToDevice, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if (s->want_mates && s->mates_valid == s->n_records) s->mates_valid = Nn;
-        s->n_records = Nn; s->n_cigar = Cn;
-        s->finished = false;
-    }
+    { const cov_status c = ingest_commit(s); if (c != COV_OK) return c; }
     if (n_records_out) *n_records_out = s->ing_rec_total + s->ing_rec_spilled;
     return COV_OK;
 }
@@ -2396,40 +2284,28 @@ static_assert(sizeof(cov_pair_filter) == sizeof(covp::PairFilter) && offsetof(co
 static cov_status gather_store(cov_session *s, const u32 *order, u32 S, bool with_mates) {
     hipStream_t st = s->stream;
     DevBuf<u32> d_bsum; DevBuf<u64> d_tot;
-    DevBuf<int32_t> n_tid, n_pos, n_mtid; DevBuf<uint16_t> n_flag; DevBuf<uint8_t> n_mapq, n_nmk; DevBuf<u32> n_nm, n_lseq, n_coff, n_cig, n_qh2; DevBuf<u64> n_qh1;
-    struct Rel { std::function<void()> f; ~Rel() { f(); } } rel{[&] {      // (after the swap below: the old store)
-        n_tid.release(); n_pos.release(); n_mtid.release(); n_flag.release(); n_mapq.release(); n_nmk.release(); n_nm.release(); n_lseq.release(); n_coff.release(); n_cig.release();
-        n_qh1.release(); n_qh2.release(); d_bsum.release(); d_tot.release(); }};
+    struct Rel { DevBuf<u32> &a; DevBuf<u64> &b; ~Rel() { a.release(); b.release(); } } rel{d_bsum, d_tot};
+    RecordStore sel;      // (after the swap below: the old store, which goes with it)
     const u32 nb = (S + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
     HIPCHK(d_bsum.reserve((size_t)nb + 1, st)); HIPCHK(d_tot.reserve(1, st));
-    const covp::SelCigarLen clen{order, s->s_coff.p};
+    const covp::SelCigarLen clen{order, s->store.cigar_off.p};
     hipLaunchKernelGGL((covp::k_scan_sums<covp::SelCigarLen>), dim3(nb), dim3(256), 0, st, clen, S, d_bsum.p);
     hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_tot.p);
     HIPCHK(hipGetLastError());
     u64 n_cig_sel = 0;
     HIPCHK(hipMemcpyAsync(&n_cig_sel, d_tot.p, sizeof n_cig_sel, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    HIPCHK(n_tid.reserve(S, st)); HIPCHK(n_pos.reserve(S, st)); HIPCHK(n_flag.reserve(S, st)); HIPCHK(n_mapq.reserve(S, st)); HIPCHK(n_nmk.reserve(S, st));
-    HIPCHK(n_nm.reserve(S, st)); HIPCHK(n_lseq.reserve(S, st)); HIPCHK(n_coff.reserve((size_t)S + 1, st)); HIPCHK(n_cig.reserve((size_t)n_cig_sel + 1, st));
-    covp::SelGather G{};
-    G.order = order;
-    G.src = covp::Store{s->s_tid.p, s->s_pos.p, s->s_flag.p, s->s_mapq.p, s->s_nmk.p, s->s_nm.p, s->s_lseq.p, s->s_coff.p, s->s_cig.p};
-    G.dst = covp::Store{n_tid.p, n_pos.p, n_flag.p, n_mapq.p, n_nmk.p, n_nm.p, n_lseq.p, n_coff.p, n_cig.p};
+    HIPCHK(sel.reserve(S, (size_t)n_cig_sel + 1, st, 0, 0, with_mates));
+    covp::SelGather G{}; G.order = order; s->store.view(G.src); sel.view(G.dst);
     hipLaunchKernelGGL((covp::k_scan_apply<covp::SelCigarLen, covp::SelGather>), dim3(nb), dim3(256), 0, st, clen, G, S, (const u32 *)d_bsum.p);
     HIPCHK(hipGetLastError());
     if (with_mates) {
-        HIPCHK(n_mtid.reserve(S, st)); HIPCHK(n_qh1.reserve(S, st)); HIPCHK(n_qh2.reserve(S, st));
-        hipLaunchKernelGGL(covg::k_group_gather_mates, dim3((S + 255u) / 256u), dim3(256), 0, st, order, S, (const int32_t *)s->s_mtid.p, (const u64 *)s->s_qh1.p, (const u32 *)s->s_qh2.p,
-                           n_mtid.p, n_qh1.p, n_qh2.p);
+        hipLaunchKernelGGL(covg::k_group_gather_mates, dim3((S + 255u) / 256u), dim3(256), 0, st, order, S, (const int32_t *)s->store.mtid.p, (const u64 *)s->store.qh1.p, (const u32 *)s->store.qh2.p,
+                           sel.mtid.p, sel.qh1.p, sel.qh2.p);
         HIPCHK(hipGetLastError());
     }
-    const u32 end_off = (u32)n_cig_sel;
-    HIPCHK(hipMemcpyAsync(n_coff.p + S, &end_off, sizeof end_off, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    std::swap(s->s_tid, n_tid); std::swap(s->s_pos, n_pos); std::swap(s->s_flag, n_flag); std::swap(s->s_mapq, n_mapq); std::swap(s->s_nmk, n_nmk);
-    std::swap(s->s_nm, n_nm); std::swap(s->s_lseq, n_lseq); std::swap(s->s_coff, n_coff); std::swap(s->s_cig, n_cig);
-    if (with_mates) { std::swap(s->s_mtid, n_mtid); std::swap(s->s_qh1, n_qh1); std::swap(s->s_qh2, n_qh2); }
-    s->n_records = S; s->n_cigar = n_cig_sel;
+    HIPCHK(sel.seal(S, n_cig_sel, st));
+    s->store.swap(sel, with_mates);
     return COV_OK;
 }
 
@@ -2438,17 +2314,16 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     covr::Range rr("pair filter (cov_pair_filter_apply)");
     if (s->adopted || s->ing_active) { s->err = "cov_pair_filter_apply: needs the session's own record store, filled by the device ingest"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_pair_filter_apply: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
-    if (s->mates_valid != s->n_records) { s->err = "cov_pair_filter_apply: the store holds records without mate columns (cov_ingest_want_mates before every ingest, no cov_push_batch)"; return COV_ERR_STATE; }
+    if (s->store.mates_valid != s->store.n_records) { s->err = "cov_pair_filter_apply: the store holds records without mate columns (cov_ingest_want_mates before every ingest, no cov_push_batch)"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
     hipStream_t st = s->stream;
-    const u32 R = (u32)s->n_records;
+    const u32 R = (u32)s->store.n_records;
     if (n_selected) *n_selected = 0;
     if (n_primary) *n_primary = 0;
     s->finished = false; s->depth_all_valid = false;
     if (R == 0) return COV_OK;
     covp::PairCols C{};
-    C.tid = s->s_tid.p; C.flag = s->s_flag.p; C.mapq = s->s_mapq.p; C.nm_kind = s->s_nmk.p; C.nm = s->s_nm.p; C.l_seq = s->s_lseq.p;
-    C.cigar_off = s->s_coff.p; C.cigar = s->s_cig.p; C.mtid = s->s_mtid.p; C.qh1 = s->s_qh1.p; C.qh2 = s->s_qh2.p;
+    s->store.view_unplaced(C); s->store.view_mates(C);
     covp::PairFilter F; memcpy(&F, f, sizeof F);
     // chunks of whole references (a pair never spans two), about T records each: the table of a chunk stays small enough for the
     // last-level cache, where the scattered atomics of the join are served
@@ -2466,8 +2341,8 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     HIPCHK(hipMemcpyAsync(d_w.p, w_init, sizeof w_init, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(d_cnt.p, 0, ((size_t)n_chunks + 2) * sizeof(u32), st));
     HIPCHK(hipMemsetAsync(d_partner.p, 0xff, (size_t)R * sizeof(u32), st));
-    hipLaunchKernelGGL(covp::k_count_primary, dim3(std::min<u32>((R + 255u) / 256u, 4096u)), dim3(256), 0, st, (const uint16_t *)s->s_flag.p, R, d_w.p);
-    hipLaunchKernelGGL(covp::k_pair_cuts, dim3((n_chunks + 1 + 255) / 256), dim3(256), 0, st, (const int32_t *)s->s_tid.p, R, T, n_chunks, d_cuts.p);
+    hipLaunchKernelGGL(covp::k_count_primary, dim3(std::min<u32>((R + 255u) / 256u, 4096u)), dim3(256), 0, st, (const uint16_t *)s->store.flag.p, R, d_w.p);
+    hipLaunchKernelGGL(covp::k_pair_cuts, dim3((n_chunks + 1 + 255) / 256), dim3(256), 0, st, (const int32_t *)s->store.tid.p, R, T, n_chunks, d_cuts.p);
     HIPCHK(hipGetLastError());
     std::vector<u32> cuts((size_t)n_chunks + 1);
     HIPCHK(hipMemcpyAsync(cuts.data(), d_cuts.p, cuts.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
@@ -2565,7 +2440,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     const u64 n_sel = hw[2];
     if (n_primary) *n_primary = hw[0];
     if (n_selected) *n_selected = n_sel;
-    if (n_sel == 0) { s->n_records = 0; s->n_cigar = 0; s->mates_valid = 0; return COV_OK; }
+    if (n_sel == 0) { s->store.n_records = 0; s->store.n_cigar = 0; s->store.mates_valid = 0; return COV_OK; }
     const u32 S = (u32)n_sel;
     HIPCHK(d_order.reserve(S, st));
     const covp::PairEmit emit{d_partner.p, d_order.p};
@@ -2573,7 +2448,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     // ---- the selected store: CIGAR offsets by a second scan, whose consumer moves the records
     HIPCHK(hipGetLastError());
     { const cov_status g = gather_store(s, d_order.p, S, false); if (g != COV_OK) return g; }
-    s->mates_valid = 0;      // the mate columns still describe the unselected store: spent
+    s->store.mates_valid = 0;      // the mate columns still describe the unselected store: spent
     return COV_OK;
 }
 
@@ -2589,11 +2464,11 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
     hipStream_t st = s->stream;
-    const u32 R = (u32)s->n_records, nT = s->n_targets;
+    const u32 R = (u32)s->store.n_records, nT = s->n_targets;
     for (float &m : s->grp_ms) m = 0.f;
     s->grp_launches = 0;
     if (R < 2) return COV_OK;
-    const bool mates = s->mates_valid == s->n_records && s->mates_valid != 0;
+    const bool mates = s->store.mates_valid == s->store.n_records && s->store.mates_valid != 0;
     hipEvent_t *ev = s->ev[COV_K_GROUP];      // [0] begin, [1] end; the split: events of its own (a few per sample)
     hipEvent_t ev_mid[2] = {nullptr, nullptr};
     DevBuf<u32> d_flag, d_hist, d_key[2], d_idx[2]; DevBuf<u64> d_cnt;
@@ -2607,7 +2482,7 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
     HIPCHK(d_flag.reserve(1, st));
     HIPCHK(hipMemsetAsync(d_flag.p, 0, sizeof(u32), st));
     HIPCHK(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL(covg::k_group_check, dim3(std::min<u32>((R + 255u) / 256u, 8192u)), dim3(256), 0, st, (const int32_t *)s->s_tid.p, R, nT, d_flag.p);
+    hipLaunchKernelGGL(covg::k_group_check, dim3(std::min<u32>((R + 255u) / 256u, 8192u)), dim3(256), 0, st, (const int32_t *)s->store.tid.p, R, nT, d_flag.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev_mid[0], st));
     s->grp_launches++;
@@ -2627,7 +2502,7 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
     if (P > 1) { HIPCHK(d_key[0].reserve(R, st)); HIPCHK(d_idx[1].reserve(R, st)); }
     if (P > 2) HIPCHK(d_key[1].reserve(R, st));
     HIPCHK(hipMemsetAsync(d_cnt.p, 0, 2 * sizeof(u64), st));
-    const int32_t *tid = s->s_tid.p;
+    const int32_t *tid = s->store.tid.p;
     for (u32 p = 0; p < P; p++) {
         const bool first = p == 0, last = p + 1 == P;
         const u32 *key_in = first ? nullptr : d_key[(p - 1) & 1u].p, *idx_in = first ? nullptr : d_idx[(p - 1) & 1u].p;
@@ -2673,23 +2548,11 @@ cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_r
     if (!s || s->adopted) return COV_ERR_STATE;
     if (s->spill.active) { s->err = "cov_copy_records: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
-    if (n_records) *n_records = s->n_records;
-    if (n_cigar) *n_cigar = s->n_cigar;
+    if (n_records) *n_records = s->store.n_records;
+    if (n_cigar) *n_cigar = s->store.n_cigar;
     if (!host) return COV_OK;
-    const uint64_t n = s->n_records;
-    hipStream_t st = s->stream;
-    if (n) {
-        HIPCHK(hipMemcpyAsync((void *)host->tid, s->s_tid.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->pos, s->s_pos.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->flag, s->s_flag.p, n * 2, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->mapq, s->s_mapq.p, n, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->nm, s->s_nm.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->nm_kind, s->s_nmk.p, n, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->l_seq, s->s_lseq.p, n * 4, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync((void *)host->cigar_off, s->s_coff.p, (n + 1) * 4, hipMemcpyDeviceToHost, st));
-        if (s->n_cigar) HIPCHK(hipMemcpyAsync((void *)host->cigar, s->s_cig.p, s->n_cigar * 4, hipMemcpyDeviceToHost, st));
-    }
-    HIPCHK(hipStreamSynchronize(st));
+    HIPCHK(s->store.copy_out(*host, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
     return COV_OK;
 }
 
@@ -2697,14 +2560,10 @@ cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_r
 cov_status cov_copy_mates(cov_session *s, int32_t *mtid, uint64_t *qh1, uint32_t *qh2) {
     if (!s || s->adopted || !mtid || !qh1 || !qh2) return COV_ERR_STATE;
     if (s->spill.active) { s->err = "cov_copy_mates: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
-    const uint64_t n = s->n_records;
-    if (!s->want_mates || (n && (!s->s_mtid.p || !s->s_qh1.p || !s->s_qh2.p))) { s->err = "cov_copy_mates: the records were not ingested with cov_ingest_want_mates"; return COV_ERR_STATE; }
+    const uint64_t n = s->store.n_records;
+    if (!s->want_mates || (n && !s->store.mtid.p)) { s->err = "cov_copy_mates: the records were not ingested with cov_ingest_want_mates"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
-    if (n) {
-        HIPCHK(hipMemcpyAsync(mtid, s->s_mtid.p, n * 4, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipMemcpyAsync(qh1, s->s_qh1.p, n * 8, hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipMemcpyAsync(qh2, s->s_qh2.p, n * 4, hipMemcpyDeviceToHost, s->stream));
-    }
+    HIPCHK(s->store.copy_mates_out(mtid, qh1, qh2, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     return COV_OK;
 }
@@ -2818,7 +2677,7 @@ cov_status cov_interval_stats_compute(cov_session *s, const cov_interval *iv, ui
         HIPCHK(hipMemcpyAsync(s->d_depth_off.p, off.data(), off.size() * 8, hipMemcpyHostToDevice, st));
         HIPCHK(s->d_depth_all.reserve(std::max<size_t>(1, off.back()), st));
         HIPCHK(hipMemsetAsync(s->d_depth_all.p, 0, (size_t)off.back() * 4, st));
-        if (s->n_records && s->n_tiles) {
+        if (s->store.n_records && s->n_tiles) {
             PileupArgs a = pileup_args(s);
             HIPCHK(s->d_ctg_scratch.reserve(s->n_targets, st));   // the accumulated statistics must stay as they are
             HIPCHK(hipMemcpyAsync(s->d_ctg_scratch.p, s->d_ctg.p, (size_t)s->n_targets * sizeof(DevContig), hipMemcpyDeviceToDevice, st));
