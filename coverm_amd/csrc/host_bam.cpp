@@ -44,6 +44,8 @@
 #include "reader_filter.h"
 #include "roctx_ranges.h"
 #include "knobs.h"
+#include "bgzf_walk_core.h"
+#include "slot_ring.h"
 
 namespace {
 
@@ -101,6 +103,9 @@ struct Bam {
     bool want_names = false;
 };
 
+inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// the text of an error into the caller's buffer (cut to fit); -> rc
+inline int put_err(char *err, size_t errcap, int rc, const std::string &m) { if (err && errcap) snprintf(err, errcap, "%s", m.c_str()); return rc; }
 inline uint32_t rd32(const uint8_t *p) { uint32_t v; memcpy(&v, p, 4); return v; }
 inline uint16_t rd16(const uint8_t *p) { uint16_t v; memcpy(&v, p, 2); return v; }
 
@@ -872,18 +877,17 @@ struct Stream {
         std::vector<uint8_t> cbuf(window_comp + (256u << 10));
         size_t left = 0; uint64_t fpos = start_off;
         std::vector<Blk> blocks;
-        auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         for (;;) {
             StreamWindow *w = nullptr;
             {
-                const double t0 = now();
+                const double t0 = now_s();
                 std::unique_lock<std::mutex> lk(m);
                 cv.wait(lk, [&] { return stop || !win_free.empty(); });
                 if (stop) break;
                 w = win_free.front(); win_free.pop_front();
-                t_wait_i += now() - t0;
+                t_wait_i += now_s() - t0;
             }
-            const double t0 = now();
+            const double t0 = now_s();
             size_t got = 0;
             while (got < window_comp) {
                 const ssize_t r = pread(fd, cbuf.data() + left + got, window_comp - got, (off_t)(fpos + got));
@@ -899,7 +903,7 @@ struct Stream {
             std::string e;
             if (!bgzf_block_table(cbuf.data(), n, p, blocks, total, !eof, e)) { fail(e); return; }
             if (!eof && blocks.empty() && n > (128u << 10)) { fail("BGZF block larger than 64 KiB"); return; }
-            const double t1 = now();
+            const double t1 = now_s();
             w->len = 0;
             if (!w->reserve(1u << 20, total, false)) { fail("out of memory"); return; }
             std::atomic<bool> ok{true};
@@ -911,7 +915,7 @@ struct Stream {
             left = n - p;
             if (left) memmove(cbuf.data(), cbuf.data() + p, left);
             if (cbuf.size() < left + window_comp) cbuf.resize(left + window_comp);
-            t_read += t1 - t0; t_inflate += now() - t1;
+            t_read += t1 - t0; t_inflate += now_s() - t1;
             account();
             { std::lock_guard<std::mutex> lk(m); win_full.push_back(w); }
             cv.notify_all();
@@ -926,21 +930,20 @@ struct Stream {
         bool header_done = mid_start, need_start = mid_start, finished = false;
         int64_t span_last_key = -1;
         RecVec<size_t> rec;
-        auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
         auto pfor = [&](size_t n, auto fn) { pool_p->run(n, fn); };
         const int32_t n_ref = (int32_t)names.size();
         while (!finished) {
             StreamWindow *w = nullptr;
             {
-                const double t0 = now();
+                const double t0 = now_s();
                 std::unique_lock<std::mutex> lk(m);
                 cv.wait(lk, [&] { return stop || !win_full.empty() || i_done; });
                 if (stop) break;
                 if (win_full.empty()) break;   // inflate side ended without a `last` window: only after an error
                 w = win_full.front(); win_full.pop_front();
-                t_wait_p += now() - t0;
+                t_wait_p += now_s() - t0;
             }
-            const double t0 = now();
+            const double t0 = now_s();
             const size_t c = carry.size();
             if (c > w->head && !w->reserve(c + (c >> 2), w->len, true)) { fail("out of memory"); return; }
             uint8_t *base = w->buf + w->head - c;
@@ -992,12 +995,12 @@ struct Stream {
             StreamBatch *b = nullptr;
             if (i1 > i0) {
                 {
-                    const double tw = now();
+                    const double tw = now_s();
                     std::unique_lock<std::mutex> lk(m);
                     cv.wait(lk, [&] { return stop || !bat_free.empty(); });
                     if (stop) break;
                     b = bat_free.front(); bat_free.pop_front();
-                    t_wait_p += now() - tw;
+                    t_wait_p += now_s() - tw;
                 }
                 const size_t R = i1 - i0;
                 if (!b->ensure_rec(R)) { fail("out of memory"); return; }
@@ -1019,7 +1022,7 @@ struct Stream {
             }
             carry.assign(base + end, base + N);
             if (last) finished = true;
-            t_parse += now() - t0;
+            t_parse += now_s() - t0;
             account();
             {
                 std::lock_guard<std::mutex> lk(m);
@@ -1092,10 +1095,8 @@ uint64_t find_block_start(int fd, uint64_t file_size, uint64_t off) {
         if (r < 28) return (uint64_t)-1;
         const size_t n = (size_t)r;
         for (size_t q = 0; q + 18 <= n; q++) {
-            if (c[q] != 0x1f || c[q + 1] != 0x8b || c[q + 2] != 8 || c[q + 3] != 4) continue;
-            if (rd16(&c[q + 10]) != 6 || c[q + 12] != 66 || c[q + 13] != 67 || rd16(&c[q + 14]) != 2) continue;
-            const size_t bsize = (size_t)rd16(&c[q + 16]) + 1;
-            if (bsize < 26) continue;
+            if (bgzfw::classify(&c[q], false) != bgzfw::ORDINARY) continue;
+            const size_t bsize = bgzfw::bsize_of(&c[q]);
             if (off + q + bsize == file_size) return off + q;
             if (q + bsize + 4 <= n && c[q + bsize] == 0x1f && c[q + bsize + 1] == 0x8b && c[q + bsize + 2] == 8 && c[q + bsize + 3] == 4) return off + q;
         }
@@ -1242,9 +1243,6 @@ void covh_bam_stream_close(covh_bam_stream *h) { delete h; }
 
 }  // extern "C"
 
-namespace {
-}  // namespace
-
 // ---------------------------------------------------------------------------------------------- device ingest driver
 // Host side of cov_ingest_*: reads the file into two alternating page-locked buffers (parallel pread), hops the BGZF block
 // headers of every piece (18 bytes per block; a header or a block may straddle two pieces) and feeds bytes + completed
@@ -1296,10 +1294,14 @@ const char *covh_bam_header_target_name(const covh_bam_header *h, uint32_t i) { 
 uint64_t covh_bam_header_target_len(const covh_bam_header *h, uint32_t i) { return h->h.lens[i]; }
 uint64_t covh_bam_header_first_record(const covh_bam_header *h) { return h->h.first_record; }
 
+}  // extern "C"
+
+namespace {
+
 // Bytes into a page-locked staging slot with non-temporal stores: the destination's lines are not read for ownership and do not stay in
 // the caches (the next reader of them is the DMA engine).  dst 16-byte aligned (a slot is page-aligned, chunks are multiples of 512 KiB);
 // src anywhere (a tid span starts at a block, not at a page).
-static void stream_copy(uint8_t *dst, const uint8_t *src, size_t n) {
+void stream_copy(uint8_t *dst, const uint8_t *src, size_t n) {
     size_t o = 0;
     if (((uintptr_t)dst & 15u) == 0) {
         for (; o + 64 <= n; o += 64) {
@@ -1313,353 +1315,347 @@ static void stream_copy(uint8_t *dst, const uint8_t *src, size_t n) {
     _mm_sfence();      // before the piece is announced: the upload that reads the slot is enqueued by another thread
 }
 
+// What one tid span feeds (same span definition as covh_bam_stream_open: boundaries one past the tid found at k / count of the file): the
+// bytes [f_lo, size) run from the BGZF block at the span's probe point to a margin behind the first block that begins with a record of a
+// later span (found by bisection over file offsets: the keys are sorted); the device drops the records of the neighbouring spans, whose
+// keys lie outside [key_lo, key_hi), at both ends.  first_record: where the records begin in the inflated stream (0 = to be searched).
+struct FeedRange {
+    uint64_t f_lo = 0, size = 0;
+    int64_t key_lo = 0, key_hi = KEY_INF + 1;
+    uint64_t first_record = 0;
+    bool empty = false;      // nothing to read
+};
+FeedRange span_feed_range(int fd, const HeaderOnly &h, uint32_t span_index, uint32_t span_count) {
+    FeedRange r;
+    r.size = h.file_size; r.first_record = h.first_record;
+    if (span_count <= 1) return r;
+    const uint64_t file_size = h.file_size;
+    const int32_t n_ref = (int32_t)h.names.size();
+    std::vector<int64_t> B; std::vector<uint64_t> boff;
+    span_boundaries(fd, file_size, span_count, n_ref, h.lens.data(), B, boff);
+    r.key_lo = B[span_index]; r.key_hi = B[span_index + 1];
+    if (span_index > 0) {
+        if (boff[span_index] == (uint64_t)-1 || r.key_lo >= r.key_hi) { r.empty = true; return r; }
+        r.f_lo = boff[span_index]; r.first_record = 0;
+    } else if (r.key_hi <= 0) { r.empty = true; return r; }
+    if (span_index + 1 < span_count && boff[span_index + 1] != (uint64_t)-1) {
+        // smallest offset from which the first record found has a key >= key_hi
+        uint64_t lo = boff[span_index + 1], hi = file_size;
+        bool decided = true;
+        while (hi - lo > 65536 && decided) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            uint64_t bo = 0;
+            const int64_t key = probe_key(fd, file_size, mid, n_ref, h.lens.data(), &bo);
+            if (key == PROBE_FAILED) decided = false;        // not "beyond the span": feed up to the end of the file instead
+            else if (key >= r.key_hi) hi = mid; else lo = mid;
+        }
+        // every record of this span starts before that point and may run on for up to the carry size of the device ingest
+        const uint64_t want = hi + ((uint64_t)17 << 20);
+        if (decided && want < file_size) { const uint64_t e = find_block_start(fd, file_size, want); if (e != (uint64_t)-1) r.size = e; }
+    }
+    return r;
+}
+
+// Where the pieces of [f_lo, size) come from, and the memory the DMA engine reads them in.  COVERM_INGEST_IO = pread | mmap | mmap-upfront:
+//   pread staging slots in page-locked memory filled by threaded preads;
+//   mmap  the file is mapped and its pages are registered with the device piece by piece, ahead of the uploads, so that the
+//         bytes go from the page cache to HBM with no copy by the CPU.  Alone on an idle device this reaches the link's rate
+//         (tools/ubench/io_probe: 57 GB/s against 42-54 GB/s through staging slots), but inside the running pipeline
+//         hipHostRegister drops to ~20 GB/s, the copies take longer to enqueue and unregistering 20 GB at the end costs
+//         another 0.4 s (profiles/r03_io_modes.log: 200 M reads 1.78 s against 0.98 s): kept as an option, not the default.
+//   More than two devices fed at once (covh_bam_set_concurrent_feeders; coverm-amd --devices): until round 6 the mapping, registered up
+//   front, was the default there, on a model (a staged byte crosses the host's memory three times, a mapped one once).  Measured with eight
+//   feeders on the one-GPU box (profiles/r06_eight_feeders_io.json): the eight registrations do NOT run beside one another — 0.2 to 1.2 s
+//   per 2.6 GB span, 20.6 GB in ~1.2 s all told = 17 GB/s for the process —, which alone is longer than the whole single-device run
+//   (0.76-0.96 s), while eight staged readers under the same 16-CPU quota copy at the one reader's rate (~49 GB/s in aggregate).  The
+//   staging slots are therefore the default for any number of feeders; COVERM_INGEST_IO=mmap-upfront | mmap remain as options.
+//   How the staging slots are FILLED (round 6, tools/ubench/copy_probe, profiles/r06_copy_probe.log): the feed was bound by the host's
+//   memory system — 14 threads pread at 80-88 GB/s alone, but beside them the DMA out of the slots falls from 58 to 37-52 GB/s (pread's
+//   copy_to_user reads the source, reads the destination lines for ownership and writes them; the DMA reads them once more), and the
+//   pipeline settles where both run at ~50 GB/s.  Copying from a MAPPING of the file with non-temporal stores (no read for ownership,
+//   nothing of the destination left in the caches) runs at 99-102 GB/s and leaves the DMA its 58-60 GB/s; zapping every chunk's pages
+//   behind the copy (74-83 GB/s; a 20 GB mapping's page tables would otherwise cost ~0.4 s when the process ends) still does.  That is
+//   the default; COVERM_INGEST_IO=pread keeps the preads (and is what a refused mapping falls back to).
+// Its destructor is every way out of the ingest: it first gives up whatever is still queued on the device (no-op once cov_ingest_end has
+// run), and only then parks the staging slots / unregisters the mapping: an upload may still be reading them, and an extraction still
+// writing the store the CPU reader is about to push into.
+struct PieceSource {
+    static constexpr int NS = COV_INGEST_SLOTS;
+    static constexpr uint64_t PG = 4096, ZPART = 4ull << 20;
+    cov_session *const s; const int fd; const std::string path; const uint64_t file_size, f_lo, size;
+    bool use_map, map_upfront, copy_map;
+    uint8_t *map = nullptr;
+    uint8_t *buf[NS] = {};       // page-locked on first use by the reader thread: slots 1.. are pinned while piece 0 is already on its way
+    std::vector<uint8_t *> regs;      // registered ranges of the mapping: [first range's start, reg_hi) in whole pages; a piece registers what of its pages is not registered yet
+    uint64_t reg_hi;
+    // staging slots: page-locked memory costs ~0.17 s per GiB to obtain and ~0.13 s per GiB to give back when the process ends
+    // (tools/ubench/exit_probe), so the slots are as small as the reader's rate allows: 4 x 32 MiB in 2 MiB chunks read 5 GB in
+    // 0.098 s inside the pipeline, 4 x 64 MiB in 4 MiB chunks in 0.114 s (profiles/r03_reader_sweep_50M.log)
+    size_t piece;
+    bool piece_env;              // COVERM_KNOBS ingest_piece_kb (tests: many small pieces)
+    // chunks well below a piece / threads: a piece ends in a barrier, and with one chunk per thread the slowest thread sets its
+    // pace (64 MiB pieces: 4 MiB chunks 0.114 s per 5 GB, 1 MiB chunks 0.091 s; the coordinator hops the blocks that straddle chunks)
+    const size_t chunk = 512u << 10;
+    size_t chunks_per_piece = 0;
+    uint64_t n_pieces = 0;
+    std::vector<bgzfw::PreChunk> pre;      // [slot][chunk]: the per-chunk hop of the piece in that slot (bgzf_walk_core.h)
+    // The mapping's pages leave the page table again behind the copy (a 20 GB mapping left to the end of the process costs ~0.4 s there, and
+    // counts as resident meanwhile).  HOW matters: a madvise per 512 KiB chunk interrupts every thread of the process 41 000 times per 20 GB
+    // (a TLB shootdown each) and tripled the time the coordinator spends in the feed calls; the piece in front, in 4 MiB parts handed to the
+    // same pool, is an eighth of the calls (COVERM_KNOBS ingest_zap: 1 = per chunk, 2 = the piece in front (default), 0 = all at the end).
+    long long zap_mode = 2;
+    double t_read = 0, t_wait = 0;      // the reader thread's: filling (or hopping) the pieces; waiting for a slot's upload or registering
+
+    PieceSource(cov_session *s_, int fd_, const char *path_, uint64_t file_size_, uint64_t f_lo_, uint64_t size_)
+        : s(s_), fd(fd_), path(path_), file_size(file_size_), f_lo(f_lo_), size(size_), reg_hi(f_lo_ / PG * PG) {
+        const char *io = getenv("COVERM_INGEST_IO");
+        use_map = io && (!strcmp(io, "mmap") || !strcmp(io, "mmap-upfront"));
+        map_upfront = use_map && !strcmp(io, "mmap-upfront");
+        copy_map = !use_map && !(io && !strcmp(io, "pread"));
+        if (use_map || copy_map) {
+            void *m = mmap(nullptr, (size_t)file_size, PROT_READ, MAP_SHARED, fd, 0);
+            if (m == MAP_FAILED) use_map = copy_map = false; else map = (uint8_t *)m;
+        }
+        piece = use_map ? (size_t)256 << 20 : (size_t)32 << 20;
+        long long piece_kb = 0;
+        piece_env = covknob::get("ingest_piece_kb", piece_kb);
+        if (piece_env && piece_kb >= 64) piece = (size_t)piece_kb << 10;
+        (void)covknob::get("ingest_zap", zap_mode);
+    }
+    ~PieceSource() {
+        (void)cov_ingest_abort(s);
+        for (int k = 0; k < NS; k++) if (buf[k]) cov_host_free(buf[k]);
+        for (uint8_t *r : regs) (void)cov_host_unregister(s, r);
+        if (map) munmap(map, (size_t)file_size);
+    }
+    PieceSource(const PieceSource &) = delete;
+
+    // Once the session's device is set up (cov_ingest_begin has returned): the first registration of the mapping — the whole range up front,
+    // or the first piece —, staging slots instead if it is refused; then the layout of the pieces.
+    void prepare() {
+        if (use_map && !register_piece(f_lo, map_upfront ? size - f_lo : std::min<uint64_t>(piece, size - f_lo))) {
+            use_map = false; copy_map = true;      // (the mapping itself is there: its bytes are copied into the slots)
+            if (!piece_env) piece = (size_t)32 << 20;
+        }
+        n_pieces = (size - f_lo + piece - 1) / piece;
+        chunks_per_piece = (piece + chunk - 1) / chunk;
+        pre.resize((size_t)NS * chunks_per_piece);
+    }
+    bool register_piece(uint64_t off, uint64_t n) {
+        const uint64_t map_len = (file_size + PG - 1) / PG * PG;
+        const uint64_t hi = std::min<uint64_t>(map_len, (off + n + PG - 1) / PG * PG);
+        if (hi <= reg_hi) return true;
+        if (cov_host_register(s, map + reg_hi, (size_t)(hi - reg_hi)) != COV_OK) return false;
+        regs.push_back(map + reg_hi);
+        reg_hi = hi;
+        return true;
+    }
+    void zap_range(uint64_t a, uint64_t b) const {
+        const uint64_t z0 = (a + PG - 1) / PG * PG, z1 = b / PG * PG;
+        if (z1 > z0) (void)madvise(map + z0, (size_t)(z1 - z0), MADV_DONTNEED);
+    }
+
+    uint64_t offset(uint64_t k) const { return f_lo + k * piece; }
+    uint64_t length(uint64_t k) const { return std::min<uint64_t>(piece, size - offset(k)); }
+    const uint8_t *bytes(uint64_t k) const { return use_map ? map + offset(k) : buf[k % NS]; }      // what the DMA engine reads piece k from
+    const bgzfw::PreChunk *pre_of(uint64_t k) const { return &pre[(size_t)(k % NS) * chunks_per_piece]; }
+    int io_code() const { return use_map ? (map_upfront ? 2 : 1) : copy_map ? 3 : 0; }
+    // this thread's caller and the coordinator need CPUs too (12 threads read no slower than 16 under a 16-CPU quota)
+    static int pool_threads(int threads) { return std::max(1, threads > 6 ? threads - 2 : threads); }
+
+    // Piece k into slot k % NS (the reader thread, once the ring has let go of the slot), each chunk's header hop right behind its bytes.
+    // false: err says why; soft = the file can still go to the CPU reader.
+    bool fill(uint64_t k, Pool &pool, std::string &err, bool &soft) {
+        const int slot = (int)(k % NS);
+        double t0 = now_s();
+        const uint64_t off = offset(k), n = length(k);
+        const size_t nch = (size_t)((n + chunk - 1) / chunk);
+        bgzfw::PreChunk *const P = &pre[(size_t)slot * chunks_per_piece];
+        if (use_map) {
+            // the piece's pages become device-readable (a few ms per 256 MiB), the pool hops its block headers in the mapping
+            if (!register_piece(off, n)) { err = cov_last_error(s); soft = true; return false; }
+            t_wait += now_s() - t0;
+            t0 = now_s();
+            const uint8_t *src = map + off;
+            pool.run(nch, [&](size_t c) {
+                const size_t o0 = c * chunk, e = (size_t)std::min<uint64_t>(n, (uint64_t)o0 + chunk);
+                bgzfw::prewalk(src + o0, e - o0, off + o0, P[c]);
+            });
+            t_read += now_s() - t0;
+            return true;
+        }
+        if (k >= NS && cov_ingest_slot_wait(s, slot) != COV_OK) { err = cov_last_error(s); return false; }      // the upload of piece k - NS has left the slot
+        t_wait += now_s() - t0;
+        if (!buf[slot]) {
+            buf[slot] = (uint8_t *)cov_host_alloc(std::min<uint64_t>(piece, size - f_lo));
+            if (!buf[slot]) { err = "no page-locked staging memory (is a HIP device usable?)"; return false; }
+        }
+        t0 = now_s();
+        uint8_t *dst = buf[slot];
+        std::atomic<bool> ok{true};
+        const size_t nz = (copy_map && zap_mode == 2 && k > 0) ? (size_t)((piece + ZPART - 1) / ZPART) : 0;      // the piece in front, in parts
+        pool.run(nch + nz, [&](size_t c) {
+            if (c >= nch) { const uint64_t a = off - piece + (uint64_t)(c - nch) * ZPART; zap_range(a, std::min<uint64_t>(a + ZPART, off)); return; }
+            const size_t o0 = c * chunk;
+            size_t o = o0; const size_t e = (size_t)std::min<uint64_t>(n, (uint64_t)o + chunk);
+            if (copy_map) {
+                // from the mapping, with stores that go past the caches; the block headers are hopped in the SOURCE, whose lines the
+                // copy has just loaded
+                const uint8_t *src = map + off + o0;
+                stream_copy(dst + o0, src, e - o0);
+                bgzfw::prewalk(src, e - o0, off + o0, P[c]);
+                if (zap_mode == 1) zap_range(off + o0, off + e);
+                return;
+            }
+            while (o < e) {
+                const ssize_t r = pread(fd, dst + o, e - o, (off_t)(off + o));
+                if (r <= 0) { ok = false; return; }
+                o += (size_t)r;
+            }
+            bgzfw::prewalk(dst + o0, e - o0, off + o0, P[c]);
+        });
+        t_read += now_s() - t0;
+        if (!ok) { err = "read error on " + path; return false; }
+        return true;
+    }
+    // what of the mapping is still in the page table goes now, beside the device's last window (the pool has nothing else to do)
+    void zap_rest(Pool &pool) const {
+        if (!copy_map || zap_mode == 1 || !n_pieces) return;
+        const uint64_t a0 = zap_mode == 2 ? f_lo + (n_pieces - 1) * piece : f_lo;
+        const size_t parts = (size_t)((size - a0 + ZPART - 1) / ZPART);
+        pool.run(parts, [&](size_t c) { const uint64_t a = a0 + (uint64_t)c * ZPART; zap_range(a, std::min<uint64_t>(a + ZPART, size)); });
+    }
+    // covh_bam_set_release_staging: the slots go back to the system right after the ingest has ended
+    void release_staging() {
+        if (use_map) return;
+        for (int k = 0; k < NS; k++)
+            if (buf[k]) { cov_host_free(buf[k]); buf[k] = nullptr; }
+        cov_host_trim();
+    }
+};
+
+const char *walk_error(bgzfw::Status st) {
+    switch (st) {
+        case bgzfw::NOT_A_BGZF_BLOCK: return "not a BGZF block (device ingest hands the file to the CPU reader)";
+        case bgzfw::BLOCK_WITH_EXTRA_SUBFIELDS: return "BGZF block with extra subfields (device ingest hands the file to the CPU reader)";
+        case bgzfw::MALFORMED_HEADER: return "malformed BGZF block header";
+        case bgzfw::ISIZE_ABOVE_64K: return "BGZF block inflates to more than 64 KiB";
+        case bgzfw::OK: break;
+    }
+    return "";
+}
+
+// A producer thread of a SlotRing: whichever way its owner leaves, the ring is stopped and the thread joined.
+template <int NS>
+struct RingThread {
+    SlotRing<NS> &ring; std::thread t;
+    ~RingThread() { ring.stop(); if (t.joinable()) t.join(); }
+};
+
+}  // namespace
+
+extern "C" {
+
 // 0 = records are in the session's store; 1 = the file needs the CPU reader (reason in err; nothing appended); -1 = error;
 // -2 = the record keys decrease inside the span (the reference's "appears to be unsorted" text in err).
-// timing (optional, 8 doubles): seconds reading the file, waiting for staging slots, in cov_ingest_end, total, until the first piece's upload call
-// (cov_ingest_begin's streams, events and buffers beside the first reads), in the header walk, in the feed calls, [7] see below.
+// timing (optional, 8 doubles; [0]..[6] in seconds):
+//   [0] the reader thread filling the staging slots (or hopping the headers of the mapped pieces)
+//   [1] the reader thread waiting for a slot's upload to leave it (or registering the mapped pieces)
+//   [2] in cov_ingest_end
+//   [3] the whole call
+//   [4] from the start of the call to the first cov_ingest_feed (cov_ingest_begin's streams, events and buffers beside the first reads)
+//   [5] in the header walk
+//   [6] in the feed calls, the wait for cov_ingest_begin in front of the first included
+//   [7] where the DMA read the bytes: 0 staging slots filled by pread, 1 mapped file registered piece by piece, 2 mapped and registered up
+//       front, 3 staging slots filled from the mapping
 int covh_bam_gpu_ingest(const char *path, int threads, cov_session *s, const covh_bam_header *hd, int check_crc, uint64_t *n_records,
                         double *timing, char *err, size_t errcap) {
     return covh_bam_gpu_ingest_span(path, threads, s, hd, check_crc, 0, 1, n_records, timing, err, errcap);
 }
 
-// One tid span of the file through the device ingest (same span definition as covh_bam_stream_open: boundaries one past the
-// tid found at k / count of the file).  The bytes fed run from the BGZF block at the span's probe point to a margin behind the
-// first block that begins with a record of a later span (found by bisection over file offsets: the keys are sorted); the
-// device drops the records of the neighbouring spans at both ends.
+// One tid span of the file through the device ingest (span_feed_range: which bytes).  A reader thread fills staging slot k % NS with
+// piece k as soon as the upload of piece k - NS has left the slot; this thread walks the block headers of the pieces in order and feeds
+// them: file reading, the serial header walk and the device never wait for one another in turn.
 int covh_bam_gpu_ingest_span(const char *path, int threads, cov_session *s, const covh_bam_header *hd, int check_crc, uint32_t span_index,
                              uint32_t span_count, uint64_t *n_records, double *timing, char *err, size_t errcap) {
-    auto fail = [&](int rc, const std::string &e) { if (err && errcap) { strncpy(err, e.c_str(), errcap - 1); err[errcap - 1] = 0; } return rc; };
+    auto fail = [&](int rc, const std::string &e) { return put_err(err, errcap, rc, e); };
     covr::Range rr("device ingest of one file span (covh_bam_gpu_ingest_span)");
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
+    const double t_start = now_s();
     if (n_records) *n_records = 0;
     if (span_count == 0 || span_index >= span_count) return fail(-1, "span index out of range");
     const int fd = open(path, O_RDONLY);
     if (fd < 0) return fail(-1, std::string("Unable to find BAM file ") + path);
     struct FdClose { int fd; ~FdClose() { close(fd); } } fdc{fd};
     const uint64_t file_size = hd->h.file_size;
-    uint64_t f_lo = 0, size = file_size;          // bytes [f_lo, size) are fed
-    int64_t key_lo = 0, key_hi = KEY_INF + 1;
-    uint64_t first_record = hd->h.first_record;
-    if (span_count > 1) {
-        const int32_t n_ref = (int32_t)hd->h.names.size();
-        std::vector<int64_t> B; std::vector<uint64_t> boff;
-        span_boundaries(fd, file_size, span_count, n_ref, hd->h.lens.data(), B, boff);
-        key_lo = B[span_index]; key_hi = B[span_index + 1];
-        if (span_index > 0) {
-            if (boff[span_index] == (uint64_t)-1 || key_lo >= key_hi) return 0;          // empty span: nothing to read
-            f_lo = boff[span_index]; first_record = 0;
-        } else if (key_hi <= 0) return 0;
-        if (span_index + 1 < span_count && boff[span_index + 1] != (uint64_t)-1) {
-            // smallest offset from which the first record found has a key >= key_hi
-            uint64_t lo = boff[span_index + 1], hi = file_size;
-            bool decided = true;
-            while (hi - lo > 65536 && decided) {
-                const uint64_t mid = lo + (hi - lo) / 2;
-                uint64_t bo = 0;
-                const int64_t key = probe_key(fd, file_size, mid, n_ref, hd->h.lens.data(), &bo);
-                if (key == PROBE_FAILED) decided = false;        // not "beyond the span": feed up to the end of the file instead
-                else if (key >= key_hi) hi = mid; else lo = mid;
-            }
-            // every record of this span starts before that point and may run on for up to the carry size of the device ingest
-            const uint64_t want = hi + ((uint64_t)17 << 20);
-            if (decided && want < file_size) { const uint64_t e = find_block_start(fd, file_size, want); if (e != (uint64_t)-1) size = e; }
-        }
-    }
-    const bool mid_start = f_lo != 0, open_end = size != file_size;
-    // Where the DMA engine takes the compressed bytes from (COVERM_INGEST_IO = pread | mmap):
-    //   pread (default) staging slots in page-locked memory filled by threaded preads;
-    //   mmap  the file is mapped and its pages are registered with the device piece by piece, ahead of the uploads, so that the
-    //         bytes go from the page cache to HBM with no copy by the CPU.  Alone on an idle device this reaches the link's rate
-    //         (tools/ubench/io_probe: 57 GB/s against 42-54 GB/s through staging slots), but inside the running pipeline
-    //         hipHostRegister drops to ~20 GB/s, the copies take longer to enqueue and unregistering 20 GB at the end costs
-    //         another 0.4 s (profiles/r03_io_modes.log: 200 M reads 1.78 s against 0.98 s): kept as an option, not the default.
-    //   More than two devices fed at once (covh_bam_set_concurrent_feeders; coverm-amd --devices): until round 6 the mapping, registered up
-    //   front, was the default there, on a model (a staged byte crosses the host's memory three times, a mapped one once).  Measured with eight
-    //   feeders on the one-GPU box (profiles/r06_eight_feeders_io.json): the eight registrations do NOT run beside one another — 0.2 to 1.2 s
-    //   per 2.6 GB span, 20.6 GB in ~1.2 s all told = 17 GB/s for the process —, which alone is longer than the whole single-device run
-    //   (0.76-0.96 s), while eight staged readers under the same 16-CPU quota copy at the one reader's rate (~49 GB/s in aggregate).  The
-    //   staging slots are therefore the default for any number of feeders; COVERM_INGEST_IO=mmap-upfront | mmap remain as options.
-    //   How the staging slots are FILLED (round 6, tools/ubench/copy_probe, profiles/r06_copy_probe.log): the feed was bound by the host's
-    //   memory system — 14 threads pread at 80-88 GB/s alone, but beside them the DMA out of the slots falls from 58 to 37-52 GB/s (pread's
-    //   copy_to_user reads the source, reads the destination lines for ownership and writes them; the DMA reads them once more), and the
-    //   pipeline settles where both run at ~50 GB/s.  Copying from a MAPPING of the file with non-temporal stores (no read for ownership,
-    //   nothing of the destination left in the caches) runs at 99-102 GB/s and leaves the DMA its 58-60 GB/s; zapping every chunk's pages
-    //   behind the copy (74-83 GB/s; a 20 GB mapping's page tables would otherwise cost ~0.4 s when the process ends) still does.  That is
-    //   the default; COVERM_INGEST_IO=pread keeps the preads (and is what a refused mapping falls back to).
-    const char *io = getenv("COVERM_INGEST_IO");
-    bool use_map = io && (!strcmp(io, "mmap") || !strcmp(io, "mmap-upfront"));
-    const bool map_upfront = use_map && !strcmp(io, "mmap-upfront");
-    bool copy_map = !use_map && !(io && !strcmp(io, "pread"));
-    uint8_t *map = nullptr;
-    const uint64_t PG = 4096, map_len = (file_size + PG - 1) / PG * PG;
-    if (use_map || copy_map) {
-        void *m = mmap(nullptr, (size_t)file_size, PROT_READ, MAP_SHARED, fd, 0);
-        if (m == MAP_FAILED) use_map = copy_map = false; else map = (uint8_t *)m;
-    }
+    const FeedRange r = span_feed_range(fd, hd->h, span_index, span_count);
+    if (r.empty) return 0;
     constexpr int NS = COV_INGEST_SLOTS;
-    uint8_t *buf[NS];
-    for (int k = 0; k < NS; k++) buf[k] = nullptr;       // page-locked on first use by the reader thread: slots 1.. are pinned while piece 0 is already on its way
-    // Every way out of this function after cov_ingest_begin first gives up whatever is still queued on the device (no-op once
-    // cov_ingest_end has run), and only then parks the staging buffers / unregisters the mapping: an upload may still be reading
-    // them, and an extraction still writing the store the CPU reader is about to push into.
-    struct BufFree {
-        cov_session *s; uint8_t **b; uint8_t *&map; uint64_t file_size; std::vector<std::pair<uint8_t *, uint64_t>> regs; std::mutex m;
-        ~BufFree() {
-            (void)cov_ingest_abort(s);
-            for (int k = 0; k < NS; k++) if (b[k]) cov_host_free(b[k]);
-            for (auto &r : regs) (void)cov_host_unregister(s, r.first);
-            if (map) munmap(map, (size_t)file_size);
-        }
-    } bf{s, buf, map, file_size, {}, {}};
+    // The order of these four declarations is the order of every way out, in reverse: the reader thread is stopped and joined; then
+    // cov_ingest_begin has returned (begun's destructor waits for it); only then does src give up what is queued on the device and let go
+    // of the memory the uploads read.
+    PieceSource src(s, fd, path, file_size, r.f_lo, r.size);
     // cov_ingest_begin (four streams, a dozen events, two page-locked tables: ~25 ms) runs BESIDE the reader's first pieces (their
     // page-locked slots cost ~5 ms each to obtain): the coordinator waits for it in front of the first feed.
-    std::future<int> begun = std::async(std::launch::async, [&]() -> int {
-        if (cov_ingest_begin(s, file_size, first_record, check_crc) != COV_OK) return 1;
-        if (span_count > 1 && cov_ingest_span(s, key_lo, key_hi, mid_start ? 1 : 0, open_end ? 1 : 0, f_lo, size) != COV_OK) return 1;
+    struct Begun {
+        std::future<int> f; int rc = 0;
+        int get() { if (f.valid()) rc = f.get(); return rc; }
+        ~Begun() { (void)get(); }
+    } begun{std::async(std::launch::async, [&]() -> int {
+        if (cov_ingest_begin(s, file_size, r.first_record, check_crc) != COV_OK) return 1;
+        if (span_count > 1 && cov_ingest_span(s, r.key_lo, r.key_hi, r.f_lo != 0 ? 1 : 0, r.size != file_size ? 1 : 0, r.f_lo, r.size) != COV_OK) return 1;
         return 0;
+    })};
+    SlotRing<NS> ring;
+    RingThread<NS> reader{ring, {}};
+    if (src.use_map && begun.get() != 0) return fail(-1, cov_last_error(s));      // registering the mapping needs the session's device set up
+    src.prepare();
+    const double t_begin = now_s() - t_start;
+    reader.t = std::thread([&]() {
+        Pool pool(PieceSource::pool_threads(threads));
+        for (uint64_t k = 0; k < src.n_pieces; k++) {
+            if (!ring.acquire(k)) return;
+            std::string e; bool soft = false;
+            if (!src.fill(k, pool, e, soft)) { ring.fail(e, soft); return; }
+            ring.publish(k, (size_t)src.length(k));
+        }
+        ring.finish();
+        src.zap_rest(pool);
     });
-    struct BegunWait { std::future<int> &f; ~BegunWait() { if (f.valid()) (void)f.get(); } } begun_wait{begun};     // (destroyed before bf: abort sees a finished begin)
-    if (use_map && begun.get() != 0) return fail(-1, cov_last_error(s));      // registering the mapping needs the session's device set up
-    // staging slots: page-locked memory costs ~0.17 s per GiB to obtain and ~0.13 s per GiB to give back when the process ends
-    // (tools/ubench/exit_probe), so the slots are as small as the reader's rate allows: 4 x 32 MiB in 2 MiB chunks read 5 GB in
-    // 0.098 s inside the pipeline, 4 x 64 MiB in 4 MiB chunks in 0.114 s (profiles/r03_reader_sweep_50M.log)
-    size_t piece = use_map ? (size_t)256 << 20 : (size_t)32 << 20;
-    long long piece_kb = 0;
-    const bool piece_env = covknob::get("ingest_piece_kb", piece_kb);      // tests: many small pieces
-    if (piece_env && piece_kb >= 64) piece = (size_t)piece_kb << 10;
-    // registered so far: [reg_lo0, reg_hi) of the mapping, in whole pages; a piece registers what of its pages is not registered yet
-    uint64_t reg_hi = f_lo / PG * PG;
-    auto register_piece = [&](uint64_t off, uint64_t n) -> bool {
-        const uint64_t hi = std::min<uint64_t>(map_len, (off + n + PG - 1) / PG * PG);
-        if (hi <= reg_hi) return true;
-        if (cov_host_register(s, map + reg_hi, (size_t)(hi - reg_hi)) != COV_OK) return false;
-        { std::lock_guard<std::mutex> lk(bf.m); bf.regs.emplace_back(map + reg_hi, hi - reg_hi); }
-        reg_hi = hi;
-        return true;
-    };
-    if (use_map && !register_piece(f_lo, map_upfront ? size - f_lo : std::min<uint64_t>(piece, size - f_lo))) {     // refused: staging slots instead
-        use_map = false; copy_map = true;      // (the mapping itself is there: its bytes are copied into the slots)
-        if (!piece_env) piece = (size_t)32 << 20;
-    }
-    const double t_begin = now() - t_start;
     std::vector<cov_bgzf_block> blocks;
-    uint64_t next_blk = f_lo, out_off = 0, pending_bsize = 0;     // absolute file offset of the next block header; running inflated size; BSIZE of a block whose header is read but whose end is not here yet
-    uint8_t tail[64]; uint64_t tail_end = 0; size_t tail_len = 0;   // last bytes of the previous piece (a header may straddle)
-    double t_read = 0, t_wait = 0, t_walk = 0, t_feed = 0, t_first_feed = 0;
-    const uint64_t n_pieces = (size - f_lo + piece - 1) / piece;
-    // Hopping the block headers is a chain of dependent cache misses (~0.3 us per block, 0.28 s for the 944 k blocks of a 200 M-read
-    // file) if one thread does it after the fact.  The pool thread that has just read a 4 MiB chunk hops the blocks that lie
-    // entirely inside it while the bytes are still in its cache (first header found by its 16-byte signature); the coordinator
-    // takes over a chunk's list when the chain arrives exactly at the list's first header, and hops by itself otherwise (the blocks
-    // that straddle chunks, or a chunk whose first signature was a coincidence inside compressed data).
-    // chunks well below a piece / threads: a piece ends in a barrier, and with one chunk per thread the slowest thread sets its
-    // pace (64 MiB pieces: 4 MiB chunks 0.114 s per 5 GB, 1 MiB chunks 0.091 s; the coordinator hops the blocks that straddle chunks)
-    size_t chunk = 512u << 10;
-    struct PreBlock { uint64_t hdr; uint32_t bsize, crc, isize; };
-    struct PreChunk { uint64_t first = ~0ull, next = 0; std::vector<PreBlock> blocks; };
-    const size_t chunks_per_piece = (piece + chunk - 1) / chunk;
-    std::vector<PreChunk> pre((size_t)NS * chunks_per_piece);
-    auto prewalk = [](const uint8_t *p, size_t n, uint64_t abs, PreChunk &out) {
-        out.first = ~0ull; out.next = 0; out.blocks.clear();
-        auto is_hdr = [&](size_t q) {
-            return q + 18 <= n && p[q] == 0x1f && p[q + 1] == 0x8b && p[q + 2] == 8 && p[q + 3] == 4 && p[q + 10] == 6 && p[q + 11] == 0 && p[q + 12] == 66 &&
-                   p[q + 13] == 67 && p[q + 14] == 2 && p[q + 15] == 0;
-        };
-        size_t q = 0;
-        for (;;) {     // first header signature in the chunk
-            const void *f = q < n ? memchr(p + q, 0x1f, n - q) : nullptr;
-            if (!f) return;
-            q = (size_t)((const uint8_t *)f - p);
-            if (is_hdr(q)) break;
-            q++;
-        }
-        out.first = abs + q;
-        while (is_hdr(q)) {
-            const size_t bsize = (size_t)(p[q + 16] | (p[q + 17] << 8)) + 1;
-            if (bsize < 26 || q + bsize > n) break;                  // ends in a later chunk: the coordinator's business
-            PreBlock b; b.hdr = abs + q; b.bsize = (uint32_t)bsize;
-            memcpy(&b.crc, p + q + bsize - 8, 4); memcpy(&b.isize, p + q + bsize - 4, 4);
-            if (b.isize > 65536u) break;
-            out.blocks.push_back(b);
-            q += bsize;
-        }
-        out.next = abs + q;
-    };
-    // The reader thread fills staging slot k % NS with piece k (threaded preads) as soon as the upload of piece k - NS has left
-    // the slot; this thread walks the block headers of the pieces in order and feeds them: file reading, the serial header walk
-    // and the device never wait for one another in turn.
-    std::mutex mu; std::condition_variable cv;
-    uint64_t ready = 0, fed = 0;        // pieces read so far / pieces handed to cov_ingest_feed so far
-    bool reader_failed = false, reader_soft = false, stop = false;      // soft: the file can still go to the CPU reader
-    std::string reader_err;
-    // The mapping's pages leave the page table again behind the copy (a 20 GB mapping left to the end of the process costs ~0.4 s there, and
-    // counts as resident meanwhile).  HOW matters: a madvise per 512 KiB chunk interrupts every thread of the process 41 000 times per 20 GB
-    // (a TLB shootdown each) and tripled the time the coordinator spends in the feed calls; the piece in front, in 4 MiB parts handed to the
-    // same pool, is an eighth of the calls (COVERM_KNOBS ingest_zap: 1 = per chunk, 2 = the piece in front (default), 0 = all at the end).
-    long long zap_mode = 2;
-    (void)covknob::get("ingest_zap", zap_mode);
-    const uint64_t ZPART = 4ull << 20;
-    auto zap_range = [&](uint64_t a, uint64_t b) {
-        const uint64_t z0 = (a + PG - 1) / PG * PG, z1 = b / PG * PG;
-        if (z1 > z0) (void)madvise(map + z0, (size_t)(z1 - z0), MADV_DONTNEED);
-    };
-    std::thread reader([&]() {
-        Pool pool(std::max(1, threads > 6 ? threads - 2 : threads));     // this thread's caller and the coordinator need CPUs too (12 threads read no slower than 16 under a 16-CPU quota)
-        for (uint64_t k = 0; k < n_pieces; k++) {
-            const int slot = (int)(k % NS);
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || k < NS || fed + NS > k; });      // piece k - NS has been fed: its upload is on the copy stream
-                if (stop) return;
-            }
-            double t0 = now();
-            const uint64_t off = f_lo + k * piece, n = std::min<uint64_t>(piece, size - off);
-            const size_t nch = (size_t)((n + chunk - 1) / chunk);
-            std::atomic<bool> ok{true};
-            if (use_map) {
-                // the piece's pages become device-readable (a few ms per 256 MiB), the pool hops its block headers in the mapping
-                if (!register_piece(off, n)) { std::lock_guard<std::mutex> lk(mu); reader_failed = true; reader_soft = true; reader_err = cov_last_error(s); cv.notify_all(); return; }
-                t_wait += now() - t0;
-                t0 = now();
-                const uint8_t *src = map + off;
-                pool.run(nch, [&](size_t c) {
-                    const size_t o0 = c * chunk, e = (size_t)std::min<uint64_t>(n, (uint64_t)o0 + chunk);
-                    prewalk(src + o0, e - o0, off + o0, pre[(size_t)slot * chunks_per_piece + c]);
-                });
-                t_read += now() - t0;
-            } else {
-            if (k >= NS && cov_ingest_slot_wait(s, slot) != COV_OK) {
-                std::lock_guard<std::mutex> lk(mu); reader_failed = true; reader_err = cov_last_error(s); cv.notify_all(); return;
-            }
-            t_wait += now() - t0;
-            if (!buf[slot]) {
-                buf[slot] = (uint8_t *)cov_host_alloc(std::min<uint64_t>(piece, size - f_lo));
-                if (!buf[slot]) { std::lock_guard<std::mutex> lk(mu); reader_failed = true; reader_err = "no page-locked staging memory (is a HIP device usable?)"; cv.notify_all(); return; }
-            }
-            t0 = now();
-            uint8_t *dst = buf[slot];
-            const size_t nz = (copy_map && zap_mode == 2 && k > 0) ? (size_t)((piece + ZPART - 1) / ZPART) : 0;      // the piece in front, in parts
-            pool.run(nch + nz, [&](size_t c) {
-                if (c >= nch) { const uint64_t a = off - piece + (uint64_t)(c - nch) * ZPART; zap_range(a, std::min<uint64_t>(a + ZPART, off)); return; }
-                const size_t o0 = c * chunk;
-                size_t o = o0; const size_t e = (size_t)std::min<uint64_t>(n, (uint64_t)o + chunk);
-                if (copy_map) {
-                    // from the mapping, with stores that go past the caches; the block headers are hopped in the SOURCE, whose lines the
-                    // copy has just loaded
-                    const uint8_t *src = map + off + o0;
-                    stream_copy(dst + o0, src, e - o0);
-                    prewalk(src, e - o0, off + o0, pre[(size_t)slot * chunks_per_piece + c]);
-                    if (zap_mode == 1) zap_range(off + o0, off + e);
-                    return;
-                }
-                while (o < e) {
-                    const ssize_t r = pread(fd, dst + o, e - o, (off_t)(off + o));
-                    if (r <= 0) { ok = false; return; }
-                    o += (size_t)r;
-                }
-                prewalk(dst + o0, e - o0, off + o0, pre[(size_t)slot * chunks_per_piece + c]);
-            });
-            t_read += now() - t0;
-            }
-            std::lock_guard<std::mutex> lk(mu);
-            if (!ok) { reader_failed = true; reader_err = std::string("read error on ") + path; cv.notify_all(); return; }
-            ready = k + 1;
-            cv.notify_all();
-        }
-        // what of the mapping is still in the page table goes now, beside the device's last window (the pool has nothing else to do)
-        if (copy_map && zap_mode != 1 && n_pieces) {
-            const uint64_t a0 = zap_mode == 2 ? f_lo + (n_pieces - 1) * piece : f_lo;
-            const size_t parts = (size_t)((size - a0 + ZPART - 1) / ZPART);
-            pool.run(parts, [&](size_t c) { const uint64_t a = a0 + (uint64_t)c * ZPART; zap_range(a, std::min<uint64_t>(a + ZPART, size)); });
-        }
-    });
-    struct Join { std::thread &t; std::mutex &mu; std::condition_variable &cv; bool &stop;
-                  ~Join() { { std::lock_guard<std::mutex> lk(mu); stop = true; } cv.notify_all(); if (t.joinable()) t.join(); } } joiner{reader, mu, cv, stop};
-    for (uint64_t k = 0; k < n_pieces; k++) {
-        const int slot = (int)(k % NS);
-        const uint64_t off = f_lo + k * piece, n = std::min<uint64_t>(piece, size - off);
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return reader_failed || ready > k; });
-            if (reader_failed) return fail(reader_soft ? 1 : -1, reader_err);
-        }
-        const uint8_t *dst = use_map ? map + off : buf[slot];
-        double t0 = now();
-        // ---- block headers completed by this piece
-        auto byte_at = [&](uint64_t a) -> uint8_t {   // absolute file offset, within this piece or the saved tail of the previous one
-            if (a >= off) return dst[a - off];
-            return tail[tail_len - (size_t)(tail_end - a)];
-        };
-        blocks.clear();
-        const uint64_t have = off + n;
-        for (;;) {
-            if (pending_bsize == 0 && next_blk >= off && next_blk < have) {     // a chunk's own hop starts exactly here: take its blocks
-                const PreChunk &P = pre[(size_t)slot * chunks_per_piece + (size_t)((next_blk - off) / chunk)];
-                if (P.first == next_blk && !P.blocks.empty()) {
-                    for (const PreBlock &pb : P.blocks) {
-                        cov_bgzf_block b;
-                        b.in_off = pb.hdr + 18; b.in_len = pb.bsize - 26; b.crc = pb.crc; b.isize = pb.isize; b.out_off = out_off; b.pad = 0;
-                        out_off += pb.isize;
-                        blocks.push_back(b);
-                    }
-                    next_blk = P.next;
-                    continue;
-                }
-            }
-            if (pending_bsize == 0) {          // header of the next block (may straddle into the saved tail of the previous piece)
-                if (next_blk + 18 > have) break;
-                uint8_t hb[18];
-                for (int q = 0; q < 18; q++) hb[q] = byte_at(next_blk + (uint64_t)q);
-                if (hb[0] != 0x1f || hb[1] != 0x8b || hb[2] != 8 || !(hb[3] & 4)) return fail(1, "not a BGZF block (device ingest hands the file to the CPU reader)");
-                const uint32_t xlen = hb[10] | (hb[11] << 8);
-                if (xlen != 6 || hb[12] != 66 || hb[13] != 67 || hb[14] != 2 || hb[15] != 0)    // extra subfields besides BC: rare, let the CPU reader take it
-                    return fail(1, "BGZF block with extra subfields (device ingest hands the file to the CPU reader)");
-                pending_bsize = (uint64_t)(hb[16] | (hb[17] << 8)) + 1;
-                if (pending_bsize < 26) return fail(1, "malformed BGZF block header");
-            }
-            const uint64_t bsize = pending_bsize;
-            if (next_blk + bsize > have) break;             // completed by a later piece (its header is not read again)
-            cov_bgzf_block b;
-            b.in_off = next_blk + 18; b.in_len = (uint32_t)(bsize - 26);
-            uint8_t tr[8];
-            for (int q = 0; q < 8; q++) tr[q] = byte_at(next_blk + bsize - 8 + (uint64_t)q);
-            memcpy(&b.crc, tr, 4); memcpy(&b.isize, tr + 4, 4);
-            if (b.isize > 65536u) return fail(1, "BGZF block inflates to more than 64 KiB");
-            b.out_off = out_off; b.pad = 0;
-            out_off += b.isize;
-            blocks.push_back(b);
-            next_blk += bsize;
-            pending_bsize = 0;
-        }
-        tail_len = (size_t)std::min<uint64_t>(sizeof tail, n);
-        memcpy(tail, dst + n - tail_len, tail_len);
-        tail_end = have;
-        t_walk += now() - t0;
-        t0 = now();
-        if (begun.valid() && begun.get() != 0) return fail(-1, cov_last_error(s));
-        if (k == 0) t_first_feed = now() - t_start;
-        if (cov_ingest_feed(s, slot, dst, off, n, blocks.data(), (uint32_t)blocks.size()) != COV_OK) return fail(-1, cov_last_error(s));
-        t_feed += now() - t0;
-        { std::lock_guard<std::mutex> lk(mu); fed = k + 1; }
-        cv.notify_all();
+    bgzfw::Walker walk(r.f_lo);
+    double t_walk = 0, t_feed = 0, t_first_feed = 0;
+    uint64_t k = 0; size_t n = 0;
+    SlotRing<NS>::Take got;
+    for (; (got = ring.take(k, &n)) == SlotRing<NS>::PIECE; k++) {
+        const uint8_t *bytes = src.bytes(k);
+        double t0 = now_s();
+        blocks.clear();      // the blocks completed by this piece
+        const bgzfw::Status st = walk.piece(bytes, src.offset(k), n, src.pre_of(k), src.chunk, blocks);
+        if (st != bgzfw::OK) return fail(1, walk_error(st));
+        t_walk += now_s() - t0;
+        t0 = now_s();
+        if (begun.get() != 0) return fail(-1, cov_last_error(s));
+        if (k == 0) t_first_feed = now_s() - t_start;
+        if (cov_ingest_feed(s, (int)(k % NS), bytes, src.offset(k), n, blocks.data(), (uint32_t)blocks.size()) != COV_OK) return fail(-1, cov_last_error(s));
+        t_feed += now_s() - t0;
+        ring.fed(k);
     }
-    reader.join();
-    if (begun.valid() && begun.get() != 0) return fail(-1, cov_last_error(s));      // (a span without pieces)
-    if (next_blk != size) return fail(1, "truncated BGZF block at the end of the file");
-    double t0 = now();
+    if (got == SlotRing<NS>::FAILED) return fail(ring.soft() ? 1 : -1, ring.error());
+    reader.t.join();
+    if (begun.get() != 0) return fail(-1, cov_last_error(s));      // (a span without pieces)
+    if (walk.next_blk != r.size) return fail(1, "truncated BGZF block at the end of the file");
+    double t0 = now_s();
     // (Giving the staging slots back to the system BESIDE the device's last rounds was measured — exit 0.03 s shorter, tail as much
     // longer, hipHostFree waits for the device: profiles/r03_tail_variants.log — and it had a second thread call into the session that
     // cov_ingest_end is working on.  With covh_bam_set_release_staging the slots now go back right after the ingest has ended.)
     uint64_t nrec = 0;
     const cov_status rc = cov_ingest_end(s, &nrec);
-    if (g_release_staging.load() && !use_map) {
-        for (int k = 0; k < NS; k++)
-            if (buf[k]) { cov_host_free(buf[k]); buf[k] = nullptr; }
-        cov_host_trim();
+    if (g_release_staging.load()) src.release_staging();
+    const double t_end = now_s() - t0;
+    if (timing) {
+        timing[0] = src.t_read; timing[1] = src.t_wait; timing[2] = t_end; timing[3] = now_s() - t_start;
+        timing[4] = t_first_feed > 0 ? t_first_feed : t_begin; timing[5] = t_walk; timing[6] = t_feed; timing[7] = src.io_code();
     }
-    const double t_end = now() - t0;
-    if (timing) { timing[0] = t_read; timing[1] = t_wait; timing[2] = t_end; timing[3] = now() - t_start; timing[4] = t_first_feed > 0 ? t_first_feed : t_begin; timing[5] = t_walk; timing[6] = t_feed; timing[7] = use_map ? (map_upfront ? 2 : 1) : copy_map ? 3 : 0; }      /* [7]: where the DMA read the bytes: 0 staging slots filled by pread, 1 mapped file, 2 mapped and registered up front, 3 staging slots filled from the mapping */
     if (rc == COV_ERR_INGEST_FALLBACK) return fail(1, cov_last_error(s));
     if (rc == COV_ERR_UNSORTED) return fail(-2, cov_last_error(s));      // keys decrease inside the span: the caller may send the file through one device whole
     if (rc != COV_OK) return fail(-1, cov_last_error(s));
@@ -1675,25 +1671,24 @@ struct covh_bam { Bam b; };
 
 covh_bam *covh_bam_open(const char *path, int threads, int want_names, char *err, size_t errcap) {
     const bool timing = covh_timing_on();
-    auto now = []() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t0 = now(), t1 = t0, t2 = t0, t3 = t0;
+    double t0 = now_s(), t1 = t0, t2 = t0, t3 = t0;
     covh_bam *h = new covh_bam();
     h->b.path = path; h->b.threads = std::max(1, threads); h->b.want_names = want_names != 0;
     Buf raw;
     bool ok = read_file(path, raw, h->b.err);
     if (ok && raw.size() == 0) { ok = false; h->b.err = std::string(path) + ": empty file (no BAM/SAM header)"; }   // htslib: sam_hdr_read fails
-    t1 = now();
+    t1 = now_s();
     if (ok) {
         if (raw.size() >= 2 && raw[0] == 0x1f && raw[1] == 0x8b) {
             Buf u;
             ok = bgzf_inflate_all(raw, u, h->b.threads, h->b.err);
             raw.alloc(0);
-            t2 = now();
+            t2 = now_s();
             if (ok) ok = parse_bam(h->b, u);
-            t3 = now();
+            t3 = now_s();
             const size_t umb = u.size() >> 20;
             u.alloc(0);
-            if (timing) fprintf(stderr, "[covh_bam] read %.3fs inflate %.3fs (%zu MB) parse %.3fs release %.3fs\n", t1 - t0, t2 - t1, umb, t3 - t2, now() - t3);
+            if (timing) fprintf(stderr, "[covh_bam] read %.3fs inflate %.3fs (%zu MB) parse %.3fs release %.3fs\n", t1 - t0, t2 - t1, umb, t3 - t2, now_s() - t3);
         } else ok = parse_sam(h->b, raw);
     }
     if (!ok) {
@@ -1981,9 +1976,8 @@ int covh_bam_filter_file(const char *in_path, const char *out_path, const covh_p
     if (n_out) *n_out = 0;
     const int T = std::max(1, threads);
     const bool timing = covh_timing_on();
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double t_prev = now(), t_part[5] = {0, 0, 0, 0, 0};
-    auto stamp = [&](int k) { const double t = now(); t_part[k] += t - t_prev; t_prev = t; };
+    double t_prev = now_s(), t_part[5] = {0, 0, 0, 0, 0};
+    auto stamp = [&](int k) { const double t = now_s(); t_part[k] += t - t_prev; t_prev = t; };
     struct File { FILE *f = nullptr; ~File() { if (f) fclose(f); } } fi, fo;
     fi.f = fopen(in_path, "rb");
     if (!fi.f) return fail(std::string("Unable to find BAM file ") + in_path);
@@ -2222,9 +2216,8 @@ void covh_sam_close(covh_sam *h) { if (!h) return; if (h->own_fd && h->fd >= 0) 
 // the file on the host if it can be read again; -1 = error.  tm: [0] read, [1] waiting for slots, [2] feed calls, [3] total (seconds).
 int covh_sam_gpu_ingest(covh_sam *h, int threads, cov_session *s, uint64_t *n_records, double *tm, char *err, size_t errcap) {
     (void)threads;
-    auto fail = [&](int rc, const std::string &m) { if (err && errcap) snprintf(err, errcap, "%s", m.c_str()); return rc; };
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
+    auto fail = [&](int rc, const std::string &m) { return put_err(err, errcap, rc, m); };
+    const double t_start = now_s();
     if (n_records) *n_records = 0;
     if (h->kind != 0) return fail(-1, h->path + ": not SAM text");
     std::string blob; std::vector<uint64_t> off(1, 0);
@@ -2240,80 +2233,68 @@ int covh_sam_gpu_ingest(covh_sam *h, int threads, cov_session *s, uint64_t *n_re
         if (!slots.p[k]) slots.p[k] = (uint8_t *)malloc(W);
         if (!slots.p[k]) { (void)cov_ingest_abort(s); return fail(-1, "out of memory for the SAM staging slots"); }
     }
-    // reader -> feeder: filled pieces in order; feeder -> reader: how many pieces have been fed (a slot is free once its piece was fed AND uploaded)
-    struct Piece { int slot; size_t n; };
-    std::mutex mu; std::condition_variable cv;
-    std::deque<Piece> q; bool reader_done = false, stop = false; std::string reader_err;
-    uint64_t fed = 0;
-    std::atomic<bool> halt{false};
-    double t_read = 0, t_wait = 0;
-    std::thread reader([&] {
+    // the reader fills slot i % NS with piece i once piece i - NS has been fed AND uploaded; the feeder takes the pieces in order
+    constexpr int NS = COV_INGEST_SLOTS;
+    SlotRing<NS> ring;
+    std::atomic<bool> halt{false};      // read_full looks at it between read() calls: a slow pipe is not waited on once the feeder has failed
+    double t_read = 0, t_wait = 0, t_feed = 0;
+    RingThread<NS> reader{ring, std::thread([&] {
         std::vector<uint8_t> carry;           // the cut-off last line of the previous piece
         size_t head_at = 0;                   // bytes of h->head already replayed
         bool eof = false;
         for (uint64_t i = 0; !eof; i++) {
-            const int k = (int)(i % COV_INGEST_SLOTS);
-            { std::lock_guard<std::mutex> lk(mu); if (stop) break; }
-            if (i >= COV_INGEST_SLOTS) {
-                const double t0 = now();
-                { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return stop || fed > i - COV_INGEST_SLOTS; }); if (stop) break; }
-                if (cov_sam_slot_wait(s, k) != COV_OK) { std::lock_guard<std::mutex> lk(mu); reader_err = cov_last_error(s); break; }
-                t_wait += now() - t0;
+            const int k = (int)(i % NS);
+            double t0 = now_s();
+            if (!ring.acquire(i)) return;
+            if (i >= NS) {
+                if (cov_sam_slot_wait(s, k) != COV_OK) return ring.fail(cov_last_error(s), false);
+                t_wait += now_s() - t0;
             }
             uint8_t *dst = slots.p[k];
             size_t fill = carry.size();
             if (fill) memcpy(dst, carry.data(), fill);
             carry.clear();
-            const double t0 = now();
+            t0 = now_s();
             if (head_at < h->head.size()) { const size_t m = std::min(W - fill, h->head.size() - head_at); memcpy(dst + fill, h->head.data() + head_at, m); fill += m; head_at += m; }
             if (head_at == h->head.size() && !h->head.empty()) { std::vector<uint8_t>().swap(h->head); head_at = 0; }
             if (h->head.empty() && fill < W) {
                 if (h->eof) eof = true;
                 else {
                     const ssize_t r = read_full(h->fd, dst + fill, W - fill, eof, &halt);
-                    if (r < 0) { std::lock_guard<std::mutex> lk(mu); reader_err = "read error on " + h->path; break; }
+                    if (r < 0) return ring.fail("read error on " + h->path, false);
                     fill += (size_t)r;
                 }
             }
-            t_read += now() - t0;
+            t_read += now_s() - t0;
             size_t cut = fill;
             if (!eof) {      // whole lines only: the bytes behind the last '\n' wait for the next piece (none: a line as long as the window, the device says so)
                 const void *nl = memrchr(dst, '\n', fill);
                 if (nl) { cut = (size_t)((const uint8_t *)nl - dst) + 1; carry.assign(dst + cut, dst + fill); }
             }
-            { std::lock_guard<std::mutex> lk(mu); q.push_back(Piece{k, cut}); }
-            cv.notify_all();
+            ring.publish(i, cut);
         }
-        { std::lock_guard<std::mutex> lk(mu); reader_done = true; }
-        cv.notify_all();
-    });
+        ring.finish();
+    })};
     int rc = 0; std::string msg;
-    double t_feed = 0;
-    for (;;) {
-        Piece pc{-1, 0};
-        {
-            std::unique_lock<std::mutex> lk(mu);
-            cv.wait(lk, [&] { return !q.empty() || reader_done; });
-            if (q.empty()) break;
-            pc = q.front(); q.pop_front();
-        }
-        const double t0 = now();
-        const cov_status st = pc.n ? cov_sam_feed(s, pc.slot, slots.p[pc.slot], pc.n) : COV_OK;
-        t_feed += now() - t0;
+    size_t n = 0;
+    for (uint64_t i = 0; ring.take(i, &n) == SlotRing<NS>::PIECE; i++) {
+        const int k = (int)(i % NS);
+        const double t0 = now_s();
+        const cov_status st = n ? cov_sam_feed(s, k, slots.p[k], n) : COV_OK;
+        t_feed += now_s() - t0;
         if (st != COV_OK) { rc = st == COV_ERR_INGEST_FALLBACK ? 1 : -1; msg = cov_last_error(s); break; }
-        { std::lock_guard<std::mutex> lk(mu); fed++; }
-        cv.notify_all();
+        ring.fed(i);
     }
-    { std::lock_guard<std::mutex> lk(mu); stop = true; halt = true; }
-    cv.notify_all();
-    reader.join();
-    if (rc == 0 && !reader_err.empty()) { rc = -1; msg = reader_err; }
+    halt = true;
+    ring.stop();
+    reader.t.join();
+    if (rc == 0 && ring.failed()) { rc = -1; msg = ring.error(); }
     if (rc != 0) { (void)cov_ingest_abort(s); return fail(rc, h->path + ": " + msg); }
     uint64_t nrec = 0;
     if (cov_sam_end(s, &nrec) != COV_OK) return fail(-1, cov_last_error(s));
     for (int k = 0; k < COV_INGEST_SLOTS; k++) (void)cov_sam_slot_wait(s, k);
     if (n_records) *n_records = nrec;
-    if (tm) { tm[0] = t_read; tm[1] = t_wait; tm[2] = t_feed; tm[3] = now() - t_start; }
+    if (tm) { tm[0] = t_read; tm[1] = t_wait; tm[2] = t_feed; tm[3] = now_s() - t_start; }
     return 0;
 }
 

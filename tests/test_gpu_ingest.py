@@ -80,6 +80,49 @@ def test_device_ingest_equals_cpu_reader(tmp_path, monkeypatch, with_seq, piece_
     np.testing.assert_array_equal(w.records.pos, b.pos)
 
 
+def _io_code(path, ref_lens, threads=4):
+    """timing[7] of a device ingest of the whole file: where the DMA engine read the bytes (covh_bam_gpu_ingest's comment, csrc/host_bam.cpp)"""
+    import ctypes as C
+    from coverm_amd import native
+    L = native.lib()
+    L.covh_bam_read_header.restype = C.c_void_p
+    L.covh_bam_read_header.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]
+    L.covh_bam_header_free.argtypes = [C.c_void_p]
+    L.covh_bam_gpu_ingest.argtypes = [C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+    err = C.create_string_buffer(512)
+    hd = L.covh_bam_read_header(path.encode(), err, 512)
+    assert hd, err.value
+    try:
+        with Session(0, FilterConfig(), 75) as s:
+            s.set_targets(ref_lens)
+            n, t = C.c_uint64(0), (C.c_double * 8)()
+            rc = L.covh_bam_gpu_ingest(path.encode(), threads, s._h, hd, 1, C.byref(n), t, err, 512)
+            assert rc == 0, (rc, err.value)
+            return int(t[7]), int(n.value)
+    finally:
+        L.covh_bam_header_free(hd)
+
+
+@pytest.mark.parametrize("io,code", [(None, 3), ("pread", 0), ("mmap", 1)])
+def test_device_ingest_through_every_piecewise_source(tmp_path, monkeypatch, io, code):
+    """64 KiB pieces, so that the four staging slots come round dozens of times, with the bytes taken from staging slots filled from a
+    mapping of the file (the default), from staging slots filled by pread, and from the mapping itself, registered with the device piece by
+    piece: the same records as the CPU reader's every time, and the driver says which source it used."""
+    set_knobs(monkeypatch, ingest_piece_kb=64)
+    if io is None:
+        monkeypatch.delenv("COVERM_INGEST_IO", raising=False)
+    else:
+        monkeypatch.setenv("COVERM_INGEST_IO", io)
+    ref = synth.make_reference(40, 6_000_000, seed=18, min_len=5000, max_len=800_000)
+    b = synth.make_reads(ref, 120_000, seed=19)
+    p = str(tmp_path / "s.bam")
+    cbam.write_bam(p, ref.names, ref.lengths, b, with_seq=2, threads=4)
+    assert os.path.getsize(p) > 40 * 4 * (64 << 10)
+    w = _check(p)
+    np.testing.assert_array_equal(w.records.pos, b.pos)
+    assert _io_code(p, w.ref_lens) == (code, b.n_records)
+
+
 @pytest.mark.parametrize("level,block", [(0, 0xFF00), (9, 0xFF00), (6, 700), (1, 90)])
 def test_device_inflate_block_types(tmp_path, level, block):
     """Stored blocks (level 0), long-match streams (level 9), and tiny BGZF blocks, which zlib emits with FIXED Huffman codes."""
