@@ -87,7 +87,9 @@ struct cov_session {
     std::string err;
     int tile = 1024;  // bases per tile (one wave per tile: STREAM_TW)
     bool use_fast = true;  // k_pileup_fast + k_pileup_stream on the slow-tile list (default); COVERM_PILEUP=stream: k_pileup_stream alone
-    int chunk_tiles = 8;   // consecutive tiles walked by one wave (swept in round 4: 4 -> 0.627 ms, 8 -> 0.596, 16 -> 0.642, 32 -> 0.866)
+    int chunk_tiles = 4;   // consecutive tiles walked by one wave.  (Round 4, when every chunk end paid the statistics' reductions and atomics: 4 -> 0.627 ms, 8 -> 0.596,
+                           // 16 -> 0.642, 32 -> 0.866.  With the statistics derived from the histogram a chunk end only moves bins and the better balance of short
+                           // chunks wins: profiles/hist_derived_stats_ab.json.)  COVERM_KNOBS pileup_chunk_tiles overrides it.
     int prep_kernel = 0;   // 0 = k_prep_lean (prep_lean.hip.h); COVERM_PREP_KERNEL=7 forces k_prep7s, the second implementation (tests)
     int est_lanes = -1;        // k_estimate_lanes (a lane per contig) from 65 536 contigs on; COVERM_EST_LANES=1 | 0 forces it on / off (tests)
     int fast_tables = 1;       // k_pileup_fast (one table of biased deltas: the default) or k_pileup_fast2t (two count tables; COVERM_FAST_TABLES=2)
@@ -546,6 +548,7 @@ cov_status cov_create(const cov_config *cfg, cov_session **out) {
     if (const char *im = getenv("COVERM_IDENTITY")) s->id_mode = strcmp(im, "serial") ? 1 : 0;
     { long long v; if (covknob::get("store_cap_records", v) && v >= 1) s->cap_records = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
     { long long v; if (covknob::get("store_cap_cigar", v) && v >= 1) s->cap_cigar = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
+    { long long v; if (covknob::get("pileup_chunk_tiles", v) && v >= 1 && v <= 64) s->chunk_tiles = (int)v; }
     // (every stream costs ~6 ms to create and as much again when the process ends, tools/ubench/exit_probe: the side stream of the
     // identity kernels is created by the first cov_finish that wants it, and borrows the ingest's second stream when there is one)
     e = hipEventCreateWithFlags(&s->ev_prep_done, hipEventDisableTiming);
@@ -1064,6 +1067,8 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     const bool want_hist = s->cfg.want & COV_WANT_HIST, want_id = s->cfg.want & COV_WANT_IDENTITY;
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
     bool compacted = false;      // the compact histogram was built by this pass (else: by the first cov_fetch_hist)
+    bool derive_in_est = false;  // the estimator kernel derives the contigs' window statistics from their bins (else k_hist_stats did, or there are none)
+    const bool est_lanes = s->est_lanes < 0 ? nT >= 65536u : s->est_lanes == 1;      // an assembly: a lane per contig (pileup_kernels.hip.h, estimate_body)
     s->est_valid = false; s->gen_valid = false;
     s->ev_fresh = -1;
 
@@ -1223,13 +1228,21 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
             HIPCHK(hipGetLastError());
         }
         PileupArgs a = pileup_args(s);
+        // With the histogram wanted the pileup leaves the bins and cov_out; the contigs' window statistics are derived from the bins once
+        // per contig (hist_stats_derive): by the estimator kernel as its prologue when it is the first reader — no launch added —, else
+        // by k_hist_stats here, in front of k_hist_sum<1> / the genome and separator kernels / the copy of the result block.
+        compacted = want_hist && (s->est.n == 0 || s->hist_fetch_seen);
+        derive_in_est = want_hist && !compacted && !(s->have_mask || s->have_runs) && s->est.n != 0;
         time_begin(s, COV_K_PILEUP);
         if (want_hist) launch_any_pileup<true, false>(s, a, s->n_tiles);
         else launch_any_pileup<false, false>(s, a, s->n_tiles);
+        if (want_hist && !derive_in_est) {
+            if (est_lanes) hipLaunchKernelGGL((k_hist_stats<true>), dim3((nT + 255) / 256), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u32 *)s->d_arena.p);
+            else hipLaunchKernelGGL((k_hist_stats<false>), dim3((nT + 3) / 4), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u32 *)s->d_arena.p);
+        }
         time_end(s, COV_K_PILEUP);
         HIPCHK(hipGetLastError());
         if (want_hist) {
-            compacted = s->est.n == 0 || s->hist_fetch_seen;
             s->hist_prefetched = 0;
             if (compacted) {
                 HIPCHK(s->d_chist.reserve((size_t)R + nT + 1, st));
@@ -1275,12 +1288,12 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
     if (want_id && R && nT) { HIPCHK(hipStreamWaitEvent(st, s->ev_side_done, 0)); s->ev_fresh = -1; }      // (the wait is not the next group's time)
     if (nf) {      // CoverageEstimator::calculate_coverage of every contig (k_init left n_pass = 0 everywhere when nothing ran: rows of zeros)
         time_begin(s, COV_K_ESTIMATE);
-        if (s->est_lanes < 0 ? nT >= 65536u : s->est_lanes == 1)      // an assembly: a lane per contig (pileup_kernels.hip.h, estimate_body)
-            hipLaunchKernelGGL(k_estimate_lanes, dim3((nT + 255) / 256), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
-                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block));
+        if (est_lanes)
+            hipLaunchKernelGGL(k_estimate_lanes, dim3((nT + 255) / 256), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
+                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block), derive_in_est ? 1u : 0u);
         else
-            hipLaunchKernelGGL(k_estimate, dim3((nT + 3) / 4), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
-                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block));
+            hipLaunchKernelGGL(k_estimate, dim3((nT + 3) / 4), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
+                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block), derive_in_est ? 1u : 0u);
         time_end(s, COV_K_ESTIMATE);
         HIPCHK(hipGetLastError());
     }

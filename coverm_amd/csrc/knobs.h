@@ -2,6 +2,7 @@
 // variable, COVERM_KNOBS="name=value,name=value" (e.g. "store_cap_records=50000,ingest_round_blocks=128"), looked up where a session, an
 // ingest or a reader is set up and never in a launch path.  A name that is absent leaves the built-in size in place.  The names:
 //   store_cap_records, store_cap_cigar      cov_create: the bounded record store (covermhip.hip)
+//   pileup_chunk_tiles                      cov_create: consecutive tiles one wave of the pileup kernels walks (1 .. 64)
 //   ingest_round_blocks, ingest_carry_kb, ingest_cwin_kb      cov_ingest_begin: blocks per inflate window, carry buffer, compressed window
 //   pair_chunk                              cov_pair_filter: records per table chunk
 //   ingest_piece_kb                         covh_bam_ingest_device: bytes per staging piece

@@ -20,6 +20,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#define HSTC_FN __host__ __device__ __forceinline__
+#include "hist_stats_core.h"
+
 namespace covk {
 
 typedef unsigned long long u64;
@@ -38,7 +41,7 @@ constexpr u32 CX_MIN_OPS = 16;   // RW_COMPLEX records with more CIGAR operation
 struct DevContig {
     u64 n_primary, n_pass, n_nonsupp, sum_nm, sum_indel;   // k_prep
     double id_primary, id_nonsupp;                          // k_identity
-    u64 sum_d, sum_d2, cov_win, cov_full, proc_win;         // k_pileup
+    u64 sum_d, sum_d2, cov_win, cov_full, proc_win;         // k_pileup; with the histogram wanted: derived from its bins (hist_stats_derive)
     u64 hist_off;                                           // k_hist_off<0>
     u32 first_rec, last_rec;                                // considered records (file order)
     u32 rec_start, rec_end;                                 // span of ALL records carrying this tid
@@ -48,7 +51,7 @@ struct DevContig {
     u32 hist_cap;                                           // upper bound on depth (max candidate count of a tile)
     u32 min_d, max_d;                                       // k_pileup, window positions of processed tiles
     u32 hist_len;                                           // k_hist_compact_layout
-    u32 pad;
+    u32 cov_out;                                            // k_pileup with the histogram wanted: covered positions of the contig OUTSIDE the window
     u64 chist_off;                                          // offset in the compact histogram
 };
 static_assert(sizeof(DevContig) == 160, "DevContig layout");
@@ -134,7 +137,7 @@ __device__ __forceinline__ u32 wave_max_u32(u32 v) {
 }
 
 // Wave totals by DPP prefix sums (VALU only; the __shfl_xor versions above go through the LDS crossbar, twelve round trips for a u64).  Every lane
-// returns the total.  wave_sum_u56: the values must be below 2^56 (two 24-bit-apart halves, each summed in 32 bits).
+// returns the total.  wave_sum_u56: two 24-bit-apart halves, each summed in 32 bits — exact while the 64 values are below 2^50 (callers test that).
 __device__ __forceinline__ u32 wave_sum_u32_dpp(u32 v) { return (u32)__builtin_amdgcn_readlane(wave_incl_scan((int)v), 63); }
 __device__ __forceinline__ u64 wave_sum_u56(u64 v) {
     const u32 lo = (u32)v & 0xffffffu, hi = (u32)(v >> 24);
@@ -229,7 +232,7 @@ __global__ void k_init(DevContig *ctg, u32 n_targets, DevGlobal *g, TileIdx ti, 
     z.first_rec = 0xffffffffu; z.last_rec = 0;
     z.rec_start = 0xffffffffu; z.rec_end = 0;
     z.n_groups = 0; z.max_span = 0; z.flags = 0; z.hist_cap = 0;
-    z.min_d = 0xffffffffu; z.max_d = 0; z.hist_len = 0; z.pad = 0; z.chist_off = 0;
+    z.min_d = 0xffffffffu; z.max_d = 0; z.hist_len = 0; z.cov_out = 0; z.chist_off = 0;
     ctg[c] = z;
 }
 
@@ -1399,8 +1402,12 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
 #pragma unroll
         for (int b = lane; b < HBW; b += 64) lhist[b] = 0u;
     }
-    u64 sum_d = 0, sum_d2 = 0, proc_win = 0;
-    u32 cov_w = 0, cov_f = 0, mn = 0xffffffffu, mx = 0;
+    // With the histogram wanted: the histogram and the covered positions outside the window, nothing else (as in pileup_fast_body: the
+    // window statistics are derived from the contig's final bins, hist_stats_derive) — both kernels feed one histogram per contig.
+    u64 sum_d = 0, sum_d2 = 0, proc_win = 0;                      // (no histogram only)
+    u32 cov_w = 0, cov_f = 0, mn = 0xffffffffu, mx = 0;           // (no histogram only)
+    u32 cov_o = 0;             // (histogram wanted only) covered positions of the contig outside the window
+    u32 hbound = 0;            // no LDS bin above this was touched since the last flush (depth <= candidate runs of the tile)
     int cur_c = -1;
     u64 hoff = 0; u32 hcap = 0;
     const u64 excl = a.excl;
@@ -1410,6 +1417,22 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
         else hist_add_overflow(a.hist_arena, hoff, hcap, a.g, d, x);
     };
     auto flush = [&]() {
+        if (WANT_HIST) {
+            if (cur_c >= 0) {
+                lds_fence();
+                for (u32 b = (u32)lane; b <= hbound; b += 64) {
+                    const u32 x = lhist[b];
+                    if (x) { atomicAdd(&a.hist_arena[hoff + b], x); lhist[b] = 0u; }
+                }
+                lds_fence();
+                if (__any(cov_o != 0u)) {
+                    const u32 co = wave_sum_u32(cov_o);
+                    if (lane == 0) atomicAdd(&a.ctg[cur_c].cov_out, co);
+                }
+            }
+            cov_o = 0; hbound = 0;
+            return;
+        }
         if (cur_c >= 0) {
             const u64 s1 = wave_sum_u64(sum_d), s2 = wave_sum_u64(sum_d2);
             const u32 c1 = wave_sum_u32(cov_w), c2 = wave_sum_u32(cov_f);
@@ -1425,15 +1448,6 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
                     atomicMin(&C->min_d, m1);
                     atomicMax(&C->max_d, m2);
                 }
-            }
-            if (WANT_HIST && proc_win) {
-                lds_fence();
-                const u32 hi_b = min(m2, (u32)HBW - 1u);
-                for (u32 b = m1 + (u32)lane; b <= hi_b; b += 64) {
-                    const u32 x = lhist[b];
-                    if (x) { atomicAdd(&a.hist_arena[hoff + b], x); lhist[b] = 0u; }
-                }
-                lds_fence();
             }
         }
         sum_d = sum_d2 = 0; proc_win = 0; cov_w = cov_f = 0; mn = 0xffffffffu; mx = 0;
@@ -1523,7 +1537,8 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
             const u32 ws = has_win ? (u32)excl : 0u, we = has_win ? (u32)(L - excl) : 0u;
             const u32 wst = max(ws, lo), wet = min(we, lo + tlen_t);
             const bool win_any = has_win && wst < wet;
-            if (win_any) proc_win += (u64)(wet - wst);
+            if (!WANT_HIST && win_any) proc_win += (u64)(wet - wst);
+            if (WANT_HIST) hbound = max(hbound, min(ds.y - ds.x + cxn, (u32)HBW - 1u));
 
             if (!WRITE_DEPTH && E <= (u32)CAP) {
                 // ---- sparse path.  LDS requests of one wave are served in order, so the entry writes below cannot
@@ -1544,7 +1559,7 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
                 if (lane == 0) {
                     const u32 en = min(E ? (u32)ent[0].x : tlen_t, tlen_t);
                     const u32 a1 = min(en, wl1);
-                    if (a1 > wl0) { mn = 0u; if (WANT_HIST) hist_add(0u, a1 - wl0); }
+                    if (a1 > wl0) { if (WANT_HIST) hist_add(0u, a1 - wl0); else mn = 0u; }
                 }
                 int carry = 0;
                 // Per-tile 32-bit partial sums: while depth < 1024 the products fit 24-bit multiplies (full rate; a
@@ -1563,15 +1578,20 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
                     const bool small = !__any(live && du >= 1024u);
                     if (live) {
                         const u32 s = min((u32)en.x, tlen_t), t_ = min(nxt, tlen_t);
-                        if (d > 0) cov_f += t_ - s;
                         const u32 a0 = max(s, wl0), a1 = min(t_, wl1);
-                        if (a1 > a0) {
-                            const u32 len = a1 - a0;
-                            if (small) { s1t += __umul24(du, len); s2t += __umul24(__umul24(du, du), len); }
-                            else { sum_d += (u64)du * len; sum_d2 += (u64)du * du * len; }
-                            if (d > 0) cov_w += len;
-                            mn = min(mn, du); mx = max(mx, du);
-                            if (WANT_HIST) hist_add(du, len);
+                        if (WANT_HIST) {
+                            const u32 len = a1 > a0 ? a1 - a0 : 0u;      // the segment's window positions
+                            if (d > 0) cov_o += (t_ - s) - len;
+                            if (len) hist_add(du, len);
+                        } else {
+                            if (d > 0) cov_f += t_ - s;
+                            if (a1 > a0) {
+                                const u32 len = a1 - a0;
+                                if (small) { s1t += __umul24(du, len); s2t += __umul24(__umul24(du, du), len); }
+                                else { sum_d += (u64)du * len; sum_d2 += (u64)du * du * len; }
+                                if (d > 0) cov_w += len;
+                                mn = min(mn, du); mx = max(mx, du);
+                            }
                         }
                     }
                 }
@@ -1587,17 +1607,21 @@ __global__ __launch_bounds__(256) void k_pileup_stream(PileupArgs a, u32 n_tiles
                     const u32 p = lo + (u32)(j * 64 + lane);
                     const u32 du = (u32)d;
                     if (p < L) {
-                        cov_f += d > 0;
                         if (WRITE_DEPTH) a.depth_out[dbase + p] = d;
-                        if (win_any && p >= wst && p < wet) {
-                            sum_d += du;
-                            sum_d2 += (u64)du * du;
-                            cov_w += d > 0;
-                            mn = min(mn, du); mx = max(mx, du);
-                            if (WANT_HIST) {
+                        const bool in_w = win_any && p >= wst && p < wet;
+                        if (WANT_HIST) {
+                            if (in_w) {      // change-point form: bin of the depth left of p gains the positions so far, the bin of d loses them
                                 const u32 rel = p - wst;
                                 if (x[j] != 0 && rel) { hist_add((u32)(d - x[j]), rel); hist_add(du, 0u - rel); }
                                 if (p == wet - 1) hist_add(du, wet - wst);
+                            } else cov_o += d > 0;
+                        } else {
+                            cov_f += d > 0;
+                            if (in_w) {
+                                sum_d += du;
+                                sum_d2 += (u64)du * du;
+                                cov_w += d > 0;
+                                mn = min(mn, du); mx = max(mx, du);
                             }
                         }
                     }
@@ -1614,21 +1638,30 @@ constexpr size_t pileup_stream_smem_bytes() { return (size_t)4 * ((size_t)STREAM
 
 // ------------------------------------------------------------------------------------ k_pileup_fast
 // Default pileup.  Same tile / candidate-range / run-word contract as k_pileup_stream (one wave per 1024-base tile,
-// chunks of consecutive tiles, sums kept in registers across the tiles of a contig), different arithmetic:
+// chunks of consecutive tiles) and the same output — with the histogram wanted: the contig's bins in the arena and cov_out, the covered
+// positions outside the window, nothing else (the window statistics are derived from the final bins once per contig: hist_stats_derive);
+// without: explicit sums kept in registers across the tiles of a contig, one set of reductions and atomics per chunk —, different arithmetic:
 //
-//   * two u16 count tables per wave in LDS, S[p] = runs starting at p (clipped to the tile start: the carry-in),
-//     E[p] = runs ending at p.  2 x 2 KiB; one ds_add_u32 per event; a tile with >= 32768 candidates (a u16 could
-//     wrap) is left to k_pileup_stream through the slow-tile list.
-//   * BLOCKED ownership: lane l owns positions [16 l, 16 l + 16) = 32 contiguous bytes of each table, read with two
-//     ds_read_b128.  Depth is then a lane-serial running sum over 16 packed i16 deltas (v_pk_sub_i16 of the two
+//   * u16 count fields per wave in LDS.  The default (TABLES = 1, k_pileup_fast): ONE table of biased deltas, 2 KiB — see the comment
+//     above pileup_fast_body.  The second implementation (TABLES = 2, k_pileup_fast2t): two tables, S[p] = runs starting at p (clipped to
+//     the tile start: the carry-in), E[p] = runs ending at p, 2 x 2 KiB.  One ds_add_u32 / ds_sub_u32 per event either way; a tile with
+//     more than FAST_MAX_CAND candidates (a field could wrap) is left to k_pileup_stream through the slow-tile list.
+//   * BLOCKED ownership: lane l owns positions [16 l, 16 l + 16) = 32 contiguous bytes of a table, read with two
+//     ds_read_b128.  Depth is then a lane-serial running sum over 16 packed i16 deltas (an xor with the bias, or v_pk_sub_i16 of the two
 //     tables) started from ONE wave prefix sum of the per-lane net deltas: one cross-lane scan per tile instead of
 //     one per 64 bases, no ballot / mbcnt compaction, no second LDS round trip.  Per tile the only LDS dependency is
 //     zero -> scatter -> read (LDS serves one wave's requests in order, so no s_waitcnt between them).
-//   * the next tile's descriptor (scalar loads) and run words (two 8-byte vector loads) are requested before the
-//     statistics of the current tile, so HBM latency overlaps the VALU work of the same wave.
-//   * interior tiles (wholly inside the contig and its end-exclusion window) with < 512 candidates take a loop with
-//     32-bit per-tile partial sums and no bounds tests; everything else takes the general loop (window / contig-end
-//     masks, 64-bit sums, histogram overflow to the arena).
+//   * the next tile's run words (two 8-byte vector loads) are requested before the statistics of the current tile, so their HBM latency
+//     overlaps the VALU work of the same wave.  The next tile's DESCRIPTOR is requested at the top of the current tile's step, but it is
+//     wave-uniform data fetched through the vector path (global_load_dwordx4 + v_readfirstlane in the listing, not s_load), and the
+//     run-word addresses depend on it: the wave waits for it at once; the other waves of the SIMD cover that wait.
+//   * tiles with < 512 candidates (depth fits the LDS bins), histogram wanted: one LDS atomic per constant-depth segment and nothing else
+//     per position — interior tiles (wholly inside the contig and its end-exclusion window) without bounds tests, tiles at an end of the
+//     contig or of the window with the segments clipped to the window and a 16-bit mask of covered positions for cov_out; deeper tiles
+//     take a loop with window / contig-end tests per position and histogram overflow to the arena.  A chunk's end moves the bins to the
+//     arena; only a chunk with a contig-end tile has a count to reduce and add.
+//   * no histogram: interior tiles with < 512 candidates take a loop with 32-bit per-tile partial sums and no bounds tests, everything
+//     else the general loop (window / contig-end masks, 64-bit sums).
 //   * histogram: one LDS atomic per constant-depth segment of a lane's 16 positions (depth changes only where a delta
 //     is non-zero).  (Copies of every bin in adjacent words, lane l adding to copy l mod 2 | 4, were measured: 0.62 -> 0.72 / 0.85 ms,
 //     profiles/r04_pileup_hrep.log — what the conflicts cost is less than what the lost occupancy does.)
@@ -1668,29 +1701,22 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
 #pragma unroll
         for (int b = lane; b < HBW; b += 64) lhist[b] = 0u;
     }
-    u64 sum_d = 0, sum_d2 = 0, proc_win = 0;
-    u32 cov_w = 0, cov_f = 0, mn = 0xffffffffu, mx = 0;
+    u64 sum_d = 0, sum_d2 = 0, proc_win = 0;                      // (no histogram only)
+    u32 cov_w = 0, cov_f = 0, mn = 0xffffffffu, mx = 0;           // (no histogram only)
+    u32 cov_o = 0;             // (histogram wanted only) covered positions of the contig outside the window
     int cur_c = -1;
     u64 hoff = 0; u32 hcap = 0;
     const u64 excl = a.excl;
-    // With the histogram wanted, interior tiles do NOT accumulate sum d, sum d^2, covered, min and max per position: every position's
-    // depth goes into the wave's LDS histogram anyway, and the five are read off its bins when they are moved to the arena (`drain`).
-    // The general loop (contig ends, tiles deeper than the bins) counts per position as before, so the bins hold segments of ONE kind at a
-    // time — lh_explicit says which — and are drained when the kind changes.  All wave-uniform.
-    bool lh_explicit = false;
+    // With the histogram wanted the kernel produces the histogram and ONE counter: every window position's depth goes into the contig's bins
+    // (the wave's LDS bins, moved to the arena by `drain`; depths beyond them straight to the arena), and the bins determine sum d, sum d^2,
+    // covered, min, max and the number of window positions seen — derived once per contig from the final bins (hist_stats_derive), not
+    // per position, per chunk or per wave here.  What the bins cannot tell is the covered positions of the contig OUTSIDE the window.
     u32 hbound = 0;            // no LDS bin above this was touched since the last drain (depth <= candidate runs of the tile)
-    auto drain = [&](bool derive) {
+    auto drain = [&]() {
         lds_fence();
         for (u32 b = (u32)lane; b <= hbound; b += 64) {
             const u32 x = lhist[b];
-            if (x) {
-                atomicAdd(&a.hist_arena[hoff + b], x); lhist[b] = 0u;
-                if (derive) {
-                    const u32 cv = b ? x : 0u;
-                    sum_d += (u64)b * x; sum_d2 += (u64)(b * b) * x; cov_w += cv; cov_f += cv;
-                    mn = min(mn, b); mx = max(mx, b);
-                }
-            }
+            if (x) { atomicAdd(&a.hist_arena[hoff + b], x); lhist[b] = 0u; }
         }
         lds_fence();
         hbound = 0;
@@ -1701,10 +1727,20 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
         else hist_add_overflow(a.hist_arena, hoff, hcap, a.g, d, x);
     };
     auto flush = [&]() {
+        if (WANT_HIST) {
+            if (cur_c >= 0) {
+                drain();
+                if (__any(cov_o != 0u)) {      // wave-uniform: only a chunk with a tile at an end of its contig has something to add
+                    const u32 co = wave_sum_u32_dpp(cov_o);
+                    if (lane == 0) atomicAdd(&a.ctg[cur_c].cov_out, co);
+                }
+            }
+            cov_o = 0; hbound = 0;
+            return;
+        }
         if (cur_c >= 0) {
-            if (WANT_HIST && proc_win) drain(!lh_explicit);
             // (DPP sums: a contig of an assembly is a tile or two, so this runs as often as the tile loop does)
-            const bool narrow = !__any((sum_d | sum_d2) >> 56);
+            const bool narrow = !__any((sum_d | sum_d2) >> 50);      // (wave_sum_u56 adds the 64 high halves in 32 bits: below 2^26 each)
             const u64 s1 = narrow ? wave_sum_u56(sum_d) : wave_sum_u64(sum_d), s2 = narrow ? wave_sum_u56(sum_d2) : wave_sum_u64(sum_d2);
             const u32 c1 = wave_sum_u32_dpp(cov_w), c2 = wave_sum_u32_dpp(cov_f);
             const u32 m1 = wave_min_u32_dpp(mn), m2 = wave_max_u32_dpp(mx);
@@ -1721,7 +1757,7 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
                 }
             }
         }
-        sum_d = sum_d2 = 0; proc_win = 0; cov_w = cov_f = 0; mn = 0xffffffffu; mx = 0; hbound = 0; lh_explicit = false;
+        sum_d = sum_d2 = 0; proc_win = 0; cov_w = cov_f = 0; mn = 0xffffffffu; mx = 0;
     };
     auto load_runs = [&](const uint4 &d, uint2 &r0, uint2 &r1) {
         const u32 i0 = d.x + (u32)lane, i1 = i0 + 64u;
@@ -1831,15 +1867,11 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
             const u32 ws = has_win ? (u32)excl : 0u, we = has_win ? (u32)(L - excl) : 0u;
             const u32 wst = max(ws, lo), wet = min(we, lo + tlen_t);
             const bool win_any = has_win && wst < wet;
-            if (win_any) proc_win += (u64)(wet - wst);
+            if (!WANT_HIST && win_any) proc_win += (u64)(wet - wst);
             const bool interior = has_win && lo >= ws && lo + (u32)TW <= we;
             const u32 cand = ds.y - ds.x + cxn;
             const bool fast_tile = interior && cand < (u32)HBW;
-            const bool derive_tile = fast_tile || cand < (u32)HBW;      // (with the histogram wanted) the tile's statistics come off the bins
-            if (WANT_HIST) {
-                if (lh_explicit == derive_tile) { if (proc_win) drain(!lh_explicit); lh_explicit = !derive_tile; }   // the bins change kind
-                hbound = max(hbound, min(cand, (u32)HBW - 1u));
-            }
+            if (WANT_HIST) hbound = max(hbound, min(cand, (u32)HBW - 1u));
             if (WANT_HIST && fast_tile) {
                 // ---- fast loop, histogram wanted: every position is inside the window and depth < 512 = the LDS bins: one atomic per
                 // constant-depth segment of the lane's 16 positions and nothing else
@@ -1854,8 +1886,8 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
                 lds_atomic_add(da, 16u - seg0);
             } else if (WANT_HIST && cand < (u32)HBW) {
                 // ---- a tile at an end of its contig (or of the end-exclusion window), shallow enough for the LDS bins: the same loop with every
-                // segment clipped to the lane's part [wa, wb) of the window, so that the bins still hold window positions only and the window
-                // statistics still come off them (`drain`); the covered positions of the contig OUTSIDE the window — the full-length covered
+                // segment clipped to the lane's part [wa, wb) of the window, so that the bins hold window positions only;
+                // the covered positions of the contig OUTSIDE the window — the full-length covered
                 // count has no end exclusion (estimators.rs:467-502) — are counted from a 16-bit mask of the lane's covered positions.
                 // (Until round 6 such tiles took the general loop below: ~20 instructions per position where this takes ~8; an assembly
                 // of short contigs has no other tiles.)
@@ -1882,7 +1914,24 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
                 }
                 // positions [0, le) without [wa, wb), as bits 15 - j
                 const u32 in_ctg = 0xffffu & ~(0xffffu >> le), in_win = (0xffffu >> wa) & ~(0xffffu >> wb);
-                cov_f += (u32)__popc(covm & in_ctg & ~in_win);
+                cov_o += (u32)__popc(covm & in_ctg & ~in_win);
+            } else if (WANT_HIST) {
+                // ---- a tile deeper than the LDS bins: window and contig-end tests per position, one histogram add per constant-depth segment
+                // of the lane's window positions (depths beyond the LDS bins go to the arena), covered positions outside the window counted
+                const u32 p0 = lo + 16u * (u32)lane;
+                u32 seg0 = 0;          // first window position (lane-relative) of the open constant-depth segment
+                bool seg_open = false;
+#pragma unroll 4
+                for (int j = 0; j < 16; j++) {
+                    const int dj = (j & 1) ? (int)dl[j >> 1].y : (int)dl[j >> 1].x;
+                    const u32 p = p0 + (u32)j;
+                    const bool in_w = win_any && p >= wst && p < wet;
+                    if (seg_open && (dj != 0 || !in_w)) { hist_add((u32)d >> DS, (u32)j - seg0); seg_open = false; }
+                    d += dj;
+                    if (in_w) { if (!seg_open) { seg_open = true; seg0 = (u32)j; } }
+                    else if (p < L) cov_o += d != 0 ? 1u : 0u;
+                }
+                if (seg_open) hist_add((u32)d >> DS, 16u - seg0);
             } else if (fast_tile) {
                 // ---- fast loop, no histogram: every position is inside the window; depth < 512 so 24-bit multiplies and 32-bit
                 // per-tile sums are exact (16 positions x 2^18 per lane)
@@ -1899,16 +1948,13 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
                 }
                 sum_d += s1t; sum_d2 += s2t; cov_w += cv; cov_f += cv;
             } else {
-                // ---- general loop: window and contig-end tests per position, 64-bit sums, histogram overflow
+                // ---- general loop, no histogram: window and contig-end tests per position, 64-bit sums
                 const u32 p0 = lo + 16u * (u32)lane;
-                u32 seg0 = 0;          // first window position (lane-relative) of the open constant-depth segment
-                bool seg_open = false;
 #pragma unroll 4
                 for (int j = 0; j < 16; j++) {
                     const int dj = (j & 1) ? (int)dl[j >> 1].y : (int)dl[j >> 1].x;
                     const u32 p = p0 + (u32)j;
                     const bool in_w = win_any && p >= wst && p < wet;
-                    if (WANT_HIST && seg_open && (dj != 0 || !in_w)) { hist_add((u32)d >> DS, (u32)j - seg0); seg_open = false; }
                     d += dj;
                     const u32 du = (u32)d >> DS;
                     if (p < L) cov_f += du != 0u ? 1u : 0u;
@@ -1916,10 +1962,8 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
                         sum_d += du; sum_d2 += (u64)du * du;
                         cov_w += du != 0u ? 1u : 0u;
                         mn = min(mn, du); mx = max(mx, du);
-                        if (WANT_HIST && !seg_open) { seg_open = true; seg0 = (u32)j; }
                     }
                 }
-                if (WANT_HIST && seg_open) hist_add((u32)d >> DS, 16u - seg0);
             }
         }
         if (chunk_end) { flush(); cur_c = -1; }
@@ -2136,40 +2180,111 @@ __device__ __forceinline__ bool estimate_entry(const EstEntry &E, const BIN *__r
     return nonzero;
 }
 
-// `coverm contig`: entry = contig c.
+// ------------------------------------------------------------------------------------ window statistics from the histogram
+// With the histogram wanted the pileup kernels leave a contig's bins in the arena and cov_out; this derives the rest of its k_pileup
+// fields (hist_stats_core.h) ONCE per contig from the final bins arena[hist_off .. hist_off + hist_cap] and STORES them: sum_d, sum_d2,
+// cov_win, proc_win, min_d, max_d, and cov_full = cov_out + cov_win.  `act`: the contig has a considered record and is not masked out
+// (only then has it bins); without a window no bin is read and the six are those of an empty histogram.  Returns the values — the caller
+// goes on with them in registers (what lane 0 stores is not visible to the other lanes' loads).
+// LANES = false: the whole wave on one contig (every argument wave-uniform), bins lane, lane + 64, ...; every lane returns the totals.
+// LANES = true: a lane per contig walking its own bins; contigs with more than EST_SERIAL_BINS bins are walked by the whole wave, one
+// after the other.  Every lane of the wave must call it.
+__device__ __forceinline__ hstc::Stats hist_stats_wave(const u32 *__restrict__ bins, u64 n) {
+    hstc::Stats s = hstc::of_bins(bins, n, (u32)lane_id(), 64u);
+    // hstc::merge across the 64 lanes.  (DPP sums while every lane's values are below 2^50, so that the 64 high halves wave_sum_u56 adds in 32
+    // bits cannot overflow: the shuffles of wave_sum_u64 go through the LDS crossbar, twelve round trips each, and this runs once per contig
+    // in front of the estimators.)
+    const bool narrow = !__any((s.sum_d | s.sum_d2 | s.proc_win) >> 50);
+    s.sum_d = narrow ? wave_sum_u56(s.sum_d) : wave_sum_u64(s.sum_d);
+    s.sum_d2 = narrow ? wave_sum_u56(s.sum_d2) : wave_sum_u64(s.sum_d2);
+    s.proc_win = narrow ? wave_sum_u56(s.proc_win) : wave_sum_u64(s.proc_win);
+    s.cov_win = narrow ? wave_sum_u56(s.cov_win) : wave_sum_u64(s.cov_win);
+    s.min_d = wave_min_u32_dpp(s.min_d); s.max_d = wave_max_u32_dpp(s.max_d);
+    return s;
+}
 template <bool LANES>
-__device__ __forceinline__ void estimate_body(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
-                                              const u32 *__restrict__ arena, const EstParams &P, float *__restrict__ out) {
+__device__ __forceinline__ hstc::Stats hist_stats_derive(DevContig *C, const u32 *__restrict__ arena, bool act, bool has_win) {
+    const int lane = lane_id();
+    const u64 n = (act && has_win) ? (u64)C->hist_cap + 1 : 0ull;
+    const u32 *bins = arena + (n ? C->hist_off : 0ull);
+    hstc::Stats s = hstc::empty();
+    if (!LANES) s = hist_stats_wave(bins, n);
+    else {
+        const bool serial = n <= (u64)EST_SERIAL_BINS;
+        if (serial) s = hstc::of_bins(bins, n, 0u, 1u);
+        for (u64 bm = __ballot(!serial); bm != 0; bm &= bm - 1) {      // deep contigs: the whole wave on each
+            const int l = __builtin_ctzll(bm);
+            const u64 bp = bcast_u64((u64)(uintptr_t)bins, l);
+            const hstc::Stats t = hist_stats_wave(reinterpret_cast<const u32 *>((uintptr_t)bp), bcast_u64(n, l));
+            if (lane == l) s = t;
+        }
+    }
+    if (act && (LANES || lane == 0)) {
+        C->sum_d = s.sum_d; C->sum_d2 = s.sum_d2; C->cov_win = s.cov_win; C->proc_win = s.proc_win;
+        C->cov_full = (u64)C->cov_out + s.cov_win;
+        C->min_d = s.min_d; C->max_d = s.max_d;
+    }
+    return s;
+}
+// The derivation as a launch of its own, right behind the pileup: for every finish whose estimator kernel does not run first — no
+// estimators, a target mask, the compact histogram (k_hist_off<1> needs max_d), cov_finish_genomes without per-contig floats.
+template <bool LANES>
+__global__ __launch_bounds__(256) void k_hist_stats(DevContig *ctg, u32 n_targets, const u32 *__restrict__ tlen, const uint8_t *__restrict__ mask, u64 excl,
+                                                    const u32 *__restrict__ arena) {
+    const u32 c_raw = LANES ? blockIdx.x * 256u + threadIdx.x : blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (!LANES && c_raw >= n_targets) return;
+    const bool in = c_raw < n_targets;
+    const u32 c = in ? c_raw : n_targets - 1u;        // (LANES: lanes behind the last contig walk along, write nothing)
+    DevContig *C = &ctg[c];
+    const bool act = in && C->n_pass != 0 && (mask == nullptr || mask[c]);
+    if (!LANES && !act) return;
+    (void)hist_stats_derive<LANES>(C, arena, act, 2 * excl < (u64)tlen[c]);
+}
+
+// `coverm contig`: entry = contig c.  `derive`: the pileup ran with the histogram wanted and nothing has derived the contigs' window
+// statistics yet (no k_hist_stats launch): this kernel does, as its prologue, and writes them for the readers behind it.
+template <bool LANES>
+__device__ __forceinline__ void estimate_body(DevContig *ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
+                                              const u32 *__restrict__ arena, const EstParams &P, float *__restrict__ out, bool derive) {
     const int lane = lane_id();
     const u32 c_raw = LANES ? blockIdx.x * 256u + threadIdx.x : blockIdx.x * 4u + (threadIdx.x >> 6);
     if (!LANES && c_raw >= n_targets) return;
     const bool in = c_raw < n_targets;
     const u32 c = in ? c_raw : n_targets - 1u;        // (LANES: lanes behind the last contig walk along, write nothing)
-    const DevContig *C = &ctg[c];
+    DevContig *C = &ctg[c];
     float *o = out + (size_t)c * P.n;
     const bool touched = C->n_pass != 0;
     if (!LANES && !touched) { if ((u32)lane < P.n) o[lane] = 0.0f; return; }     // (the host prints such a contig through print_zero_coverage)
     // the integer statistics as convert_results + EntryAcc::add_contig would hand them to calculate (host_coverage.cpp)
     const u64 L = tlen[c];
     const bool has_win = 2 * excl < L;
+    hstc::Stats S;
+    u64 cov_full;
+    if (derive) {
+        S = hist_stats_derive<LANES>(C, arena, in && touched, has_win);
+        cov_full = (u64)C->cov_out + S.cov_win;
+    } else {
+        S.sum_d = C->sum_d; S.sum_d2 = C->sum_d2; S.cov_win = C->cov_win; S.proc_win = C->proc_win; S.min_d = C->min_d; S.max_d = C->max_d;
+        cov_full = C->cov_full;
+    }
     EstEntry E;
     E.win_len = has_win ? L - 2 * excl : 0;
-    E.win_sum_d = has_win ? C->sum_d : 0; E.win_sum_d2 = has_win ? C->sum_d2 : 0; E.win_covered = has_win ? C->cov_win : 0;
-    E.win_min_d = has_win ? ((C->proc_win < E.win_len || C->min_d == 0xffffffffu) ? 0u : C->min_d) : 0xffffffffu;
-    E.full_len = L; E.full_covered = C->cov_full; E.n_reads = C->n_primary; E.mismatches = C->sum_nm - C->sum_indel;
-    E.nh = has_win ? C->max_d + 1u : 0u;              // = the compact histogram's length (k_hist_off<1>; no target mask here)
-    E.bin0_extra = E.win_len - C->proc_win;           // window positions of tiles no record touched: depth 0 (k_hist_compact adds the same)
+    E.win_sum_d = has_win ? S.sum_d : 0; E.win_sum_d2 = has_win ? S.sum_d2 : 0; E.win_covered = has_win ? S.cov_win : 0;
+    E.win_min_d = has_win ? ((S.proc_win < E.win_len || S.min_d == 0xffffffffu) ? 0u : S.min_d) : 0xffffffffu;
+    E.full_len = L; E.full_covered = cov_full; E.n_reads = C->n_primary; E.mismatches = C->sum_nm - C->sum_indel;
+    E.nh = has_win ? S.max_d + 1u : 0u;               // = the compact histogram's length (k_hist_off<1>; no target mask here)
+    E.bin0_extra = E.win_len - S.proc_win;            // window positions of tiles no record touched: depth 0 (k_hist_compact adds the same)
     E.unobs_win = 0; E.unobs_full = 0;                // unobserved lengths [0] (contig.rs:62-66)
     E.identity = C->id_primary;
     (void)estimate_entry<LANES, u32>(E, arena + C->hist_off, in, touched, P, o);
 }
-__global__ __launch_bounds__(256) void k_estimate(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
-                                                  const u32 *__restrict__ arena, EstParams P, float *__restrict__ out) {
-    estimate_body<false>(ctg, n_targets, tlen, excl, arena, P, out);
+__global__ __launch_bounds__(256) void k_estimate(DevContig *ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
+                                                  const u32 *__restrict__ arena, EstParams P, float *__restrict__ out, u32 derive) {
+    estimate_body<false>(ctg, n_targets, tlen, excl, arena, P, out, derive != 0u);
 }
-__global__ __launch_bounds__(256) void k_estimate_lanes(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
-                                                        const u32 *__restrict__ arena, EstParams P, float *__restrict__ out) {
-    estimate_body<true>(ctg, n_targets, tlen, excl, arena, P, out);
+__global__ __launch_bounds__(256) void k_estimate_lanes(DevContig *ctg, u32 n_targets, const u32 *__restrict__ tlen, u64 excl,
+                                                        const u32 *__restrict__ arena, EstParams P, float *__restrict__ out, u32 derive) {
+    estimate_body<true>(ctg, n_targets, tlen, excl, arena, P, out, derive != 0u);
 }
 
 // ------------------------------------------------------------------------------------ interval statistics
