@@ -32,6 +32,7 @@
 #include "knobs.h"
 #include "record_store.h"
 #include "store_plan_core.h"
+#include "finish_plan_core.h"
 
 using namespace covk;
 
@@ -271,7 +272,7 @@ struct cov_session {
     uint32_t k_launches[COV_K_COUNT] = {};
 };
 
-static cov_status spill_store(cov_session *s, bool &progress);      // bounded record store (defined behind finish_once)
+static cov_status spill_store(cov_session *s, bool &progress);      // bounded record store (defined behind finish_once and its stages)
 
 namespace {
 
@@ -282,6 +283,15 @@ size_t result_block_bytes(u32 n_targets) { return sizeof(DevGlobal) + (size_t)st
 static size_t result_host_bytes(const cov_session *s, u32 nT) {
     // (with a target mask no per-contig floats come back — the entries are genomes — so the block does not grow with the estimators)
     return result_block_bytes(nT) + (size_t)std::max<u32>(nT, 1) * ((s->have_mask || s->have_runs) ? 1u : std::max<u32>(s->est.n, 1u)) * sizeof(float);
+}
+// A page-locked buffer grows: freed, then allocated for n elements (the content is not kept; cap = 0 when the allocation fails).
+template <class T, class N>
+static hipError_t pinned_grow(T *&p, N &cap, N n) {
+    if (p) (void)hipHostFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipHostMalloc((void **)&p, (size_t)n * sizeof(T), hipHostMallocDefault);
+    if (e == hipSuccess) cap = n;
+    return e;
 }
 static void result_host_take(cov_session *s) {
     if (!s->h_res_prep.valid()) return;
@@ -388,30 +398,40 @@ void time_begin(cov_session *s, int k) {
 }
 void time_end(cov_session *s, int k) { (void)hipEventRecord(s->ev[k][1], s->stream); s->k_launches[k]++; s->ev_fresh = k; }
 
-// k_pileup_fast over every tile (it skips the ones k_ranges flagged TILE_F_SLOW)
-template <bool H, int TABLES>
-void launch_fast_v(cov_session *s, const PileupArgs &a, u32 n_tiles) {
-    const auto kern = TABLES == 1 ? &k_pileup_fast<H> : &k_pileup_fast2t<H>;
-    const size_t smem = pileup_fast_smem_bytes(H, TABLES == 1 ? FAST_HB : FAST_HB7, TABLES);
-    // the dynamic-LDS limit and the occupancy are per-device facts, and span mode launches from one thread per device: cached per
-    // device id, in atomics (two threads racing for the same device compute the same value)
-    static std::atomic<int> occ_dev[64];
+// Resident workgroups per CU of a pileup kernel that takes `smem` bytes of dynamic LDS (allowed here, before its first launch).  The
+// dynamic-LDS limit and the occupancy are per-device facts, and span mode launches from one thread per device: cached per device id, in
+// atomics (two threads racing for the same device compute the same value); the caller owns one cache per kernel instantiation.
+int pileup_occupancy(const cov_session *s, std::atomic<int> (&occ_dev)[64], const void *kern, size_t smem) {
     std::atomic<int> &occ_slot = occ_dev[(unsigned)s->cfg.device & 63u];
     int occ = occ_slot.load(std::memory_order_relaxed);
-    const u32 chunk = (u32)s->chunk_tiles;
-    const u32 n_chunks = (n_tiles + chunk - 1) / chunk;
     if (!occ) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+        (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(kern), 256, smem) != hipSuccess || nb < 1) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, smem) != hipSuccess || nb < 1) {
             (void)hipGetLastError();
             nb = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / smem));
         }
         occ = nb; occ_slot.store(nb, std::memory_order_relaxed);
     }
-    const u32 wg_per_cu = 8u * (u32)occ;
-    const u32 grid = std::max(1u, std::min((n_chunks + 3) / 4, (u32)s->n_cus * wg_per_cu));
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), smem, s->stream, a, n_tiles, chunk);
+    return occ;
+}
+// Grid = 8x the resident workgroups (registers, not LDS, bound residency): each wave still walks several chunks
+// and keeps its sums in registers across them, but the hardware dispatcher hands out the 8 successive "rounds",
+// which evens out the heavy-tailed per-chunk cost far better than a purely persistent grid (measured, 50 M reads:
+// 1.06 ms at 1x, 0.905 ms at 8x, 0.956 ms at one chunk per wave).
+u32 pileup_grid(const cov_session *s, int occ, u32 n_tiles) {
+    const u32 n_chunks = (n_tiles + (u32)s->chunk_tiles - 1) / (u32)s->chunk_tiles, wg_per_cu = 8u * (u32)occ;
+    return std::max(1u, std::min((n_chunks + 3) / 4, (u32)s->n_cus * wg_per_cu));
+}
+
+// k_pileup_fast over every tile (it skips the ones k_ranges flagged TILE_F_SLOW)
+template <bool H, int TABLES>
+void launch_fast_v(cov_session *s, const PileupArgs &a, u32 n_tiles) {
+    const auto kern = TABLES == 1 ? &k_pileup_fast<H> : &k_pileup_fast2t<H>;
+    const size_t smem = pileup_fast_smem_bytes(H, TABLES == 1 ? FAST_HB : FAST_HB7, TABLES);
+    static std::atomic<int> occ_dev[64];
+    const int occ = pileup_occupancy(s, occ_dev, reinterpret_cast<const void *>(kern), smem);
+    hipLaunchKernelGGL(kern, dim3(pileup_grid(s, occ, n_tiles)), dim3(256), smem, s->stream, a, n_tiles, (u32)s->chunk_tiles);
 }
 template <bool H>
 void launch_fast_t(cov_session *s, const PileupArgs &a, u32 n_tiles) {
@@ -422,33 +442,15 @@ void launch_fast_t(cov_session *s, const PileupArgs &a, u32 n_tiles) {
 template <bool H, bool W>
 void launch_stream_t(cov_session *s, const PileupArgs &a, u32 n_tiles, bool slow_list_only = false) {
     const size_t smem = pileup_stream_smem_bytes();
-    static std::atomic<int> occ_dev[64];       // per device id, as in launch_fast_t
-    std::atomic<int> &occ_slot = occ_dev[(unsigned)s->cfg.device & 63u];
-    int occ = occ_slot.load(std::memory_order_relaxed);
-    const u32 chunk = (u32)s->chunk_tiles;
-    const u32 n_chunks = (n_tiles + chunk - 1) / chunk;
-    // Grid = 8x the resident workgroups (registers, not LDS, bound residency): each wave still walks several chunks
-    // and keeps its sums in registers across them, but the hardware dispatcher hands out the 8 successive "rounds",
-    // which evens out the heavy-tailed per-chunk cost far better than a purely persistent grid (measured, 50 M reads:
-    // 1.06 ms at 1x, 0.905 ms at 8x, 0.956 ms at one chunk per wave).
-    if (!occ) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_pileup_stream<H, W>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, reinterpret_cast<const void *>(&k_pileup_stream<H, W>), 256, smem) != hipSuccess || nb < 1) {
-            (void)hipGetLastError();
-            nb = (int)std::max<size_t>(1, std::min<size_t>(8, (160 * 1024) / smem));
-        }
-        occ = nb; occ_slot.store(nb, std::memory_order_relaxed);
-    }
-    const u32 wg_per_cu = 8u * (u32)occ;
+    static std::atomic<int> occ_dev[64];
+    const int occ = pileup_occupancy(s, occ_dev, reinterpret_cast<const void *>(&k_pileup_stream<H, W>), smem);
     if (slow_list_only) {   // the listed tiles only, one per wave step; the count lives on the device (usually 0: waves exit at once)
         hipLaunchKernelGGL((k_pileup_stream<H, W>), dim3((u32)s->n_cus), dim3(256), smem, s->stream, a, 0u, 1u,
                            (const u32 *)s->d_slow_list.p, (const u32 *)&s->d_glob.p->n_slow);
         return;
     }
-    const u32 grid = std::max(1u, std::min((n_chunks + 3) / 4, (u32)s->n_cus * wg_per_cu));
-    hipLaunchKernelGGL((k_pileup_stream<H, W>), dim3(grid), dim3(256), smem, s->stream, a, n_tiles, chunk, (const u32 *)nullptr,
-                       (const u32 *)nullptr);
+    hipLaunchKernelGGL((k_pileup_stream<H, W>), dim3(pileup_grid(s, occ, n_tiles)), dim3(256), smem, s->stream, a, n_tiles, (u32)s->chunk_tiles,
+                       (const u32 *)nullptr, (const u32 *)nullptr);
 }
 // dispatches to the configured pileup kernel
 template <bool H, bool W>
@@ -459,12 +461,63 @@ void launch_any_pileup(cov_session *s, const PileupArgs &a, u32 n_tiles) {
     } else launch_stream_t<H, W>(s, a, n_tiles);
 }
 
+const uint8_t *device_mask(const cov_session *s) { return s->have_mask ? s->d_mask.p : nullptr; }
+
+// The compact histogram from the arena's bins: the contigs' compact offsets (a block's total, then its scan), then the bins moved
+// (d_hist_top and d_chist are sized by the caller: inside a finish, or on the first cov_fetch_hist behind one that left the bins in the arena)
+void launch_hist_compact(cov_session *s, const uint8_t *mask, u64 excl) {
+    const u32 nT = s->n_targets, hb = (nT + 1023u) / 1024u;
+    hipLaunchKernelGGL((k_hist_sum<1>), dim3(hb), dim3(1024), 0, s->stream, (const DevContig *)s->d_ctg.p, nT, s->d_tlen.p, mask, excl, s->d_hist_top.p);
+    hipLaunchKernelGGL((k_hist_off<1>), dim3(hb), dim3(1024), 0, s->stream, s->d_ctg.p, nT, s->d_tlen.p, mask, excl, (const u64 *)s->d_hist_top.p, s->d_glob.p);
+    hipLaunchKernelGGL(k_hist_compact, dim3((nT + 3u) / 4u), dim3(256), 0, s->stream, s->d_ctg.p, nT, s->d_tlen.p, excl, s->d_arena.p, s->d_chist.p);
+}
+
 PileupArgs pileup_args(cov_session *s) {
     PileupArgs a{};
     a.tile_contig = s->d_tile_contig.p; a.tile_start = s->d_tile_start.p; a.desc = s->d_desc.p;
     a.runs = s->d_runs.p; a.cx_runs = s->d_cx_runs.p; a.r = records_of(s); a.ctg = s->d_ctg.p; a.g = s->d_glob.p;
     a.hist_arena = s->d_arena.p; a.excl = s->cfg.contig_end_exclusion; a.depth_out = nullptr; a.tile_base = 0;
     return a;
+}
+
+using finplan::FinishPlan;
+static_assert(finplan::LEAN_PASSES == 2 * PREP_PASSES, "finish_plan_core.h sizes k_prep_lean's workgroups");
+
+// The device views of one pass over the store, built once (stage_begin) and read by every stage.
+struct PassViews {
+    hipStream_t st = nullptr;
+    u32 R = 0, nT = 0;
+    Records r{};
+    const uint8_t *mask = nullptr;     // the target mask on the device, when there is one
+    u64 excl = 0;                      // cov_config::contig_end_exclusion
+    TileIdx ti{};
+    CxIdx cx{};
+    double *idp = nullptr, *idn = nullptr;      // identity streams actually needed (NULL = skipped by k_prep and the k_id_* kernels)
+    FilterCfg f{};
+    PrepArgs pa{};
+    size_t block = 0;                  // bytes of [DevGlobal][DevContig x nT]: the estimators' floats lie behind it, in d_res and in h_res
+};
+
+// The prep kernels of one <IDENTITY, FILTER, MASKED>: k_prep7s, or k_prep_generic over every step, or k_prep_lean and k_prep_generic over its list.
+template <bool ID, bool FI, bool MA>
+void launch_prep(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    const PrepArgs *pa = s->d_prep_args.p;
+    if (p.prep7)
+        hipLaunchKernelGGL((k_prep7s<ID, FI, MA>), dim3(p.prep_grid), dim3(256), 0, v.st, v.r, s->d_tlen.p, v.nT, v.mask, v.f, s->d_ctg.p,
+                           s->d_glob.p, s->d_runs.p, v.idp, v.idn, s->d_part.p, v.ti, p.prep_passes, p.prep_b, v.cx.list, v.cx.list_cap);
+    else if (p.gen_all)
+        hipLaunchKernelGGL((k_prep_generic<ID, FI, MA>), dim3(p.gen_grid), dim3(256), 0, v.st, pa, p.n_steps);
+    else {
+        hipLaunchKernelGGL((k_prep_lean<ID, FI, MA>), dim3(p.prep_grid), dim3(256), 0, v.st, v.pa.hot, pa);
+        hipLaunchKernelGGL((k_prep_generic<ID, FI, MA>), dim3(p.gen_grid), dim3(256), 0, v.st, pa, 0u);
+    }
+}
+// key = IDENTITY << 2 | FILTER << 1 | MASKED: one bit after the other becomes a template argument, which names the eight instantiations
+template <int KEY = 0, int BIT = 4>
+void launch_prep_key(int key, cov_session *s, const FinishPlan &p, const PassViews &v) {
+    if constexpr (BIT == 0) launch_prep<(KEY & 4) != 0, (KEY & 2) != 0, (KEY & 1) != 0>(s, p, v);
+    else if (key & BIT) launch_prep_key<KEY | BIT, BIT / 2>(key, s, p, v);
+    else launch_prep_key<KEY, BIT / 2>(key, s, p, v);
 }
 
 }  // namespace
@@ -586,7 +639,7 @@ void cov_destroy(cov_session *s) {
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
     s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
     s->d_cx_list.release(); s->d_cx_cnt.release(); s->d_cx_cur.release(); s->d_cx_scan.release(); s->d_cx_top.release(); s->d_cx_runs.release();
-    if (s->side) {     // before ing_aux goes: `side` may be that very stream (finish_once borrows the idle ingest stream)
+    if (s->side) {     // before ing_aux goes: `side` may be that very stream (stage_identity_side borrows the idle ingest stream)
         (void)hipStreamSynchronize(s->side);
         if (s->side_owned) (void)hipStreamDestroy(s->side);
         s->side = nullptr; s->side_owned = false;
@@ -756,12 +809,7 @@ cov_status cov_set_genomes(cov_session *s, const int32_t *genome_of_tid, uint32_
     }
     HIPCHK(hipStreamSynchronize(st));
     const size_t need = (size_t)n_genomes * (sizeof(cov_genome_stats) + COV_EST_MAX * sizeof(float));
-    if (need > s->h_gout_cap) {
-        if (s->h_gout) (void)hipHostFree(s->h_gout);
-        s->h_gout = nullptr; s->h_gout_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&s->h_gout, need, hipHostMallocDefault));
-        s->h_gout_cap = need;
-    }
+    if (need > s->h_gout_cap) HIPCHK(pinned_grow(s->h_gout, s->h_gout_cap, need));
     s->n_genomes = n_genomes; s->n_gseg = (uint32_t)n_seg;
     s->have_genomes = true;
     return COV_OK;
@@ -799,12 +847,7 @@ cov_status cov_set_genome_runs(cov_session *s, const int32_t *gid_of_tid, uint32
         HIPCHK(hipMemcpyAsync(s->d_sblk.p, blk.data(), (size_t)nT * 4, hipMemcpyHostToDevice, st));
     }
     HIPCHK(hipStreamSynchronize(st));
-    if (need > s->h_gout_cap) {
-        if (s->h_gout) (void)hipHostFree(s->h_gout);
-        s->h_gout = nullptr; s->h_gout_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&s->h_gout, need, hipHostMallocDefault));
-        s->h_gout_cap = need;
-    }
+    if (need > s->h_gout_cap) HIPCHK(pinned_grow(s->h_gout, s->h_gout_cap, need));
     s->finished = false;
     s->n_gids = n_gids; s->sep_ent_cap = (uint32_t)ent_cap; s->sep_seg_cap = (uint32_t)seg_cap; s->n_genomes = 0;
     s->have_runs = true;
@@ -874,6 +917,35 @@ cov_status cov_reset(cov_session *s) {
     return COV_OK;
 }
 
+// The verdicts of a finished pipeline in their precedence: internal error, the order rule when it breaks no later than the first erroring
+// record (the reference panics at the first offending record, in file order), that record's error.  unsorted_at = ~0: the order holds.
+static cov_status record_verdict(cov_session *s, const DevGlobal &G, uint64_t unsorted_at, uint64_t rec_base) {
+    if (G.internal_error) { s->err = "internal error: depth or histogram size exceeded its proven bound"; return COV_ERR_STATE; }
+    uint64_t err_rec = ~0ull; int err_code = 0;
+    if (G.first_error != ~0ull) { err_rec = G.first_error >> 8; err_code = (int)(G.first_error & 0xff); }
+    if (unsorted_at != ~0ull && unsorted_at <= err_rec) {
+        s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
+        return COV_ERR_UNSORTED;
+    }
+    if (err_code) {
+        char b[256];
+        const char *what = err_code == 2 ? "Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format"
+                         : err_code == 3 ? "Unexpected data type of NM aux tag"
+                         : err_code == 4 ? "aligned block starts at or beyond the end of its reference sequence"
+                         : err_code == 7 ? "record refers to a reference id outside the header (Corrupt BAM file?)"
+                                         : "invalid CIGAR operation";
+        snprintf(b, sizeof b, "%s (record %llu)", what, (unsigned long long)(err_rec + rec_base));
+        s->err = b;
+        return (cov_status)err_code;
+    }
+    return COV_OK;
+}
+static void summary_of(const DevGlobal &G, uint64_t n_records, uint64_t hist_total, cov_summary *summary) {
+    uint64_t prim = 0, cons = 0;
+    for (u32 k = 0; k < COUNTER_SLOTS * 8; k++) { prim += G.prim_slots[k]; cons += G.cons_slots[k]; }
+    summary->num_detected_primary_alignments = prim; summary->n_records = n_records; summary->n_considered = cons; summary->hist_total = hist_total;
+}
+
 // Host side of a finished pipeline: error checks in file order, sortedness, DevContig -> cov_contig_stats.  Used for the
 // session's own results and for the blocks cov_gather collected from other ranks.
 // `min_ok_tid` / `rec_base`: the session's own results after a spill (bounded record store) — a considered contig below the contig that
@@ -883,10 +955,7 @@ static cov_status convert_results(cov_session *s, const DevGlobal &G, const DevC
                                   cov_summary *summary, int64_t min_ok_tid = -1, uint64_t rec_base = 0) {
     const u32 nT = s->n_targets;
     const bool want_hist = s->cfg.want & COV_WANT_HIST;
-    if (G.internal_error) { s->err = "internal error: depth or histogram size exceeded its proven bound"; return COV_ERR_STATE; }
-    // errors in file order (the reference panics at the first offending record)
-    uint64_t err_rec = ~0ull; int err_code = 0;
-    if (G.first_error != ~0ull) { err_rec = G.first_error >> 8; err_code = (int)(G.first_error & 0xff); }
+    if (G.internal_error) return record_verdict(s, G, ~0ull, rec_base);
     // The two passes below walk every contig; above 64 k contigs (assemblies: 10^5 - 10^7 of them) they run on a few threads — each chunk
     // first leaves what the chunks behind it need from it (its largest last record, its histogram bins), then every chunk runs the
     // serial loop from the prefix of the chunks in front of it.  (One thread until round 6: 2 M contigs cost ~50 ms per finish.)
@@ -935,21 +1004,8 @@ static cov_status convert_results(cov_session *s, const DevGlobal &G, const DevC
         });
         uint64_t unsorted_at = ~0ull;
         for (u32 k = 0; k < n_chunks; k++) unsorted_at = std::min(unsorted_at, ch_unsorted[k]);
-        if (unsorted_at != ~0ull && unsorted_at <= err_rec) {
-            s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
-            return COV_ERR_UNSORTED;
-        }
-    }
-    if (err_code) {
-        char b[256];
-        const char *what = err_code == 2 ? "Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format"
-                         : err_code == 3 ? "Unexpected data type of NM aux tag"
-                         : err_code == 4 ? "aligned block starts at or beyond the end of its reference sequence"
-                         : err_code == 7 ? "record refers to a reference id outside the header (Corrupt BAM file?)"
-                                         : "invalid CIGAR operation";
-        snprintf(b, sizeof b, "%s (record %llu)", what, (unsigned long long)(err_rec + rec_base));
-        s->err = b;
-        return (cov_status)err_code;
+        const cov_status v = record_verdict(s, G, unsorted_at, rec_base);
+        if (v != COV_OK) return v;
     }
     uint64_t hist_total = 0;
     std::vector<uint64_t> ch_total(n_chunks, 0);
@@ -980,44 +1036,16 @@ static cov_status convert_results(cov_session *s, const DevGlobal &G, const DevC
         ch_total[k] = hist_run;
     });
     hist_total = ch_total[n_chunks - 1];
-    if (summary) {
-        uint64_t prim = 0, cons = 0;
-        for (u32 k = 0; k < COUNTER_SLOTS * 8; k++) { prim += G.prim_slots[k]; cons += G.cons_slots[k]; }
-        summary->num_detected_primary_alignments = prim;
-        summary->n_records = n_records;
-        summary->n_considered = cons;
-        summary->hist_total = hist_total;
-    }
+    if (summary) summary_of(G, n_records, hist_total, summary);
     return COV_OK;
 }
 
 // convert_results without the per-contig block (cov_finish_genomes): the same verdicts in the same precedence — internal error, the order
 // rule when it breaks no later than the first erroring record, that record's error — from DevGlobal and k_order_check's word.
 static cov_status verdict_results(cov_session *s, const DevGlobal &G, uint64_t unsorted_at, uint64_t n_records, cov_summary *summary) {
-    if (G.internal_error) { s->err = "internal error: depth or histogram size exceeded its proven bound"; return COV_ERR_STATE; }
-    uint64_t err_rec = ~0ull; int err_code = 0;
-    if (G.first_error != ~0ull) { err_rec = G.first_error >> 8; err_code = (int)(G.first_error & 0xff); }
-    if (unsorted_at != ~0ull && unsorted_at <= err_rec) {
-        s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
-        return COV_ERR_UNSORTED;
-    }
-    if (err_code) {
-        char b[256];
-        const char *what = err_code == 2 ? "Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format"
-                         : err_code == 3 ? "Unexpected data type of NM aux tag"
-                         : err_code == 4 ? "aligned block starts at or beyond the end of its reference sequence"
-                         : err_code == 7 ? "record refers to a reference id outside the header (Corrupt BAM file?)"
-                                         : "invalid CIGAR operation";
-        snprintf(b, sizeof b, "%s (record %llu)", what, (unsigned long long)err_rec);
-        s->err = b;
-        return (cov_status)err_code;
-    }
-    if (summary) {
-        uint64_t prim = 0, cons = 0;
-        for (u32 k = 0; k < COUNTER_SLOTS * 8; k++) { prim += G.prim_slots[k]; cons += G.cons_slots[k]; }
-        summary->num_detected_primary_alignments = prim; summary->n_records = n_records; summary->n_considered = cons; summary->hist_total = 0;
-    }
-    return COV_OK;
+    const cov_status v = record_verdict(s, G, unsorted_at, 0);
+    if (v == COV_OK && summary) summary_of(G, n_records, 0, summary);
+    return v;
 }
 
 static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summary *summary, bool &again);
@@ -1054,370 +1082,380 @@ cov_status cov_finish_genomes(cov_session *s, cov_summary *summary) {
     return st;
 }
 
-static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summary *summary, bool &again) {
-    again = false;
-    if (!s || (!stats && s->n_targets && !s->lean_finish)) return COV_ERR_INVALID_ARG;
-    const bool lean = s->lean_finish;
+// ---- one pass of the device pipeline over what the store holds.  Its decisions are taken once (finish_plan_core.h), its device views are
+// built once (PassViews), and finish_once below is the list of its stages in stream order.
+static finplan::Facts finish_facts(const cov_session *s) {
+    finplan::Facts f;
+    f.R = (u32)s->store.n_records; f.nT = s->n_targets; f.n_tiles = s->n_tiles;
+    f.ncig = s->adopted ? s->adopted_ncig : s->store.n_cigar;
+    f.want = s->cfg.want; f.est_n = s->est.n; f.est_lanes_knob = s->est_lanes; f.prep_kernel = s->prep_kernel; f.n_cus = s->n_cus;
+    f.have_mask = s->have_mask; f.have_runs = s->have_runs; f.have_genomes = s->have_genomes;
+    f.spill_active = s->spill.active; f.in_spill = s->in_spill; f.lean_finish = s->lean_finish; f.hist_fetch_seen = s->hist_fetch_seen;
+    return f;
+}
+
+static FilterCfg filter_of(const cov_config &c) {
+    FilterCfg f{};
+    f.include_improper_pairs = c.include_improper_pairs; f.include_supplementary = c.include_supplementary;
+    f.include_secondary = c.include_secondary; f.filter_single = c.filter_single;
+    f.min_mapq = c.min_mapq; f.min_aligned_length = c.min_aligned_length;
+    f.min_percent_identity = c.min_percent_identity; f.min_aligned_percent = c.min_aligned_percent;
+    return f;
+}
+
+// k_prep_lean's arguments (k_init writes them to device memory for its rare branches and for k_prep_generic), from the views filled so far
+static PrepArgs prep_args_of(const cov_session *s, const FinishPlan &p, const PassViews &v) {
+    PrepArgs pa{};
+    const Records &r = v.r; const FilterCfg &f = v.f;
+    PrepHot &ph = pa.hot;
+    ph.tid = r.tid; ph.pos = r.pos; ph.flag = r.flag; ph.nmk = r.nm_kind; ph.nm = r.nm; ph.coff = r.cigar_off; ph.cigar = r.cigar; ph.mapq = r.mapq; ph.lseq = r.l_seq;
+    ph.runs = s->d_runs.p; ph.tcnt = v.ti.tcnt; ph.fov = v.ti.fov; ph.identp = v.idp; ph.identn = v.idn;
+    ph.n = r.n; ph.cigar_end = r.cigar_end; ph.n_targets = v.nT; ph.shift = v.ti.shift; ph.steps = p.prep_chunk / 256u;
+    ph.gate_mask = 0x4u | (f.include_secondary ? 0u : 0x100u) | (f.include_supplementary ? 0u : 0x800u) | (f.include_improper_pairs ? 0u : 0x2u);
+    ph.p1_mask = 0x4u | (f.include_secondary ? 0u : 0x100u) | (f.include_supplementary ? 0u : 0x800u);
+    ph.min_mapq = f.min_mapq; ph.min_aligned_length = f.min_aligned_length; ph.min_percent_identity = f.min_percent_identity; ph.min_aligned_percent = f.min_aligned_percent;
+    PrepCold &pc = pa.cold;
+    pc.ctg = s->d_ctg.p; pc.g = s->d_glob.p; pc.part = s->d_part.p; pc.cx_list = v.cx.list; pc.mask = v.mask; pc.tlen = s->d_tlen.p; pc.tile_first = s->d_tile_first.p;
+    pc.cx_list_cap = v.cx.list_cap; pc.gen_list = s->d_gen_list.p;
+    return pa;
+}
+
+// Stage 1: the session's state of a pass, the buffers sized by the records, the views, k_init.
+static cov_status stage_begin(cov_session *s, const FinishPlan &p, PassViews &v) {
     s->depth_all_valid = false;
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
-    hipStream_t st = s->stream;
-    const u32 nT = s->n_targets;
-    const u32 R = (u32)s->store.n_records;
-    const bool want_hist = s->cfg.want & COV_WANT_HIST, want_id = s->cfg.want & COV_WANT_IDENTITY;
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
-    bool compacted = false;      // the compact histogram was built by this pass (else: by the first cov_fetch_hist)
-    bool derive_in_est = false;  // the estimator kernel derives the contigs' window statistics from their bins (else k_hist_stats did, or there are none)
-    const bool est_lanes = s->est_lanes < 0 ? nT >= 65536u : s->est_lanes == 1;      // an assembly: a lane per contig (pileup_kernels.hip.h, estimate_body)
     s->est_valid = false; s->gen_valid = false;
-    s->ev_fresh = -1;
-
+    s->ev_fresh = -1;      // a new pass: no group's end event is the last thing on the stream
+    hipStream_t st = v.st = s->stream;
+    const u32 R = v.R = (u32)s->store.n_records, nT = v.nT = s->n_targets;
     HIPCHK(s->d_runs.reserve(std::max<size_t>(1, R), st));
-    // k_prep geometry: 4096 records per workgroup for short reads (k_prep_lean: each of the four waves walks 16 steps of 64 consecutive records;
-    // k_prep7s: 16 passes of 256); one step / pass when CIGARs are long, where the work per record is large and records are few (long-read
-    // mappings), so that every CU gets workgroups
-    const uint64_t ncig_all = s->adopted ? s->adopted_ncig : s->store.n_cigar;
-    const bool long_cigars = R && ncig_all / R >= 16;
-    const int prep_kernel = s->prep_kernel;
-    const int prep_passes = long_cigars ? 1 : 2 * PREP_PASSES, prep_b = 1;
-    const u32 prep_chunk = (u32)(256 * prep_b * prep_passes);
-    const u32 prep_grid = (R + prep_chunk - 1) / prep_chunk;
-    HIPCHK(s->d_part.reserve((size_t)prep_grid + 2, st));
-    if (want_id) {
-        if (!(s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY)) HIPCHK(s->d_ident.reserve(std::max<size_t>(1, R), st));
-        if (!(s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY)) HIPCHK(s->d_identp.reserve(std::max<size_t>(1, R), st));
-        HIPCHK(s->d_idch.reserve((size_t)R / ID_CH + 2, st));
-    }
-    if (want_hist) HIPCHK(s->d_arena.reserve((size_t)R + nT + 1, st));
-
-    TileIdx ti{};
-    ti.tile_first = s->d_tile_first.p; ti.tcnt = s->d_tcnt.p; ti.fov = s->d_fov.p; ti.shift = s->tile_shift; ti.n_tiles = s->n_tiles;
-    CxIdx cx{};
-    {
-        const uint64_t ncig_now = s->adopted ? s->adopted_ncig : s->store.n_cigar;
-        HIPCHK(s->d_cx_list.reserve((size_t)(ncig_now / CX_MIN_OPS) + 64, st));
-        cx.list = s->d_cx_list.p; cx.list_cap = (u32)std::min<uint64_t>(ncig_now / CX_MIN_OPS + 64, 0xffffffffull);
-        cx.cnt = s->d_cx_cnt.p; cx.cur = s->d_cx_cur.p; cx.cscan = s->d_cx_scan.p; cx.ctop = s->d_cx_top.p;
-        cx.runs = s->d_cx_runs.p; cx.runs_cap = s->d_cx_runs.cap;
-    }
-    const Records r = records_of(s);
-    const uint8_t *mask = s->have_mask ? s->d_mask.p : nullptr;
-    FilterCfg f{};
-    f.include_improper_pairs = s->cfg.include_improper_pairs; f.include_supplementary = s->cfg.include_supplementary;
-    f.include_secondary = s->cfg.include_secondary; f.filter_single = s->cfg.filter_single;
-    f.min_mapq = s->cfg.min_mapq; f.min_aligned_length = s->cfg.min_aligned_length;
-    f.min_percent_identity = s->cfg.min_percent_identity; f.min_aligned_percent = s->cfg.min_aligned_percent;
-    // identity streams actually needed (NULL = skipped by k_prep and the k_id_* kernels)
-    double *idp = (want_id && !(s->cfg.want & COV_WANT_IDENTITY_NONSUPP_ONLY)) ? s->d_identp.p : nullptr;
-    double *idn = (want_id && !(s->cfg.want & COV_WANT_IDENTITY_PRIMARY_ONLY)) ? s->d_ident.p : nullptr;
+    HIPCHK(s->d_part.reserve((size_t)p.prep_grid + 2, st));
+    if (p.id_nonsupp) HIPCHK(s->d_ident.reserve(std::max<size_t>(1, R), st));
+    if (p.id_primary) HIPCHK(s->d_identp.reserve(std::max<size_t>(1, R), st));
+    if (p.want_id) HIPCHK(s->d_idch.reserve((size_t)R / ID_CH + 2, st));
+    if (p.want_hist) HIPCHK(s->d_arena.reserve((size_t)R + nT + 1, st));
+    HIPCHK(s->d_cx_list.reserve((size_t)(p.ncig / CX_MIN_OPS) + 64, st));
     HIPCHK(s->d_prep_args.reserve(1, st));
     HIPCHK(s->d_gen_list.reserve((size_t)R / 64 + 2, st));
-    PrepArgs pa{};
-    {
-        PrepHot &ph = pa.hot;
-        ph.tid = r.tid; ph.pos = r.pos; ph.flag = r.flag; ph.nmk = r.nm_kind; ph.nm = r.nm; ph.coff = r.cigar_off; ph.cigar = r.cigar; ph.mapq = r.mapq; ph.lseq = r.l_seq;
-        ph.runs = s->d_runs.p; ph.tcnt = ti.tcnt; ph.fov = ti.fov; ph.identp = idp; ph.identn = idn;
-        ph.n = r.n; ph.cigar_end = r.cigar_end; ph.n_targets = nT; ph.shift = ti.shift; ph.steps = (u32)prep_chunk / 256u;
-        ph.gate_mask = 0x4u | (f.include_secondary ? 0u : 0x100u) | (f.include_supplementary ? 0u : 0x800u) | (f.include_improper_pairs ? 0u : 0x2u);
-        ph.p1_mask = 0x4u | (f.include_secondary ? 0u : 0x100u) | (f.include_supplementary ? 0u : 0x800u);
-        ph.min_mapq = f.min_mapq; ph.min_aligned_length = f.min_aligned_length; ph.min_percent_identity = f.min_percent_identity; ph.min_aligned_percent = f.min_aligned_percent;
-        PrepCold &pc = pa.cold;
-        pc.ctg = s->d_ctg.p; pc.g = s->d_glob.p; pc.part = s->d_part.p; pc.cx_list = cx.list; pc.mask = mask; pc.tlen = s->d_tlen.p; pc.tile_first = s->d_tile_first.p;
-        pc.cx_list_cap = cx.list_cap; pc.gen_list = s->d_gen_list.p;
-    }
-    hipLaunchKernelGGL(k_init, dim3((std::max(std::max(nT, COUNTER_SLOTS * 8), s->n_tiles) + 255) / 256), dim3(256), 0, st, s->d_ctg.p,
-                       nT, s->d_glob.p, ti, cx, s->d_prep_args.p, pa);
-    HIPCHK(hipGetLastError());
 
-    if (R) {
-        time_begin(s, COV_K_PREP);
-        // k_prep_lean's loop takes the steps of 64 records that lie inside one contig; a sample with fewer than ~128 records per contig has few
-        // of those, and k_prep_generic then walks every step itself (no list, no partial records for k_post_prep to add)
-        const u32 n_steps = (R + 63u) / 64u;
-        const bool gen_all = prep_kernel != 7 && (uint64_t)R < (uint64_t)nT * 128u;
-        s->last_gen_all = gen_all;
-        const u32 gen_grid = gen_all ? std::min<u32>((u32)s->n_cus * 64u, (n_steps + 3u) / 4u) : std::min<u32>((u32)s->n_cus * 8u, (n_steps + 3u) / 4u);      // waves stride over the steps
-#define COV_LAUNCH_PREP(ID, FI, MA)                                                                                                       \
-        do {                                                                                                                              \
-            if (prep_kernel == 7)                                                                                                         \
-                hipLaunchKernelGGL((k_prep7s<ID, FI, MA>), dim3(prep_grid), dim3(256), 0, st, r, s->d_tlen.p, nT, mask, f, s->d_ctg.p,   \
-                                   s->d_glob.p, s->d_runs.p, idp, idn, s->d_part.p, ti, prep_passes, prep_b, cx.list, cx.list_cap);      \
-            else if (gen_all)                                                                                                             \
-                hipLaunchKernelGGL((k_prep_generic<ID, FI, MA>), dim3(gen_grid), dim3(256), 0, st, (const PrepArgs *)s->d_prep_args.p, n_steps); \
-            else {                                                                                                                        \
-                hipLaunchKernelGGL((k_prep_lean<ID, FI, MA>), dim3(prep_grid), dim3(256), 0, st, pa.hot, (const PrepArgs *)s->d_prep_args.p); \
-                hipLaunchKernelGGL((k_prep_generic<ID, FI, MA>), dim3(gen_grid), dim3(256), 0, st, (const PrepArgs *)s->d_prep_args.p, 0u); \
-            }                                                                                                                             \
-        } while (0)
-        {
-            const int key = (want_id ? 4 : 0) | (s->cfg.filter_single ? 2 : 0) | (mask != nullptr ? 1 : 0);
-            switch (key) {
-            case 0: COV_LAUNCH_PREP(false, false, false); break;
-            case 1: COV_LAUNCH_PREP(false, false, true); break;
-            case 2: COV_LAUNCH_PREP(false, true, false); break;
-            case 3: COV_LAUNCH_PREP(false, true, true); break;
-            case 4: COV_LAUNCH_PREP(true, false, false); break;
-            case 5: COV_LAUNCH_PREP(true, false, true); break;
-            case 6: COV_LAUNCH_PREP(true, true, false); break;
-            default: COV_LAUNCH_PREP(true, true, true); break;
-            }
-        }
-#undef COV_LAUNCH_PREP
-        if (nT) {   // what depends on k_prep alone, one launch: the workgroups' partial counters to their contigs (the identity kernels read them),
-                    // and the long-CIGAR bucket counts per tile (waves stride over the RW_BUCKET list; nothing to do for short reads)
-            const u32 n_red = gen_all ? 0u : (nT + 3u) / 4u, cx_grid0 = (u32)s->n_cus * 8u;
-            hipLaunchKernelGGL(k_post_prep, dim3(n_red + cx_grid0), dim3(256), 0, st, r, s->d_tlen.p, s->d_glob.p, cx, ti, s->d_ctg.p, nT, (const PrepPartial *)s->d_part.p,
-                               prep_grid, prep_chunk, n_red);
-        }
-        time_end(s, COV_K_PREP);
-        HIPCHK(hipGetLastError());
-        if (want_id && nT) {   // depends only on k_prep: run beside k_ranges / k_pileup
-            if (!s->side) {
-                (void)ingest_prep_wait(s);
-                if (s->ing_aux && !s->ing_active) s->side = s->ing_aux;      // idle since cov_ingest_end
-                else { HIPCHK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking)); s->side_owned = true; }
-            }
-            HIPCHK(hipEventRecord(s->ev_prep_done, st));
-            HIPCHK(hipStreamWaitEvent(s->side, s->ev_prep_done, 0));
-            (void)hipEventRecord(s->ev[COV_K_IDENTITY][0], s->side);
-            if (s->id_mode) {
-                const u32 nch = (R + ID_CH - 1) / ID_CH;
-                hipLaunchKernelGGL(k_id_approx, dim3(nch), dim3(256), 0, s->side, idp, idn, R, s->d_idch.p);
-                hipLaunchKernelGGL(k_id_predict, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, idp, idn, s->d_idch.p);
-                hipLaunchKernelGGL(k_id_exact, dim3(nch), dim3(256), 0, s->side, idp, idn, R, s->d_idch.p);
-                hipLaunchKernelGGL(k_id_combine, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, idp, idn, r.tid, s->d_idch.p);
-            } else
-                hipLaunchKernelGGL(k_identity, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, idp, idn, r.tid);
-            (void)hipEventRecord(s->ev[COV_K_IDENTITY][1], s->side);
-            s->k_launches[COV_K_IDENTITY]++;
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(s->ev_side_done, s->side));   // joined just before the results are copied back
-            s->ev_fresh = -1;      // the host worked between the groups (a stream created on first use, five launches on it): the next group's
-                                   // time starts at its own event, not at k_prep's end (smoke() used to print k_ranges 7.8 ms for 80 k records)
-        }
+    v.ti.tile_first = s->d_tile_first.p; v.ti.tcnt = s->d_tcnt.p; v.ti.fov = s->d_fov.p; v.ti.shift = s->tile_shift; v.ti.n_tiles = s->n_tiles;
+    v.cx.list = s->d_cx_list.p; v.cx.list_cap = (u32)std::min<uint64_t>(p.ncig / CX_MIN_OPS + 64, 0xffffffffull);
+    v.cx.cnt = s->d_cx_cnt.p; v.cx.cur = s->d_cx_cur.p; v.cx.cscan = s->d_cx_scan.p; v.cx.ctop = s->d_cx_top.p;
+    v.cx.runs = s->d_cx_runs.p; v.cx.runs_cap = s->d_cx_runs.cap;
+    v.r = records_of(s);
+    v.mask = device_mask(s); v.excl = (u64)s->cfg.contig_end_exclusion;
+    v.f = filter_of(s->cfg);
+    v.idp = p.id_primary ? s->d_identp.p : nullptr;
+    v.idn = p.id_nonsupp ? s->d_ident.p : nullptr;
+    v.pa = prep_args_of(s, p, v);
+    v.block = result_block_bytes(nT);
+    hipLaunchKernelGGL(k_init, dim3((std::max(std::max(nT, COUNTER_SLOTS * 8), s->n_tiles) + 255) / 256), dim3(256), 0, st, s->d_ctg.p,
+                       nT, s->d_glob.p, v.ti, v.cx, s->d_prep_args.p, v.pa);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 2 (there are records): filter, CIGAR summary, run words, tile index, per-contig counters.
+static cov_status stage_prep(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    time_begin(s, COV_K_PREP);
+    s->last_gen_all = p.gen_all;
+    launch_prep_key((p.want_id ? 4 : 0) | (s->cfg.filter_single ? 2 : 0) | (v.mask != nullptr ? 1 : 0), s, p, v);
+    if (v.nT) {   // what depends on k_prep alone, one launch: the workgroups' partial counters to their contigs (the identity kernels read them),
+                  // and the long-CIGAR bucket counts per tile (waves stride over the RW_BUCKET list; nothing to do for short reads)
+        const u32 n_red = p.gen_all ? 0u : (v.nT + 3u) / 4u, cx_grid0 = (u32)s->n_cus * 8u;
+        hipLaunchKernelGGL(k_post_prep, dim3(n_red + cx_grid0), dim3(256), 0, v.st, v.r, s->d_tlen.p, s->d_glob.p, v.cx, v.ti, s->d_ctg.p, v.nT, (const PrepPartial *)s->d_part.p,
+                           p.prep_grid, p.prep_chunk, n_red);
     }
-    if (R && s->n_tiles) {
-        time_begin(s, COV_K_RANGES);
-        const u32 n_blocks = (s->n_tiles + 1023u) / 1024u;
-        const u32 cx_grid = (u32)s->n_cus * 8u;     // waves stride over the RW_BUCKET list; nothing to do for short reads
-        ScanPair sp{};
-        sp.cnt[0] = s->d_tcnt.p; sp.scan[0] = s->d_tscan.p; sp.top[0] = s->d_ttop.p; sp.total[0] = nullptr;
-        sp.cnt[1] = s->d_cx_cnt.p; sp.scan[1] = s->d_cx_scan.p; sp.top[1] = s->d_cx_top.p; sp.total[1] = &s->d_glob.p->cx_total;
-        hipLaunchKernelGGL(k_tile_scan1, dim3(2u * n_blocks), dim3(1024), 0, st, sp, s->n_tiles, n_blocks);
-        hipLaunchKernelGGL(k_tile_scan2, dim3(2), dim3(1024), 0, st, sp, n_blocks);
-        hipLaunchKernelGGL((k_cx_expand<true>), dim3(cx_grid), dim3(256), 0, st, r, s->d_tlen.p, s->d_glob.p, cx, ti);
-        u32 *slow_list = s->use_fast ? s->d_slow_list.p : nullptr;
-        if (want_hist)
-            hipLaunchKernelGGL((k_ranges<true>), dim3((s->n_tiles + 255) / 256), dim3(256), 0, st, s->d_tile_contig.p,
-                               s->d_tile_start.p, s->n_tiles, s->d_tlen.p, mask, s->d_ctg.p, s->d_desc.p, ti, s->d_tscan.p,
-                               s->d_ttop.p, cx, s->d_glob.p, slow_list);
-        else
-            hipLaunchKernelGGL((k_ranges<false>), dim3((s->n_tiles + 255) / 256), dim3(256), 0, st, s->d_tile_contig.p,
-                               s->d_tile_start.p, s->n_tiles, s->d_tlen.p, mask, s->d_ctg.p, s->d_desc.p, ti, s->d_tscan.p,
-                               s->d_ttop.p, cx, s->d_glob.p, slow_list);
-        time_end(s, COV_K_RANGES);
-        HIPCHK(hipGetLastError());
-        if (want_hist) {
-            time_begin(s, COV_K_HIST);
-            const u32 hb = (nT + 1023u) / 1024u;
-            HIPCHK(s->d_hist_top.reserve(hb, st));
-            hipLaunchKernelGGL((k_hist_sum<0>), dim3(hb), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, s->d_hist_top.p);
-            hipLaunchKernelGGL((k_hist_off<0>), dim3(hb), dim3(1024), 0, st, s->d_ctg.p, nT, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u64 *)s->d_hist_top.p, s->d_glob.p);
-            hipLaunchKernelGGL(k_zero_u32, dim3(2048), dim3(256), 0, st, s->d_arena.p, &s->d_glob.p->hist_cap_total);
-            time_end(s, COV_K_HIST);
-            HIPCHK(hipGetLastError());
-        }
-        PileupArgs a = pileup_args(s);
-        // With the histogram wanted the pileup leaves the bins and cov_out; the contigs' window statistics are derived from the bins once
-        // per contig (hist_stats_derive): by the estimator kernel as its prologue when it is the first reader — no launch added —, else
-        // by k_hist_stats here, in front of k_hist_sum<1> / the genome and separator kernels / the copy of the result block.
-        compacted = want_hist && (s->est.n == 0 || s->hist_fetch_seen);
-        derive_in_est = want_hist && !compacted && !(s->have_mask || s->have_runs) && s->est.n != 0;
-        time_begin(s, COV_K_PILEUP);
-        if (want_hist) launch_any_pileup<true, false>(s, a, s->n_tiles);
-        else launch_any_pileup<false, false>(s, a, s->n_tiles);
-        if (want_hist && !derive_in_est) {
-            if (est_lanes) hipLaunchKernelGGL((k_hist_stats<true>), dim3((nT + 255) / 256), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u32 *)s->d_arena.p);
-            else hipLaunchKernelGGL((k_hist_stats<false>), dim3((nT + 3) / 4), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u32 *)s->d_arena.p);
-        }
-        time_end(s, COV_K_PILEUP);
-        HIPCHK(hipGetLastError());
-        if (want_hist) {
-            s->hist_prefetched = 0;
-            if (compacted) {
-                HIPCHK(s->d_chist.reserve((size_t)R + nT + 1, st));
-                time_begin(s, COV_K_HIST_COMPACT);
-                const u32 hb = (nT + 1023u) / 1024u;
-                hipLaunchKernelGGL((k_hist_sum<1>), dim3(hb), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, s->d_hist_top.p);
-                hipLaunchKernelGGL((k_hist_off<1>), dim3(hb), dim3(1024), 0, st, s->d_ctg.p, nT, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u64 *)s->d_hist_top.p, s->d_glob.p);
-                hipLaunchKernelGGL(k_hist_compact, dim3((nT + 3u) / 4u), dim3(256), 0, st, s->d_ctg.p, nT, s->d_tlen.p, (u64)s->cfg.contig_end_exclusion, s->d_arena.p, s->d_chist.p);
-                time_end(s, COV_K_HIST_COMPACT);
-                HIPCHK(hipGetLastError());
-                // (only for a caller that fetched the histogram after the finish before this one: a caller that never does pays no copy)
-                const u64 guess = s->hist_fetch_seen ? std::min<u64>({s->last_chist_total + s->last_chist_total / 16, (u64)R + nT + 1, (u64)(64u << 20) / 8}) : 0;
-                if (guess) {
-                    if (guess > s->h_chist_cap) {
-                        if (s->h_chist) (void)hipHostFree(s->h_chist);
-                        s->h_chist = nullptr; s->h_chist_cap = 0;
-                        HIPCHK(hipHostMalloc((void **)&s->h_chist, (size_t)guess * 8, hipHostMallocDefault));
-                        s->h_chist_cap = guess;
-                    }
-                    HIPCHK(hipMemcpyAsync(s->h_chist, s->d_chist.p, (size_t)guess * 8, hipMemcpyDeviceToHost, st));
-                    s->hist_prefetched = guess;
-                }
-            }
-            s->hist_fetch_seen = false;
-        }
+    time_end(s, COV_K_PREP);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 3 (identity wanted, records and targets): the identity sums depend only on k_prep and run beside k_ranges / k_pileup on the side stream.
+static cov_status stage_identity_side(cov_session *s, const PassViews &v) {
+    const u32 R = v.R, nT = v.nT;
+    if (!s->side) {
+        (void)ingest_prep_wait(s);
+        if (s->ing_aux && !s->ing_active) s->side = s->ing_aux;      // idle since cov_ingest_end
+        else { HIPCHK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking)); s->side_owned = true; }
     }
-    // (with a target mask the entries are genomes — aggregated below when cov_set_genomes gave their table, else by the caller: masked-out
-    // contigs have no bins in the arena, and nobody may fetch per-contig floats — no k_estimate launch, no floats in the copy)
-    const size_t block = result_block_bytes(nT), nf = (s->have_mask || s->have_runs) ? 0 : (size_t)nT * s->est.n;
-    {
-        result_host_take(s);
-        const size_t need = lean ? sizeof(DevGlobal) + sizeof(DevContig) : result_host_bytes(s, nT);      // (lean: DevGlobal + the order word)
-        if (need > s->h_res_cap) {
-            if (s->h_res) (void)hipHostFree(s->h_res);
-            s->h_res = nullptr; s->h_res_cap = 0;
-            const size_t cap = need < ((size_t)64 << 20) ? need + need / 2 : need;      // (room to grow for small blocks only)
-            HIPCHK(hipHostMalloc((void **)&s->h_res, cap, hipHostMallocDefault));
-            s->h_res_cap = cap;
-        }
-        s->h_ctg = (DevContig *)(s->h_res + sizeof(DevGlobal));
-        s->h_estf = reinterpret_cast<float *>(s->h_res + block);
-    }
-    if (want_id && R && nT) { HIPCHK(hipStreamWaitEvent(st, s->ev_side_done, 0)); s->ev_fresh = -1; }      // (the wait is not the next group's time)
-    if (nf) {      // CoverageEstimator::calculate_coverage of every contig (k_init left n_pass = 0 everywhere when nothing ran: rows of zeros)
-        time_begin(s, COV_K_ESTIMATE);
-        if (est_lanes)
-            hipLaunchKernelGGL(k_estimate_lanes, dim3((nT + 255) / 256), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
-                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block), derive_in_est ? 1u : 0u);
-        else
-            hipLaunchKernelGGL(k_estimate, dim3((nT + 3) / 4), dim3(256), 0, st, s->d_ctg.p, nT, (const u32 *)s->d_tlen.p, (u64)s->cfg.contig_end_exclusion,
-                               (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + block), derive_in_est ? 1u : 0u);
-        time_end(s, COV_K_ESTIMATE);
-        HIPCHK(hipGetLastError());
-    }
-    // genome entries (cov_set_genomes): reduce the contigs' accumulators over each genome's row, merge their histograms, evaluate.  Not
-    // after a spill: the contigs that left the store are on the host, the caller aggregates there.
-    const bool runs = s->have_runs && s->est.n != 0 && !s->spill.active && !s->in_spill;
-    const bool genomes = runs || (s->have_genomes && s->est.n != 0 && !s->spill.active && !s->in_spill);
-    if (lean && !genomes) { s->err = "cov_finish_genomes: cov_set_genomes or cov_set_genome_runs, and cov_set_estimators, first, and no spill of the bounded record store (cov_finish then)"; return COV_ERR_STATE; }
-    u32 sep_counts[SEP_N_COUNTS] = {0, 0, 0, 0};
-    if (runs) {
-        // separator / single-genome entries: which targets form an entry depends on where the reads fell — the table of this finish
-        // (sep_kernels.hip.h), then its three counts: the launches below are sized by them
-        const u32 nb = (std::max(nT, 1u) + SEP_TILE - 1u) / SEP_TILE, eb = (s->sep_ent_cap + SEP_TILE - 1u) / SEP_TILE, cap = s->sep_ent_cap;
-        time_begin(s, COV_K_SEP);
-        hipLaunchKernelGGL(k_sep_obs_top, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_stop_last1.p, s->d_stop_first.p);
-        hipLaunchKernelGGL(k_sep_flags, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p,
-                           (const u32 *)s->d_stop_last1.p, (const u32 *)s->d_stop_first.p, s->d_scode.p, s->d_stop_cnt.p);
-        hipLaunchKernelGGL(k_sep_compact, dim3(nb), dim3(SEP_TILE), 0, st, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p, (const uint8_t *)s->d_scode.p,
-                           (const u64 *)s->d_stop_cnt.p, s->d_gtids.p, s->d_sent_pos.p, s->d_sent.p, cap, s->d_scounts.p, s->d_glob.p);
-        hipLaunchKernelGGL(k_sep_rows, dim3((std::max(nT, 1u) + 255u) / 256u), dim3(256), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_sent_pos.p, s->d_grow.p, cap);
-        hipLaunchKernelGGL(k_sep_seg_sum, dim3(eb), dim3(SEP_TILE), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_grow.p, s->d_stop_seg.p);
-        hipLaunchKernelGGL(k_sep_seg_write, dim3(eb), dim3(SEP_TILE), 0, st, s->d_scounts.p, (const u32 *)s->d_grow.p, (const u64 *)s->d_stop_seg.p, s->d_gseg_genome.p,
-                           s->d_gseg_start.p, s->sep_seg_cap);
-        time_end(s, COV_K_SEP);
-        HIPCHK(hipGetLastError());
-        uint8_t *hc = s->h_gout + s->h_gout_cap - 16;
-        HIPCHK(hipMemcpyAsync(hc, s->d_scounts.p, SEP_N_COUNTS * sizeof(u32), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        memcpy(sep_counts, hc, sizeof sep_counts);
-        s->ev_fresh = -1;      // (the wait is not the next group's time)
-        s->n_genomes = sep_counts[SEP_N_ENTRIES]; s->n_gseg = sep_counts[SEP_N_SEG];
-    }
-    if (genomes && s->n_genomes != 0) {
-        const u32 nG = s->n_genomes, n_seg = s->n_gseg, sep = runs ? 1u : 0u;
-        GenomeTable gt{s->d_grow.p, s->d_gtids.p, s->d_gseg_genome.p, s->d_gseg_start.p, nG, n_seg};
-        const u64 excl = s->cfg.contig_end_exclusion;
-        const u64 ghist_cap = (u64)R + nT + 1;      // the genomes' bins are at most the contigs' (every genome bin is some contig's bin)
-        if (want_hist) HIPCHK(s->d_ghist.reserve((size_t)ghist_cap, st));
-        time_begin(s, COV_K_GENOME);
-        hipLaunchKernelGGL(k_genome_init, dim3((nG + 255u) / 256u), dim3(256), 0, st, s->d_genomes.p, nG);
-        if (n_seg) hipLaunchKernelGGL(k_genome_reduce, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl, gt, s->d_genomes.p, sep);
-        if (want_id && !(s->cfg.want & (runs ? COV_WANT_IDENTITY_NONSUPP_ONLY : COV_WANT_IDENTITY_PRIMARY_ONLY)))
-            hipLaunchKernelGGL(k_genome_identity, dim3(nG), dim3(64), 0, st, (const DevContig *)s->d_ctg.p, gt, s->d_genomes.p, sep);
-        if (want_hist) {
-            const u32 gb = (nG + 1023u) / 1024u;
-            u64 *total = s->d_ghist_top.p + gb;
-            hipLaunchKernelGGL(k_genome_hist_sum, dim3(gb), dim3(1024), 0, st, (const DevGenome *)s->d_genomes.p, nG, s->d_ghist_top.p);
-            hipLaunchKernelGGL(k_genome_hist_off, dim3(gb), dim3(1024), 0, st, s->d_genomes.p, nG, (const u64 *)s->d_ghist_top.p, total, ghist_cap, s->d_glob.p);
-            hipLaunchKernelGGL(k_zero_u64, dim3(1024), dim3(256), 0, st, s->d_ghist.p, (const u64 *)total, ghist_cap);
-            if (n_seg && R && s->n_tiles)
-                hipLaunchKernelGGL(k_genome_hist_merge, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl,
-                                   (const u32 *)s->d_arena.p, gt, (const DevGenome *)s->d_genomes.p, s->d_ghist.p, ghist_cap);
-        }
-        DevGenomeStats *gstats = reinterpret_cast<DevGenomeStats *>(s->d_gout.p);
-        float *gest = reinterpret_cast<float *>(s->d_gout.p + (size_t)nG * sizeof(DevGenomeStats));
-        if (nG >= 65536u)
-            hipLaunchKernelGGL(k_genome_estimate_lanes, dim3((nG + 255u) / 256u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
-        else
-            hipLaunchKernelGGL(k_genome_estimate, dim3((nG + 3u) / 4u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
-        time_end(s, COV_K_GENOME);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_gout, s->d_gout.p, (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float)), hipMemcpyDeviceToHost, st));
-        if (runs) HIPCHK(hipMemcpyAsync(s->h_gout + (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float)), s->d_sent.p, (size_t)nG * sizeof(SepEntry), hipMemcpyDeviceToHost, st));
-    }      // (runs and no target with a considered record: no entry, nothing to reduce)
-    if (lean) {
-        // the order rule of convert_results on the device: the first considered record of a seen contig must not lie before the last one of
-        // any seen contig in front of it (contig.rs:129-132); the verdict is one word behind DevGlobal
-        const u32 ob = (nT + 1023u) / 1024u;
-        HIPCHK(s->d_order.reserve((size_t)ob + 2, st));
-        hipLaunchKernelGGL(k_order_max, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
-        hipLaunchKernelGGL(k_order_check, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipMemcpyAsync(s->h_res + sizeof(DevGlobal), s->d_order.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipEventRecord(s->ev_prep_done, v.st));
+    HIPCHK(hipStreamWaitEvent(s->side, s->ev_prep_done, 0));
+    (void)hipEventRecord(s->ev[COV_K_IDENTITY][0], s->side);
+    if (s->id_mode) {
+        const u32 nch = (R + ID_CH - 1) / ID_CH;
+        hipLaunchKernelGGL(k_id_approx, dim3(nch), dim3(256), 0, s->side, v.idp, v.idn, R, s->d_idch.p);
+        hipLaunchKernelGGL(k_id_predict, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, v.idp, v.idn, s->d_idch.p);
+        hipLaunchKernelGGL(k_id_exact, dim3(nch), dim3(256), 0, s->side, v.idp, v.idn, R, s->d_idch.p);
+        hipLaunchKernelGGL(k_id_combine, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, v.idp, v.idn, v.r.tid, s->d_idch.p);
     } else
-    // one copy: the result block and, behind it, the estimators' floats
-    HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal) + (size_t)nT * sizeof(DevContig) + (nf ? (block - sizeof(DevGlobal) - (size_t)nT * sizeof(DevContig)) + nf * sizeof(float) : 0),
-                          hipMemcpyDeviceToHost, st));
-    // (c) a finish is a millisecond: the host looks for its end itself for a while before it asks to be woken
-    {
-        const auto t_spin = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t q = hipStreamQuery(st);
-            if (q == hipSuccess) break;
-            if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }
-            (void)hipGetLastError();
-            if (std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(4)) break;
-            __builtin_ia32_pause();
+        hipLaunchKernelGGL(k_identity, dim3(nT), dim3(64), 0, s->side, s->d_ctg.p, nT, v.idp, v.idn, v.r.tid);
+    (void)hipEventRecord(s->ev[COV_K_IDENTITY][1], s->side);
+    s->k_launches[COV_K_IDENTITY]++;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(s->ev_side_done, s->side));   // joined just before the results are copied back (stage_join_side)
+    s->ev_fresh = -1;      // the host worked between the groups (a stream created on first use, five launches on it): the next group's
+                           // time starts at its own event, not at k_prep's end (smoke() used to print k_ranges 7.8 ms for 80 k records)
+    return COV_OK;
+}
+
+// Stage 4 (records and tiles): prefix sums of the tile index and of the bucket counts, the buckets' fill, the tiles' candidate ranges.
+static cov_status stage_ranges(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    time_begin(s, COV_K_RANGES);
+    const u32 n_blocks = (s->n_tiles + 1023u) / 1024u;
+    const u32 cx_grid = (u32)s->n_cus * 8u;     // waves stride over the RW_BUCKET list; nothing to do for short reads
+    ScanPair sp{};
+    sp.cnt[0] = s->d_tcnt.p; sp.scan[0] = s->d_tscan.p; sp.top[0] = s->d_ttop.p; sp.total[0] = nullptr;
+    sp.cnt[1] = s->d_cx_cnt.p; sp.scan[1] = s->d_cx_scan.p; sp.top[1] = s->d_cx_top.p; sp.total[1] = &s->d_glob.p->cx_total;
+    hipLaunchKernelGGL(k_tile_scan1, dim3(2u * n_blocks), dim3(1024), 0, v.st, sp, s->n_tiles, n_blocks);
+    hipLaunchKernelGGL(k_tile_scan2, dim3(2), dim3(1024), 0, v.st, sp, n_blocks);
+    hipLaunchKernelGGL((k_cx_expand<true>), dim3(cx_grid), dim3(256), 0, v.st, v.r, s->d_tlen.p, s->d_glob.p, v.cx, v.ti);
+    u32 *slow_list = s->use_fast ? s->d_slow_list.p : nullptr;
+    const auto ranges = p.want_hist ? &k_ranges<true> : &k_ranges<false>;
+    hipLaunchKernelGGL(ranges, dim3((s->n_tiles + 255) / 256), dim3(256), 0, v.st, s->d_tile_contig.p, s->d_tile_start.p, s->n_tiles, s->d_tlen.p,
+                       v.mask, s->d_ctg.p, s->d_desc.p, v.ti, s->d_tscan.p, s->d_ttop.p, v.cx, s->d_glob.p, slow_list);
+    time_end(s, COV_K_RANGES);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 5 (histogram wanted): the arena's layout from the bounds k_ranges left, and its zero fill.
+static cov_status stage_hist_layout(cov_session *s, const PassViews &v) {
+    time_begin(s, COV_K_HIST);
+    const u32 hb = (v.nT + 1023u) / 1024u;
+    HIPCHK(s->d_hist_top.reserve(hb, v.st));
+    hipLaunchKernelGGL((k_hist_sum<0>), dim3(hb), dim3(1024), 0, v.st, (const DevContig *)s->d_ctg.p, v.nT, s->d_tlen.p, v.mask, v.excl, s->d_hist_top.p);
+    hipLaunchKernelGGL((k_hist_off<0>), dim3(hb), dim3(1024), 0, v.st, s->d_ctg.p, v.nT, s->d_tlen.p, v.mask, v.excl, (const u64 *)s->d_hist_top.p, s->d_glob.p);
+    hipLaunchKernelGGL(k_zero_u32, dim3(2048), dim3(256), 0, v.st, s->d_arena.p, &s->d_glob.p->hist_cap_total);
+    time_end(s, COV_K_HIST);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 6: the pileup, and k_hist_stats inside its bracket when the estimator kernel is not the first reader of the window statistics.
+static cov_status stage_pileup(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    const PileupArgs a = pileup_args(s);
+    time_begin(s, COV_K_PILEUP);
+    if (p.want_hist) launch_any_pileup<true, false>(s, a, s->n_tiles);
+    else launch_any_pileup<false, false>(s, a, s->n_tiles);
+    if (p.hist_stats_launch) {
+        const auto hist_stats = p.est_lanes ? &k_hist_stats<true> : &k_hist_stats<false>;
+        hipLaunchKernelGGL(hist_stats, dim3(p.est_lanes ? (v.nT + 255) / 256 : (v.nT + 3) / 4), dim3(256), 0, v.st, s->d_ctg.p, v.nT, (const u32 *)s->d_tlen.p,
+                           v.mask, v.excl, (const u32 *)s->d_arena.p);
+    }
+    time_end(s, COV_K_PILEUP);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 7 (histogram wanted): the compact histogram, when this pass builds it, and the start of its way to the host.
+static cov_status stage_hist_compact(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    s->hist_prefetched = 0;
+    if (p.compacted) {
+        HIPCHK(s->d_chist.reserve((size_t)v.R + v.nT + 1, v.st));
+        time_begin(s, COV_K_HIST_COMPACT);
+        launch_hist_compact(s, v.mask, v.excl);
+        time_end(s, COV_K_HIST_COMPACT);
+        HIPCHK(hipGetLastError());
+        // (only for a caller that fetched the histogram after the finish before this one: a caller that never does pays no copy)
+        const u64 guess = p.hist_prefetch ? std::min<u64>({s->last_chist_total + s->last_chist_total / 16, (u64)v.R + v.nT + 1, (u64)(64u << 20) / 8}) : 0;
+        if (guess) {
+            if (guess > s->h_chist_cap) HIPCHK(pinned_grow(s->h_chist, s->h_chist_cap, guess));
+            HIPCHK(hipMemcpyAsync(s->h_chist, s->d_chist.p, (size_t)guess * 8, hipMemcpyDeviceToHost, v.st));
+            s->hist_prefetched = guess;
         }
     }
+    s->hist_fetch_seen = false;
+    return COV_OK;
+}
+
+// The page-locked staging of the results: what cov_set_targets' helper thread obtained, or grown here.
+static cov_status result_host_bind(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    result_host_take(s);
+    const size_t need = p.lean ? sizeof(DevGlobal) + sizeof(DevContig) : result_host_bytes(s, v.nT);      // (lean: DevGlobal + the order word)
+    if (need > s->h_res_cap) HIPCHK(pinned_grow(s->h_res, s->h_res_cap, need < ((size_t)64 << 20) ? need + need / 2 : need));      // (room to grow for small blocks only)
+    s->h_ctg = (DevContig *)(s->h_res + sizeof(DevGlobal));
+    s->h_estf = reinterpret_cast<float *>(s->h_res + v.block);
+    return COV_OK;
+}
+
+// The side stream's identity sums are in the contigs' accumulators from here on.
+static cov_status stage_join_side(cov_session *s, const PassViews &v) {
+    HIPCHK(hipStreamWaitEvent(v.st, s->ev_side_done, 0));
+    s->ev_fresh = -1;      // the stream waited here: the wait is not the next group's time
+    return COV_OK;
+}
+
+// Stage 8 (per-contig floats wanted): CoverageEstimator::calculate_coverage of every contig (k_init left n_pass = 0 everywhere when nothing
+// ran: rows of zeros).
+static cov_status stage_estimate(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    time_begin(s, COV_K_ESTIMATE);
+    const auto estimate = p.est_lanes ? &k_estimate_lanes : &k_estimate;
+    hipLaunchKernelGGL(estimate, dim3(p.est_lanes ? (v.nT + 255) / 256 : (v.nT + 3) / 4), dim3(256), 0, v.st, s->d_ctg.p, v.nT, (const u32 *)s->d_tlen.p, v.excl,
+                       (const u32 *)s->d_arena.p, s->est, reinterpret_cast<float *>(s->d_res.p + v.block), p.derive_in_est ? 1u : 0u);
+    time_end(s, COV_K_ESTIMATE);
+    HIPCHK(hipGetLastError());
+    return COV_OK;
+}
+
+// Stage 9 (cov_set_genome_runs): separator / single-genome entries — which targets form an entry depends on where the reads fell: the
+// table of this finish (sep_kernels.hip.h), then its counts on the host: the genome kernels' launches are sized by them.
+static cov_status stage_sep_table(cov_session *s, const PassViews &v) {
+    hipStream_t st = v.st; const u32 nT = v.nT;
+    const u32 nb = (std::max(nT, 1u) + SEP_TILE - 1u) / SEP_TILE, eb = (s->sep_ent_cap + SEP_TILE - 1u) / SEP_TILE, cap = s->sep_ent_cap;
+    time_begin(s, COV_K_SEP);
+    hipLaunchKernelGGL(k_sep_obs_top, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_stop_last1.p, s->d_stop_first.p);
+    hipLaunchKernelGGL(k_sep_flags, dim3(nb), dim3(SEP_TILE), 0, st, (const DevContig *)s->d_ctg.p, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p,
+                       (const u32 *)s->d_stop_last1.p, (const u32 *)s->d_stop_first.p, s->d_scode.p, s->d_stop_cnt.p);
+    hipLaunchKernelGGL(k_sep_compact, dim3(nb), dim3(SEP_TILE), 0, st, nT, (const int32_t *)s->d_sgid.p, (const u32 *)s->d_sblk.p, (const uint8_t *)s->d_scode.p,
+                       (const u64 *)s->d_stop_cnt.p, s->d_gtids.p, s->d_sent_pos.p, s->d_sent.p, cap, s->d_scounts.p, s->d_glob.p);
+    hipLaunchKernelGGL(k_sep_rows, dim3((std::max(nT, 1u) + 255u) / 256u), dim3(256), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_sent_pos.p, s->d_grow.p, cap);
+    hipLaunchKernelGGL(k_sep_seg_sum, dim3(eb), dim3(SEP_TILE), 0, st, (const u32 *)s->d_scounts.p, (const u32 *)s->d_grow.p, s->d_stop_seg.p);
+    hipLaunchKernelGGL(k_sep_seg_write, dim3(eb), dim3(SEP_TILE), 0, st, s->d_scounts.p, (const u32 *)s->d_grow.p, (const u64 *)s->d_stop_seg.p, s->d_gseg_genome.p,
+                       s->d_gseg_start.p, s->sep_seg_cap);
+    time_end(s, COV_K_SEP);
+    HIPCHK(hipGetLastError());
+    u32 sep_counts[SEP_N_COUNTS] = {0, 0, 0, 0};
+    uint8_t *hc = s->h_gout + s->h_gout_cap - 16;
+    HIPCHK(hipMemcpyAsync(hc, s->d_scounts.p, SEP_N_COUNTS * sizeof(u32), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    memcpy(&s->h_glob, s->h_res, sizeof(DevGlobal));
-    if (s->h_glob.cx_total > s->d_cx_runs.cap) {
-        const uint64_t need = s->h_glob.cx_total + s->h_glob.cx_total / 8 + 1024;
-        s->d_cx_runs.release();
-        HIPCHK(s->d_cx_runs.reserve((size_t)need, st));
-        again = true;
+    memcpy(sep_counts, hc, sizeof sep_counts);
+    s->ev_fresh = -1;      // the host waited here: the wait is not the next group's time
+    s->n_genomes = sep_counts[SEP_N_ENTRIES]; s->n_gseg = sep_counts[SEP_N_SEG];
+    return COV_OK;
+}
+
+// Stage 10 (genome entries, and at least one): reduce the contigs' accumulators over each genome's row, merge their histograms, evaluate,
+// and start the entries' way to the host.  (runs and no target with a considered record: no entry, nothing to reduce.)
+static cov_status stage_genomes(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    hipStream_t st = v.st;
+    const u32 nG = s->n_genomes, n_seg = s->n_gseg, sep = p.runs ? 1u : 0u;
+    GenomeTable gt{s->d_grow.p, s->d_gtids.p, s->d_gseg_genome.p, s->d_gseg_start.p, nG, n_seg};
+    const u64 excl = v.excl;
+    const u64 ghist_cap = (u64)v.R + v.nT + 1;      // the genomes' bins are at most the contigs' (every genome bin is some contig's bin)
+    if (p.want_hist) HIPCHK(s->d_ghist.reserve((size_t)ghist_cap, st));
+    time_begin(s, COV_K_GENOME);
+    hipLaunchKernelGGL(k_genome_init, dim3((nG + 255u) / 256u), dim3(256), 0, st, s->d_genomes.p, nG);
+    if (n_seg) hipLaunchKernelGGL(k_genome_reduce, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl, gt, s->d_genomes.p, sep);
+    if (p.genome_identity) hipLaunchKernelGGL(k_genome_identity, dim3(nG), dim3(64), 0, st, (const DevContig *)s->d_ctg.p, gt, s->d_genomes.p, sep);
+    if (p.want_hist) {
+        const u32 gb = (nG + 1023u) / 1024u;
+        u64 *total = s->d_ghist_top.p + gb;
+        hipLaunchKernelGGL(k_genome_hist_sum, dim3(gb), dim3(1024), 0, st, (const DevGenome *)s->d_genomes.p, nG, s->d_ghist_top.p);
+        hipLaunchKernelGGL(k_genome_hist_off, dim3(gb), dim3(1024), 0, st, s->d_genomes.p, nG, (const u64 *)s->d_ghist_top.p, total, ghist_cap, s->d_glob.p);
+        hipLaunchKernelGGL(k_zero_u64, dim3(1024), dim3(256), 0, st, s->d_ghist.p, (const u64 *)total, ghist_cap);
+        if (n_seg && p.run_pileup)
+            hipLaunchKernelGGL(k_genome_hist_merge, dim3((n_seg + 3u) / 4u), dim3(256), 0, st, (const DevContig *)s->d_ctg.p, (const u32 *)s->d_tlen.p, excl,
+                               (const u32 *)s->d_arena.p, gt, (const DevGenome *)s->d_genomes.p, s->d_ghist.p, ghist_cap);
+    }
+    DevGenomeStats *gstats = reinterpret_cast<DevGenomeStats *>(s->d_gout.p);
+    float *gest = reinterpret_cast<float *>(s->d_gout.p + (size_t)nG * sizeof(DevGenomeStats));
+    const bool lanes = nG >= 65536u;      // a lane per genome, as for the contigs of an assembly
+    const auto estimate = lanes ? &k_genome_estimate_lanes : &k_genome_estimate;
+    hipLaunchKernelGGL(estimate, dim3(lanes ? (nG + 255u) / 256u : (nG + 3u) / 4u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
+    time_end(s, COV_K_GENOME);
+    HIPCHK(hipGetLastError());
+    const size_t rows = (size_t)nG * (sizeof(DevGenomeStats) + s->est.n * sizeof(float));
+    HIPCHK(hipMemcpyAsync(s->h_gout, s->d_gout.p, rows, hipMemcpyDeviceToHost, st));
+    if (p.runs) HIPCHK(hipMemcpyAsync(s->h_gout + rows, s->d_sent.p, (size_t)nG * sizeof(SepEntry), hipMemcpyDeviceToHost, st));
+    return COV_OK;
+}
+
+// Stage 11: the results' way to the host.  Lean (cov_finish_genomes): DevGlobal and the order rule of convert_results evaluated on the
+// device — the first considered record of a seen contig must not lie before the last one of any seen contig in front of it
+// (contig.rs:129-132); the verdict is one word behind DevGlobal.  Else one copy: the result block and, behind it, the estimators' floats.
+static cov_status stage_result_copy(cov_session *s, const FinishPlan &p, const PassViews &v) {
+    hipStream_t st = v.st; const u32 nT = v.nT;
+    if (!p.lean) {
+        HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal) + (size_t)nT * sizeof(DevContig) + (p.nf ? (v.block - sizeof(DevGlobal) - (size_t)nT * sizeof(DevContig)) + p.nf * sizeof(float) : 0),
+                              hipMemcpyDeviceToHost, st));
         return COV_OK;
     }
+    const u32 ob = (nT + 1023u) / 1024u;
+    HIPCHK(s->d_order.reserve((size_t)ob + 2, st));
+    hipLaunchKernelGGL(k_order_max, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
+    hipLaunchKernelGGL(k_order_check, dim3(std::max(ob, 1u)), dim3(1024), 0, st, (const DevContig *)s->d_ctg.p, nT, s->d_order.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(s->h_res, s->d_res.p, sizeof(DevGlobal), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s->h_res + sizeof(DevGlobal), s->d_order.p, 8, hipMemcpyDeviceToHost, st));
+    return COV_OK;
+}
+
+// Stage 12a: the end of the pass.  A finish is a millisecond: the host looks for its end itself for a while before it asks to be woken.
+static cov_status stage_wait(cov_session *s, const PassViews &v) {
+    const auto t_spin = std::chrono::steady_clock::now();
+    for (;;) {
+        const hipError_t q = hipStreamQuery(v.st);
+        if (q == hipSuccess) break;
+        if (q != hipErrorNotReady) { (void)hipGetLastError(); break; }
+        (void)hipGetLastError();
+        if (std::chrono::steady_clock::now() - t_spin > std::chrono::milliseconds(4)) break;
+        __builtin_ia32_pause();
+    }
+    HIPCHK(hipStreamSynchronize(v.st));
+    memcpy(&s->h_glob, s->h_res, sizeof(DevGlobal));
+    return COV_OK;
+}
+
+// Stage 12b: the groups' times, the algorithmic bytes, and the verdict on what came back.
+static cov_status stage_verdict(cov_session *s, const FinishPlan &p, const PassViews &v, cov_contig_stats *stats, cov_summary *summary) {
     for (int k = 0; k < COV_K_COUNT; k++)
         if (s->k_launches[k]) (void)hipEventElapsedTime(&s->k_ms[k], k == COV_K_IDENTITY ? s->ev[k][0] : s->ev_begin[k], s->ev[k][1]);
-
     // algorithmic bytes: each record's SoA fields and CIGAR words are needed once; results written once
-    {
-        const uint64_t ncig = s->adopted ? s->adopted_ncig : s->store.n_cigar;
-        s->algo_bytes = (uint64_t)R * 24 + ncig * 4 + (uint64_t)nT * sizeof(DevContig);
-    }
-
-    if (lean) {
+    s->algo_bytes = (uint64_t)v.R * 24 + p.ncig * 4 + (uint64_t)v.nT * sizeof(DevContig);
+    if (p.lean) {
         u64 unsorted_at; memcpy(&unsorted_at, s->h_res + sizeof(DevGlobal), 8);
-        const cov_status cst = verdict_results(s, s->h_glob, unsorted_at, R, summary);
+        const cov_status cst = verdict_results(s, s->h_glob, unsorted_at, v.R, summary);
         if (cst != COV_OK) return cst;
         s->last_chist_total = 0; s->hist_compacted = false; s->est_valid = false; s->gen_valid = true; s->finished = true;
         return COV_OK;
     }
-    const cov_status cst = convert_results(s, s->h_glob, s->h_ctg, R, stats, summary, s->spill.inflight, s->spill.records);
+    const cov_status cst = convert_results(s, s->h_glob, s->h_ctg, v.R, stats, summary, s->spill.inflight, s->spill.records);
     if (cst != COV_OK) return cst;
     s->last_chist_total = 0;
-    if (want_hist) for (u32 c = 0; c < nT; c++) s->last_chist_total += stats[c].hist_len;      // (the host laid the compact histogram out: convert_results)
-    s->hist_compacted = compacted;
+    if (p.want_hist) for (u32 c = 0; c < v.nT; c++) s->last_chist_total += stats[c].hist_len;      // (the host laid the compact histogram out: convert_results)
+    s->hist_compacted = p.compacted;
     s->est_valid = s->est.n != 0 && !s->have_mask && !s->have_runs;
-    s->gen_valid = genomes;
+    s->gen_valid = p.genomes;
     s->finished = true;
     return COV_OK;
+}
+
+// The stages in stream order; every condition is a field of the plan.
+static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summary *summary, bool &again) {
+    again = false;
+    if (!s || (!stats && s->n_targets && !s->lean_finish)) return COV_ERR_INVALID_ARG;
+    const FinishPlan p = finplan::plan(finish_facts(s));
+    PassViews v;
+    cov_status rc = stage_begin(s, p, v);
+    if (rc == COV_OK && p.run_prep) rc = stage_prep(s, p, v);
+    if (rc == COV_OK && p.identity_side) rc = stage_identity_side(s, v);
+    if (rc == COV_OK && p.run_pileup) rc = stage_ranges(s, p, v);
+    if (rc == COV_OK && p.run_pileup && p.want_hist) rc = stage_hist_layout(s, v);
+    if (rc == COV_OK && p.run_pileup) rc = stage_pileup(s, p, v);
+    if (rc == COV_OK && p.run_pileup && p.want_hist) rc = stage_hist_compact(s, p, v);
+    if (rc == COV_OK) rc = result_host_bind(s, p, v);
+    if (rc == COV_OK && p.identity_side) rc = stage_join_side(s, v);
+    if (rc == COV_OK && p.nf) rc = stage_estimate(s, p, v);
+    if (rc == COV_OK && p.lean_without_genomes) {      // (refused here, where the pass always refused: what it leaves the next pass stays as it was)
+        s->err = "cov_finish_genomes: cov_set_genomes or cov_set_genome_runs, and cov_set_estimators, first, and no spill of the bounded record store (cov_finish then)";
+        rc = COV_ERR_STATE;
+    }
+    if (rc == COV_OK && p.runs) rc = stage_sep_table(s, v);
+    if (rc == COV_OK && p.genomes && s->n_genomes != 0) rc = stage_genomes(s, p, v);
+    if (rc == COV_OK) rc = stage_result_copy(s, p, v);
+    if (rc == COV_OK) rc = stage_wait(s, v);
+    if (rc != COV_OK) return rc;
+    if (s->h_glob.cx_total > s->d_cx_runs.cap) {      // the long-CIGAR buckets were too small: the pass computed the exact need, and runs once more
+        const uint64_t need = s->h_glob.cx_total + s->h_glob.cx_total / 8 + 1024;
+        s->d_cx_runs.release();
+        HIPCHK(s->d_cx_runs.reserve((size_t)need, v.st));
+        again = true;
+        return COV_OK;
+    }
+    return stage_verdict(s, p, v, stats, summary);
 }
 
 
@@ -1589,12 +1627,7 @@ cov_status cov_gather(cov_session *const *sessions, uint32_t n, uint32_t root) {
     const size_t block = result_block_bytes(nT);
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(s->d_gather.reserve((size_t)n * block, s->stream));
-    if ((size_t)n * block > s->h_gather_cap) {
-        if (s->h_gather) (void)hipHostFree(s->h_gather);
-        s->h_gather = nullptr; s->h_gather_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&s->h_gather, (size_t)n * block, hipHostMallocDefault));
-        s->h_gather_cap = (size_t)n * block;
-    }
+    if ((size_t)n * block > s->h_gather_cap) HIPCHK(pinned_grow(s->h_gather, s->h_gather_cap, (size_t)n * block));
     for (u32 i = 0; i < n; i++) {   // the record count of each rank travels in its block (a padding word of DevGlobal)
         HIPCHK(hipSetDevice(devs[i]));
         const u64 nr = sessions[i]->merged_valid ? sessions[i]->merged_records : sessions[i]->store.n_records;
@@ -2625,13 +2658,8 @@ static cov_status fetch_chunk_hist(cov_session *s, uint64_t *hist) {
     if (!hist) return COV_ERR_INVALID_ARG;
     if (!s->hist_compacted) {      // the finish left the bins in the arena (its estimators were evaluated on the device): lay them out and compact them now
         HIPCHK(s->d_chist.reserve(total, s->stream));
-        const uint8_t *mask = s->have_mask ? (const uint8_t *)s->d_mask.p : (const uint8_t *)nullptr;
-        const u32 hb = (s->n_targets + 1023u) / 1024u;
-        HIPCHK(s->d_hist_top.reserve(hb, s->stream));
-        hipLaunchKernelGGL((k_hist_sum<1>), dim3(hb), dim3(1024), 0, s->stream, (const DevContig *)s->d_ctg.p, s->n_targets, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, s->d_hist_top.p);
-        hipLaunchKernelGGL((k_hist_off<1>), dim3(hb), dim3(1024), 0, s->stream, s->d_ctg.p, s->n_targets, s->d_tlen.p, mask, (u64)s->cfg.contig_end_exclusion, (const u64 *)s->d_hist_top.p, s->d_glob.p);
-        hipLaunchKernelGGL(k_hist_compact, dim3((s->n_targets + 3u) / 4u), dim3(256), 0, s->stream, s->d_ctg.p, s->n_targets, s->d_tlen.p,
-                           (u64)s->cfg.contig_end_exclusion, s->d_arena.p, s->d_chist.p);
+        HIPCHK(s->d_hist_top.reserve((s->n_targets + 1023u) / 1024u, s->stream));
+        launch_hist_compact(s, device_mask(s), (u64)s->cfg.contig_end_exclusion);
         HIPCHK(hipGetLastError());
         s->hist_prefetched = 0; s->hist_compacted = true;
     }

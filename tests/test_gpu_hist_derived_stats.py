@@ -267,26 +267,55 @@ def test_no_histogram(name, excl):
 # ------------------------------------------------------------------ case 8
 def test_second_finish_compacts_the_histogram():
     """finish, fetch the histogram, finish again: the second finish compacts the histogram itself, so max_d is needed in front of
-    k_hist_off<1> — k_hist_stats derives it, not the estimator kernel.  The same statistics, bins and floats from both."""
+    k_hist_off<1> — k_hist_stats derives it, not the estimator kernel.  The same statistics, bins and floats from both.
+    Then what travels from one pass of the session to the next (the fetch seen, the compaction done, the prefetched bins and their count):
+    a third finish behind the second one's fetch compacts and prefetches again and nobody fetches; the fourth, with no fetch since the
+    third, goes back to deriving in the estimator's prologue, and the fetch behind it compacts late — nothing of the third's unread
+    prefetch may be served; a reset and a finish over no records: rows of zeros, no bins, nothing left over."""
     excl = 75
     b, (exp, exp_hist, prim) = sample("borders", excl)
     est_e, est_o = estimators(excl)
+    compactions = []          # launches of the compaction group inside each finish
     with Session(0, FilterConfig(*FF), excl, want_hist=True, want_identity=True) as s:
         s.set_targets(b.ref_lens)
         s.set_estimators(est_e)
         s.push(to_batch(b))
         st1, _ = s.finish()
+        compactions.append(s.kernel_ms()["k_hist_compact"][1])
         st1 = st1.copy(); ef1 = s.estimates(); h1 = s.hist()
         st2, _ = s.finish()
-        ef2 = s.estimates(); h2 = s.hist()
-    for st, h in ((st1, h1), (st2, h2)):
+        compactions.append(s.kernel_ms()["k_hist_compact"][1])
+        st2 = st2.copy(); ef2 = s.estimates(); h2 = s.hist()
+        st3, _ = s.finish()
+        compactions.append(s.kernel_ms()["k_hist_compact"][1])
+        st3 = st3.copy(); ef3 = s.estimates()
+        st4, _ = s.finish()
+        compactions.append(s.kernel_ms()["k_hist_compact"][1])
+        st4 = st4.copy(); ef4 = s.estimates(); h4 = s.hist()
+        s.reset()
+        st0, summ0 = s.finish()
+        compactions.append(s.kernel_ms()["k_hist_compact"][1])
+        st0 = st0.copy(); ef0 = s.estimates(); h0 = s.hist()
+    assert compactions == [0, 1, 1, 0, 0]
+    for st, h in ((st1, h1), (st2, h2), (st3, None), (st4, h4)):
         check_stats(st, exp)
-        check_hist(st, h, exp, exp_hist)
-    np.testing.assert_array_equal(st1, st2)
-    np.testing.assert_array_equal(h1, h2)
+        np.testing.assert_array_equal(st1, st)
+        if h is not None:
+            check_hist(st, h, exp, exp_hist)
+            np.testing.assert_array_equal(h1, h)
     want = oracle_contig_floats(b, est_o).view(np.uint32)
-    np.testing.assert_array_equal(ef1.view(np.uint32), want)
-    np.testing.assert_array_equal(ef2.view(np.uint32), want)
+    for ef in (ef1, ef2, ef3, ef4):
+        np.testing.assert_array_equal(ef.view(np.uint32), want)
+    # no records: the oracle over an empty sample of the same references
+    e = to_bamdata(batch_of([]), np.asarray(b.ref_lens, np.int64))
+    exp0, exp_hist0, prim0 = O.integer_stats(e, O.FlagFilter(*FF), None, excl)
+    assert summ0.num_detected_primary_alignments == prim0 == 0 and summ0.n_records == 0 and summ0.hist_total == 0
+    assert len(h0) == len(exp_hist0) == 0
+    check_stats(st0, exp0)
+    for f in STAT_FIELDS:
+        np.testing.assert_array_equal(st0[f], exp0[f], err_msg=f)
+    np.testing.assert_array_equal(ef0.view(np.uint32), oracle_contig_floats(e, est_o).view(np.uint32))
+    assert not ef0.view(np.uint32).any()
 
 
 def test_target_mask():
