@@ -233,6 +233,23 @@ def gpu_ingest(session, path: str, threads: int = None, check_crc: bool = True, 
         L.covh_bam_header_free(hd)
 
 
+class _IngestStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("windows", "segments", "segments_with_start", "records", "max_hop_records", "long_records", "repaired_starts")]
+
+
+def ingest_stats(session) -> dict:
+    """cov_ingest_last_stats: what the session's last device ingest did (also one that raised IngestFallback) — windows, 32 KiB segments and
+    how many of them found a record start, records, the most records one lane hopped over, records extracted a wave at a time
+    (k_bam_extract_long), false starts dropped by the repair."""
+    L = native.lib()
+    L.cov_ingest_last_stats.argtypes = [C.c_void_p, C.POINTER(_IngestStats)]
+    st = _IngestStats()
+    rc = L.cov_ingest_last_stats(session._h, C.byref(st))
+    if rc:
+        raise native.CovError(rc, "cov_ingest_last_stats")
+    return {k: int(getattr(st, k)) for k, _ in _IngestStats._fields_}
+
+
 def sam_ingest(session, path, mask=None, want_mates: bool = False, group: bool = False):
     """SAM text decoded on the device (covh_sam_open + covh_sam_gpu_ingest over cov_sam_*), window by window as the bytes are read.  path: a
     file, a FIFO, "-" for standard input, or an object with fileno() (a pipe's read end), which is read through /dev/fd.  Sets the session's

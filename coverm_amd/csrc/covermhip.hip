@@ -44,6 +44,7 @@ static_assert(sizeof(cov_batch) == 80 && offsetof(cov_batch, cigar) == 64 && off
 static_assert(sizeof(cov_contig_stats) == 128 && offsetof(cov_contig_stats, sum_identity_primary) == 40 && offsetof(cov_contig_stats, win_sum_d) == 56 &&
               offsetof(cov_contig_stats, first_record) == 88 && offsetof(cov_contig_stats, win_min_d) == 104 && offsetof(cov_contig_stats, hist_len) == 112 &&
               offsetof(cov_contig_stats, hist_off) == 120, "cov_contig_stats layout");
+static_assert(sizeof(cov_ingest_stats) == 56 && offsetof(cov_ingest_stats, max_hop_records) == 32 && offsetof(cov_ingest_stats, repaired_starts) == 48, "cov_ingest_stats layout");
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
 static_assert(sizeof(cov_genome_stats) == 24 && sizeof(cov_genome_stats) == sizeof(covk::DevGenomeStats) && offsetof(cov_genome_stats, genome_len) == offsetof(covk::DevGenomeStats, genome_len) &&
@@ -202,8 +203,11 @@ struct cov_session {
     DevBuf<u64> g_recbase[4], g_cigbase[4];
     // g_result: [3] inflate failures (u32) | extract failures (u32), [5] bytes in g_carry, [6] p0 of the window being parsed,
     // [7] key of the last record of the previous window (bit 63: there is one),
-    // [8 + 8 * (w % 4) ..] result block of window w (k_bam_verify)
+    // [4] entries in g_long (u32, zeroed in front of every k_bam_extract),
+    // [8 + WIN_RESULT_WORDS * (w % 4) ..] result block of window w (k_bam_verify)
     DevBuf<u64> g_result;
+    DevBuf<covi::LongRec> g_long;                          // the long records of the window being extracted (k_bam_extract -> k_bam_extract_long, one stream)
+    cov_ingest_stats ing_stats{}, ing_stats_last{};        // of the running ingest / of the last cov_ingest_end
     DevBuf<covi::tokpos_t> g_tok, g_tok2;
     DevBuf<u32> g_ntok, g_ntok2;
     hipStream_t ing_aux = nullptr;                         // k_lz_resolve / k_crc32 of round i run beside k_inflate of round i + 1
@@ -218,7 +222,7 @@ struct cov_session {
     bool ing_search_first = false, ing_open_end = false, ing_fed_any = false;
     uint64_t ing_span_lo = 0, ing_span_hi = 0;             // file bytes the span covers (store size estimate)
     uint64_t ing_tail_key = ~0ull;                         // key of the record cut by the end of the last window (~0: none)
-    u64 *h_winres = nullptr;                               // page-locked: 4 x 8 words, the windows' result blocks
+    u64 *h_winres = nullptr;                               // page-locked: 4 x WIN_RESULT_WORDS words, the windows' result blocks
     struct WinInfo { u64 N = 0; u32 n_seg = 0; u64 comp_end = 0; };
     WinInfo ing_win[4];
     uint32_t ing_batch = 0; int ing_check_crc = 1;         // ing_batch = rounds (= windows) launched so far
@@ -548,7 +552,7 @@ static hipError_t ingest_prepare_(cov_session *s) {
     for (int k = 0; k < 2; k++) { PREP(hipEventCreateWithFlags(&s->ing_inf_done[k], hipEventDisableTiming)); PREP(hipEventCreateWithFlags(&s->ing_lz_done[k], hipEventDisableTiming)); }
     for (int k = 0; k < 4; k++) PREP(hipEventCreateWithFlags(&s->ing_ver_done[k], hipEventDisableTiming));
     for (int k = 0; k < 3; k++) { PREP(hipEventCreateWithFlags(&s->ing_ext_done[k], hipEventDisableTiming)); PREP(hipEventCreateWithFlags(&s->ing_cdone[k], hipEventDisableTiming)); }
-    PREP(hipHostMalloc((void **)&s->h_winres, 4 * 8 * sizeof(u64), hipHostMallocDefault));
+    PREP(hipHostMalloc((void **)&s->h_winres, 4 * covi::WIN_RESULT_WORDS * sizeof(u64), hipHostMallocDefault));
     {   // page-locked mirror of the block table: room for a 25 GB file of ordinary ~20 KB blocks (cov_ingest_begin replaces it for a larger one)
         const size_t nc = (size_t)3 << 19;
         PREP(hipHostMalloc((void **)&s->h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
@@ -648,7 +652,7 @@ void cov_destroy(cov_session *s) {
     if (s->ing_parse) (void)hipStreamSynchronize(s->ing_parse);
     if (s->ing_ext) (void)hipStreamSynchronize(s->ing_ext);
     ingest_free_buffers(s);
-    s->g_result.release();
+    s->g_result.release(); s->g_long.release();
     if (s->ing_aux) (void)hipStreamDestroy(s->ing_aux);
     if (s->ing_parse) (void)hipStreamDestroy(s->ing_parse);
     for (int k = 0; k < 2; k++) { if (s->ing_inf_done[k]) (void)hipEventDestroy(s->ing_inf_done[k]); if (s->ing_lz_done[k]) (void)hipEventDestroy(s->ing_lz_done[k]); }
@@ -1732,7 +1736,7 @@ cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t 
     s->ing_K = choose_inflate_kernel(s);      // (also sets the kernel's dynamic-LDS limit on this session's device)
     s->ing_first_record = first_record_offset;
     s->ing_check_crc = check_crc ? 1 : 0;
-    HIPCHK(s->g_result.reserve(8 + 4 * 8, s->stream));
+    HIPCHK(s->g_result.reserve(8 + 4 * covi::WIN_RESULT_WORDS, s->stream));
     HIPCHK(s->g_carry.reserve(inflate_kernel(s).carry, s->stream));
     if (!s->g_crc_tab.p) {      // (cov_ingest_release between two files gave the tables back with the buffers)
         std::vector<u32> t(covi::crcw::TABLE_WORDS);
@@ -1748,7 +1752,7 @@ cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t 
         HIPCHK(hipHostMalloc((void **)&s->h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
         s->h_blocks_cap = nc;
     }
-    HIPCHK(hipMemsetAsync(s->g_result.p, 0, (8 + 4 * 8) * sizeof(u64), s->stream));
+    HIPCHK(hipMemsetAsync(s->g_result.p, 0, (8 + 4 * covi::WIN_RESULT_WORDS) * sizeof(u64), s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     s->ing_comp = compressed_bytes; s->ing_infl = 0; s->ing_blocks = 0; s->ing_launched = 0; s->ing_active = true;
     s->ing_round_start = 0; s->ing_prev_end = 0; s->ing_round_n = 0; s->ing_copy_cleared = -1;
@@ -1756,6 +1760,7 @@ cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t 
     s->ing_span_lo = 0; s->ing_span_hi = compressed_bytes; s->ing_tail_key = ~0ull;
     s->ing_ccap = std::min<u64>(inflate_kernel(s).cwin, compressed_bytes + 65536u + 128u);     // a small file is one buffer: the byte rule never fires
     s->ing_s_alloc = 0; for (double &x : s->ing_s_part) x = 0;
+    s->ing_stats = cov_ingest_stats{};
     return COV_OK;
 }
 
@@ -1819,8 +1824,13 @@ static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
         const u32 w = s->ing_extracted, q = w & 3u;
         if ((int64_t)w > must_upto) { if (hipEventQuery(s->ing_ver_done[q]) != hipSuccess) { (void)hipGetLastError(); break; } }   // not ready is not an error
         else { PartTimer pt{s->ing_s_part[3]}; HIPCHK(hipEventSynchronize(s->ing_ver_done[q])); }
-        const u64 *res = s->h_winres + 8 * q;
-        const u64 nrec = res[0], ncig = res[1];
+        const u64 *res = s->h_winres + covi::WIN_RESULT_WORDS * q;
+        const u64 nrec = res[0], ncig = res[1], nlong = res[8];
+        {
+            cov_ingest_stats &I = s->ing_stats;
+            I.windows++; I.segments += s->ing_win[q].n_seg; I.segments_with_start += res[11]; I.records += nrec;
+            I.max_hop_records = std::max<u64>(I.max_hop_records, res[10]); I.repaired_starts += res[9];
+        }
         u32 st = (u32)res[2];
         s->ing_tail_key = res[7];
         const bool span = s->ing_key_lo > 0 || s->ing_key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end;
@@ -1839,8 +1849,20 @@ static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
             covi::BamScan S{};
             S.u = s->g_win[w % 3u].p; S.N = s->ing_win[q].N; S.p0 = s->g_result.p + 6; S.seg_bytes = 32768; S.n_seg = s->ing_win[q].n_seg;
             S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = 0; S.key_lo = s->ing_key_lo; S.key_hi = s->ing_key_hi; S.search_first = 0;
+            S.walk_cap = s->ing_K.carry;
+            u32 *n_long = reinterpret_cast<u32 *>(s->g_result.p + 4);
+            if (nlong) {      // (sized by the window's own count; the buffer only ever grows)
+                PartTimer alloc{s->ing_s_alloc};
+                HIPCHK(s->g_long.reserve((size_t)nlong, ps));
+                HIPCHK(hipMemsetAsync(n_long, 0, sizeof(u32), ps));
+            }
             hipLaunchKernelGGL(covi::k_bam_extract, dim3((S.n_seg * s->ing_K.ext_parts + 63) / 64), dim3(64), 0, ps, S, (const covi::SegInfo *)s->g_seg[q].p, (const u64 *)s->g_recbase[q].p,
-                               (const u64 *)s->g_cigbase[q].p, RS, reinterpret_cast<u32 *>(s->g_result.p + 3) + 1, s->ing_K.ext_parts);
+                               (const u64 *)s->g_cigbase[q].p, RS, reinterpret_cast<u32 *>(s->g_result.p + 3) + 1, s->ing_K.ext_parts,
+                               s->g_long.p, n_long, (u32)nlong);
+            if (nlong) {
+                hipLaunchKernelGGL(covi::k_bam_extract_long, dim3((u32)((nlong + 3) / 4)), dim3(256), 0, ps, S, (const covi::LongRec *)s->g_long.p, (u32)nlong, RS);
+                s->ing_stats.long_records += nlong;
+            }
             HIPCHK(hipGetLastError());
             s->ing_rec_total += nrec; s->ing_cig_total += ncig;
         }
@@ -1942,6 +1964,7 @@ static cov_status launch_round_(cov_session *s, uint64_t n64, bool final) {
     S.u = win.p; S.N = K.carry + wbytes; S.p0 = s->g_result.p + 6; S.seg_bytes = 32768; S.n_seg = (u32)((S.N + S.seg_bytes - 1) / S.seg_bytes);
     S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = (final && !s->ing_open_end) ? 1 : 0;
     S.key_lo = s->ing_key_lo; S.key_hi = s->ing_key_hi; S.search_first = (w == 0 && s->ing_search_first) ? 1 : 0;
+    S.walk_cap = K.carry;
     s->ing_win[q].N = S.N; s->ing_win[q].n_seg = S.n_seg; s->ing_win[q].comp_end = n ? s->h_blocks[b0 + n - 1].in_off + s->h_blocks[b0 + n - 1].in_len + 8 : s->ing_comp;
     hipStream_t ps = s->ing_parse;
     if (w >= 3) HIPCHK(hipStreamWaitEvent(ps, s->ing_ext_done[w % 3u], 0));     // the carried tail goes in front of a buffer whose records must be out
@@ -1949,10 +1972,10 @@ static cov_status launch_round_(cov_session *s, uint64_t n64, bool final) {
                        w == 0 ? s->ing_first_record : 0ull, s->g_result.p + 6);
     hipLaunchKernelGGL(covi::k_bam_find, dim3((S.n_seg + 3) / 4), dim3(256), 0, ps, S, s->g_seg[q].p);
     hipLaunchKernelGGL(covi::k_bam_hop, dim3((S.n_seg + 63) / 64), dim3(64), 0, ps, S, s->g_seg[q].p);
-    hipLaunchKernelGGL(covi::k_bam_verify, dim3(1), dim3(1024), 0, ps, S, s->g_seg[q].p, s->g_recbase[q].p, s->g_cigbase[q].p, s->g_result.p + 8 + 8 * q,
+    hipLaunchKernelGGL(covi::k_bam_verify, dim3(1), dim3(1024), 0, ps, S, s->g_seg[q].p, s->g_recbase[q].p, s->g_cigbase[q].p, s->g_result.p + 8 + covi::WIN_RESULT_WORDS * q,
                        s->g_carry.p, (u64)K.carry, s->g_result.p + 5, s->g_result.p + 7);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_winres + 8 * q, s->g_result.p + 8 + 8 * q, 8 * sizeof(u64), hipMemcpyDeviceToHost, ps));
+    HIPCHK(hipMemcpyAsync(s->h_winres + covi::WIN_RESULT_WORDS * q, s->g_result.p + 8 + covi::WIN_RESULT_WORDS * q, covi::WIN_RESULT_WORDS * sizeof(u64), hipMemcpyDeviceToHost, ps));
     HIPCHK(hipEventRecord(s->ing_ver_done[q], ps));
     s->ing_launched += n;
     s->ing_batch++;
@@ -2071,6 +2094,12 @@ cov_status cov_ingest_feed(cov_session *s, int slot, const void *host_bytes, uin
     return COV_OK;
 }
 
+cov_status cov_ingest_last_stats(const cov_session *s, cov_ingest_stats *out) {
+    if (!s || !out) return COV_ERR_INVALID_ARG;
+    *out = s->ing_stats_last;
+    return COV_OK;
+}
+
 static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out);
 cov_status cov_ingest_end(cov_session *s, uint64_t *n_records_out) {
     const cov_status rc = ingest_end_(s, n_records_out);
@@ -2099,6 +2128,7 @@ static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out) {
     HIPCHK(hipMemcpyAsync(glob, s->g_result.p, sizeof glob, hipMemcpyDeviceToHost, s->ing_parse));
     HIPCHK(hipStreamSynchronize(s->ing_parse));
     HIPCHK(hipStreamSynchronize(s->stream));
+    s->ing_stats_last = s->ing_stats;
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] ingest: %llu blocks in %u windows of %u, device allocations %.3fs; host time in drain %.3fs (waiting for a verification %.3fs), in launches %.3fs (drains inside included), in upload calls %.3fs\n",
                 (unsigned long long)s->ing_blocks, s->ing_batch, K.round_blocks, s->ing_s_alloc, s->ing_s_part[0], s->ing_s_part[3], s->ing_s_part[1], s->ing_s_part[2]);

@@ -587,8 +587,11 @@ void after_ingest(Run &R, cov_session *s, const Sample &S, Route route, Fed &fed
 void report_device_reader(cov_session *s, const Sample &S, Route route, const Fed &fed, uint32_t span_index, uint32_t span_count) {
     const double *tm = fed.tm;
     if (route == Route::DeviceBgzf) {
-        fprintf(stderr, "[coverm-amd] %s span %u/%u: device ingest: first upload after %.3fs, file read %.3fs, staging waits %.3fs, header walk %.3fs, feed calls %.3fs, inflate tail + parse %.3fs, total %.3fs, %llu records, bytes from %s\n",
+        cov_ingest_stats ist{};
+        (void)cov_ingest_last_stats(s, &ist);
+        fprintf(stderr, "[coverm-amd] %s span %u/%u: device ingest: first upload after %.3fs, file read %.3fs, staging waits %.3fs, header walk %.3fs, feed calls %.3fs, inflate tail + parse %.3fs, total %.3fs, %llu records, long records %llu, repaired starts %llu, longest hop %llu, bytes from %s\n",
                 S.stoit.c_str(), span_index, span_count, tm[4], tm[0], tm[1], tm[5], tm[6], tm[2], tm[3], (unsigned long long)fed.nrec,
+                (unsigned long long)ist.long_records, (unsigned long long)ist.repaired_starts, (unsigned long long)ist.max_hop_records,
                 tm[7] == 2 ? "the mapped file (registered up front)" : tm[7] == 1 ? "the mapped file" : tm[7] == 3 ? "staging slots (copied from the mapping)" : "staging slots (pread)");
         return;
     }

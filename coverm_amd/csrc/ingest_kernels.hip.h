@@ -14,12 +14,15 @@
 //                   bytes of all matches that are ready spread over the 64 lanes
 //   k_crc32_wave    every inflated block against the CRC-32 of its BGZF trailer: a wave per block, 8-byte columns, csrc/crc_wave_core.h
 //   k_crc32         the same with a lane per block (with the lane-per-block inflate)
-//   k_bam_find      per segment of the inflated stream: first offset from which a chain of 8 plausible records starts
+//   k_bam_find      per segment of the inflated stream: first offset from which a chain of 8 plausible records starts (the record
+//                   test: csrc/bam_record_core.h; fixed fields per lane, the survivors' tags by the whole wave)
 //   k_bam_hop       per segment: hop the records (block_size chain), count records and CIGAR words, note where it landed
 //   k_bam_verify    every segment's chain must land exactly on the start the next segment found (then the result equals the
-//                   serial hop by induction, as in csrc/host_bam.cpp); exclusive scans of the counts
+//                   serial hop by induction, as in csrc/host_bam.cpp); a start a chain misses is a false one and is dropped,
+//                   a bounded number of times; exclusive scans of the counts
 //   k_bam_extract   per segment: second hop, one record at a time per lane, fields written straight into the session's
 //                   record store (tid, pos, flag, mapq, l_seq, NM + its type, CIGAR words)
+//   k_bam_extract_long   one WAVE per record with a long CIGAR or long tags: its CIGAR words and its NM
 //
 // Anything irregular (malformed stream, CRC mismatch, speculation that does not verify) raises
 // a flag and the host decodes that file with the CPU reader instead: the device path is an accelerator, never a different
@@ -824,6 +827,7 @@ struct BamScan {
     // somewhere inside the file, its first record boundary is searched like any other segment's
     long long key_lo, key_hi;
     int search_first;
+    u64 walk_cap;          // largest block_size the record search accepts (the carry buffer's capacity: bam_record_core.h fixed_fields)
 };
 __device__ __forceinline__ long long rec_key(int tid) { return tid < 0 ? 0x7fffffffll : (long long)tid; }
 
@@ -836,44 +840,30 @@ __device__ __forceinline__ u32 ld32(const uint8_t *p) {   // unaligned little-en
 }
 __device__ __forceinline__ u32 ld16(const uint8_t *p) { return (u32)p[0] | ((u32)p[1] << 8); }
 
-// Can a record start at offset o?  Returns its end offset or 0.  Same tests as csrc/host_bam.cpp plausible_record.
-__device__ __forceinline__ u64 plausible_record(const BamScan &S, u64 o) {
-    if (o + 36 > S.N) return 0;
-    const uint8_t *r = S.u + o;
-    const u32 bs = ld32(r);
-    if (bs < 32u || o + 4 + (u64)bs > S.N) return 0;
-    const int rid = (int)ld32(r + 4), pos = (int)ld32(r + 8), nrid = (int)ld32(r + 24);
-    const u32 lname = r[12], ncig = ld16(r + 16), lseq = ld32(r + 20);
-    if (rid < -1 || rid >= S.n_ref || nrid < -1 || nrid >= S.n_ref || pos < -1 || lname == 0u) return 0;
-    if (rid >= 0 && (u32)pos > S.ref_len[rid]) return 0;
-    const u64 fixed = 32ull + lname + 4ull * ncig + ((u64)lseq + 1ull) / 2 + lseq;
-    if (fixed > bs) return 0;
-    if (r[36 + lname - 1] != 0) return 0;
-    // The aux area must parse as tags that end exactly at the record end.  Without this test a stray offset whose "block_size"
-    // happens to jump onto a real record start far away passes (the next seven records are then real ones): seen once per
-    // ~10^7 tested offsets on a 6 GB stream, where it cost a whole-file fallback to the CPU reader.
-    const uint8_t *p = r + 4 + fixed, *end = r + 4 + bs;
-    for (int t = 0; t < 32 && p < end; t++) {
-        if (p + 3 > end) return 0;
-        const uint8_t ty = p[2];
-        p += 3;
-        if (ty == 'A' || ty == 'c' || ty == 'C') p += 1;
-        else if (ty == 's' || ty == 'S') p += 2;
-        else if (ty == 'i' || ty == 'I' || ty == 'f') p += 4;
-        else if (ty == 'Z' || ty == 'H') { int g = 0; while (p < end && *p && g < 4096) { p++; g++; } if (p >= end || *p) return 0; p++; }
-        else if (ty == 'B') {
-            if (p + 5 > end) return 0;
-            const uint8_t st = p[0];
-            if (st != 'c' && st != 'C' && st != 's' && st != 'S' && st != 'i' && st != 'I' && st != 'f') return 0;
-            const u32 cnt = ld32(p + 1);
-            const u32 es = (st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u;
-            if ((u64)(end - p - 5) / es < cnt) return 0;
-            p += 5 + (u64)cnt * es;
-        } else return 0;
-        if (p > end) return 0;
+}  // namespace covi
+// The record test, the NM scan and the CG:B,I lookup: csrc/bam_record_core.h (plain C++, run on the CPU in tests/test_bam_record_core.py).
+#define BAMREC_FN __device__ __forceinline__
+#define BAMREC_LD32(p) covi::ld32(p)
+#include "bam_record_core.h"
+namespace covi {
+__device__ __forceinline__ bamrec::Stream rec_stream(const BamScan &S) { return bamrec::Stream{S.u, S.N, S.n_ref, S.ref_len, S.walk_cap}; }
+// The NUL of a Z / H string found by the whole wave: every lane looks at 16 bytes of a 1024-byte step (four aligned words), the lowest
+// lane with a NUL wins.  Every lane of the wave must call it with the same arguments.
+struct WaveNul {
+    __device__ __forceinline__ u64 first_nul(const uint8_t *u, u64 p, u64 end) const {
+        const u32 lane = threadIdx.x & 63u;
+        for (u64 a = p & ~3ull; a < end; a += bamrec::STEP_BYTES) {
+            const u32 m = bamrec::lane_nul_mask(u, a, lane, p, end);
+            const u64 hit = __ballot(m != 0u);
+            if (hit) {
+                const int l = __ffsll((long long)hit) - 1;
+                const u32 ml = (u32)__builtin_amdgcn_readlane((int)m, l);
+                return a + 16ull * (u32)l + (u32)(__ffs((int)ml) - 1);
+            }
+        }
+        return bamrec::NONE;
     }
-    return o + 4 + bs;
-}
+};
 
 struct SegInfo {
     u64 start;     // first record start found in the segment (~0 = none)
@@ -887,89 +877,60 @@ struct SegInfo {
     // record that starts at or beyond start + (p + 1) * EXT_PIECE bytes — part_off[p] bytes behind `start` — with part_rec[p] / part_cig[p]
     // of the span's records / CIGAR words in front of it.  Pieces the chain never reaches are empty (part_off = landed - start).
     u32 part_off[3], part_rec[3], part_cig[3];
+    u32 n_long;                  // of n_rec: records k_bam_extract leaves to k_bam_extract_long (bamrec::is_long)
 };
+static_assert(sizeof(SegInfo) == 80, "SegInfo: 80 bytes per segment");
 constexpr u32 EXT_PARTS = 4, EXT_PIECE = 8192;
+constexpr u32 REPAIR_BUDGET = 64;      // false starts k_bam_verify drops per window before it gives the file up
+// A long record waiting for its wave.
+struct LongRec { u64 off, ri, ci; u32 words, pad; };      // the record's offset in the window, its index in the store, where its CIGAR words go, how many
 
-// One wave per segment: lanes test consecutive offsets for an 8-record plausible chain; the lowest hit wins.  The segment that
-// holds *p0 starts there by definition; segments below it are dead.
-// A record whose CIGAR has more than 65535 operations stores `<l_seq>S<ref_len>N` in the CIGAR field and the real one in CG:B,I; htslib
-// swaps it back in while reading (bam_tag2cigar, sam.c), so record.cigar() at contig.rs:168 sees the real CIGAR.  The conditions of
-// csrc/host_bam.cpp real_cigar_from_cg: exactly two operations, mapped, the first one `<l_seq>S`, the first CG tag of type B,I / B,i
-// with at least as many words as the placeholder.  Returns the words and their count, or nullptr.
-__device__ __forceinline__ const uint8_t *cg_cigar(const uint8_t *r, const uint8_t *end, u32 &cnt) {
-    const u32 n_cig = ld16(r + 16), l_read_name = r[12], l_seq = ld32(r + 20);
-    if (n_cig != 2u || (int)ld32(r + 4) < 0 || (int)ld32(r + 8) < 0) return nullptr;
-    const uint8_t *c = r + 36 + l_read_name;
-    if (c + 8 > end) return nullptr;
-    const u32 c0 = ld32(c);
-    if ((c0 & 15u) != 4u || (c0 >> 4) != l_seq) return nullptr;
-    const uint8_t *p = c + 8 + ((u64)l_seq + 1ull) / 2 + l_seq;
-    if (p > end) return nullptr;
-    while (p + 3 <= end) {
-        const bool is_cg = p[0] == 'C' && p[1] == 'G';
-        const uint8_t t = p[2];
-        p += 3;
-        u32 sz;
-        if (t == 'A' || t == 'c' || t == 'C') sz = 1;
-        else if (t == 's' || t == 'S') sz = 2;
-        else if (t == 'i' || t == 'I' || t == 'f') sz = 4;
-        else if (t == 'Z' || t == 'H') {
-            while (p < end && *p) p++;
-            if (p >= end) return nullptr;
-            p++;
-            continue;
-        } else if (t == 'B') {
-            if (p + 5 > end) return nullptr;
-            const uint8_t st = p[0];
-            const u32 n = ld32(p + 1);
-            const u32 es = (st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u;
-            if ((u64)(end - p - 5) / es < n) return nullptr;
-            if (is_cg && (st == 'I' || st == 'i')) { cnt = n; return (n >= n_cig && n < (1u << 29)) ? p + 5 : nullptr; }
-            p += 5 + (u64)n * es;
-            continue;
-        } else return nullptr;
-        if (p + sz > end) return nullptr;
-        p += sz;
-    }
-    return nullptr;
-}
-
+// One wave per segment looks for the segment's first record start: the lowest offset at which a chain of eight plausible records begins.
+// The segment that holds *p0 starts there by definition; segments below it are dead.
+// Cheap per lane, thorough per wave.  Per step the 64 lanes test 64 consecutive offsets against the fixed fields and the name's NUL only
+// (bamrec::fixed_fields: a dozen loads, no loop; nearly every offset fails here).  The survivors are handed on as the set bits of one
+// ballot, lowest first — no list, no LDS — and each is checked by the WHOLE wave (bamrec::chain_start over WaveNul): the chain of up to
+// eight records is followed with wave-uniform offsets, fixed-size tags and B arrays are skipped by arithmetic, and the NUL of a Z / H
+// string is found 1024 bytes per step, 16 per lane, by ballot.  A 40 kB MM:Z costs 40 steps instead of 40 000 dependent byte loads, and no
+// step walks further than walk_cap bytes for one candidate.
+// (hipcc, gfx950: 53 VGPRs, 89 SGPRs, eight waves per SIMD, no LDS, no scratch.)
 __global__ __launch_bounds__(256) void k_bam_find(BamScan S, SegInfo *__restrict__ seg) {
     const int lane = threadIdx.x & 63;
     const u32 k = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (k >= S.n_seg) return;
     const u64 p0 = *S.p0;
     const u64 lo = (u64)k * S.seg_bytes, hi = min(S.N, lo + S.seg_bytes);
+    const bamrec::Stream B = rec_stream(S);
     u64 found = ~0ull;
     if (hi <= p0) {}
     else if (lo <= p0 && !S.search_first) found = p0 < S.N ? p0 : ~0ull;
     else {
         for (u64 base = max(lo, p0); base < hi && found == ~0ull; base += 64) {
             const u64 o = base + (u64)lane;
-            bool ok = false;
-            if (o < hi) {
-                u64 q = o; int chain = 0;
-                while (chain < 8) { const u64 e = plausible_record(S, q); if (!e) break; q = e; chain++; if (q == S.N) break; }
-                ok = chain == 8 || (chain > 0 && q == S.N);
+            u64 aux = 0;
+            u64 m = __ballot(o < hi && bamrec::fixed_fields(B, o, aux) != 0);
+            while (m) {
+                const u32 bit = (u32)(__ffsll((long long)m) - 1);
+                m &= m - 1;
+                if (bamrec::chain_start(WaveNul{}, B, base + bit)) { found = base + bit; break; }
             }
-            const u64 m = __ballot(ok);
-            if (m) found = base + (u64)(__ffsll((long long)m) - 1);
         }
     }
-    if (lane == 0) { SegInfo s; s.start = found; s.landed = 0; s.n_rec = 0; s.n_cig = 0; s.flags = 0; s.first_key = s.last_key = 0; s.n_hop = 0; seg[k] = s; }
+    if (lane == 0) {
+        SegInfo s; s.start = found; s.landed = 0; s.n_rec = 0; s.n_cig = 0; s.flags = 0; s.first_key = s.last_key = 0; s.n_hop = 0; s.n_long = 0;
+        for (u32 x = 0; x < 3u; x++) s.part_off[x] = s.part_rec[x] = s.part_cig[x] = 0;
+        seg[k] = s;
+    }
 }
 
 // One lane per segment that has a start: hop to the first record at or beyond the next live segment's start (bounded by the
-// segment end of the LAST segment before that one), counting records and CIGAR words.
-__global__ __launch_bounds__(64) void k_bam_hop(BamScan S, SegInfo *__restrict__ seg) {
-    const u32 k = blockIdx.x * 64u + threadIdx.x;
-    if (k >= S.n_seg) return;
+// segment end of the LAST segment before that one), counting records, CIGAR words and long records.  Also the repair's re-hop (k_bam_verify).
+__device__ __forceinline__ void hop_segment(const BamScan &S, SegInfo *seg, u32 k) {
     SegInfo s = seg[k];
-    if (s.start == ~0ull) return;
     // the hop ends at the start found by the next segment that has one
     u64 limit = S.N;
     for (u32 j = k + 1; j < S.n_seg; j++) { const u64 st = seg[j].start; if (st != ~0ull) { limit = st; break; } }
-    u64 q = s.start; u32 nr = 0, nc = 0, fl = 0, nh = 0, k_first = 0, k_last = 0;
+    u64 q = s.start; u32 nr = 0, nc = 0, fl = 0, nh = 0, k_first = 0, k_last = 0, nl = 0;
     u32 part = 0;        // pieces closed so far
     while (q < limit && q + 4 <= S.N) {
         while (part < EXT_PARTS - 1u && q >= s.start + (u64)(part + 1u) * EXT_PIECE) { s.part_off[part] = (u32)(q - s.start); s.part_rec[part] = nr; s.part_cig[part] = nc; part++; }
@@ -984,57 +945,88 @@ __global__ __launch_bounds__(64) void k_bam_hop(BamScan S, SegInfo *__restrict__
             u32 words = ncig;
             if (ncig == 2u) {    // `<l_seq>S <n>N` may be the placeholder of a CIGAR stored in CG:B,I (SAM spec 4.2.2): the store takes the real one
                 u32 cnt = 0;
-                if (cg_cigar(r, r + 4 + bs, cnt) != nullptr) words = cnt;
+                if (bamrec::cg_cigar(bamrec::Serial{}, S.u, q, q + 4 + bs, cnt) != bamrec::NONE) words = cnt;
             }
+            const u64 fixed = bamrec::fixed_bytes(r[12], ncig, ld32(r + 20));
+            if (fixed <= bs && bamrec::is_long(words, bs - fixed)) nl++;
             nr++; nc += words;
         }
         q += 4 + (u64)bs;
     }
     for (; part < EXT_PARTS - 1u; part++) { s.part_off[part] = (u32)(q - s.start); s.part_rec[part] = nr; s.part_cig[part] = nc; }
-    s.landed = q; s.n_rec = nr; s.n_cig = nc; s.flags = fl; s.first_key = k_first; s.last_key = k_last; s.n_hop = nh;
+    s.landed = q; s.n_rec = nr; s.n_cig = nc; s.flags = fl; s.first_key = k_first; s.last_key = k_last; s.n_hop = nh; s.n_long = nl;
     seg[k] = s;
 }
+__global__ __launch_bounds__(64) void k_bam_hop(BamScan S, SegInfo *seg) {
+    const u32 k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= S.n_seg || seg[k].start == ~0ull) return;
+    hop_segment(S, seg, k);
+}
 
-// Single workgroup: chain verification + exclusive scans over segments (records, CIGAR words) + the tail.
+// Single workgroup: chain verification, the repair of false starts, exclusive scans over segments (records, CIGAR words) + the tail.
 // result[0] = records of this window, [1] = CIGAR words, [2] = status (0 ok, 1 chain mismatch, 2 truncated, 4 needs the CPU
 // reader, 8 tail larger than the carry buffer, 64 record keys (tid) decrease somewhere in the window — looked at for spans
 // only: a span trusts the file's order when it drops its neighbours' records, the whole-file path reports disorder from
 // cov_finish in file order with the other per-record errors), [3] = offset where the tail starts (first byte no record of this window owns),
-// [4..6] = first bad segment / its start / where its hop landed.  The tail [result[3], N) goes to `carry`, its length to *carry_len.
-__global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *__restrict__ seg, u64 *__restrict__ rec_base, u64 *__restrict__ cig_base,
+// [4..6] = first bad segment / its start / where its hop landed, [7] = key of the tail's record, [8] = long records (k_bam_extract_long's
+// list entries), [9] = starts dropped by the repair, [10] = most records one hop went over, [11] = segments with a start.
+// The tail [result[3], N) goes to `carry`, its length to *carry_len.
+// The repair: a segment whose hop does not land on the next live segment's start has met a false start there — eight record-shaped images
+// inside a B array, say.  The chain in front of it comes from p0 through verified starts, so the suspect is the start it missed: thread 0
+// marks that start dead, hops the segment in front again up to the following live start (counts, keys, disorder flag and extraction
+// pieces are the hop's own), and the pass over the segments runs again — REPAIR_BUDGET times per window at the most, then status 1 as ever.
+constexpr u32 WIN_RESULT_WORDS = 12;
+__global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u64 *__restrict__ rec_base, u64 *__restrict__ cig_base,
                                                      u64 *__restrict__ result, uint8_t *__restrict__ carry, u64 carry_cap, u64 *__restrict__ carry_len,
                                                      u64 *__restrict__ prev_key) {
     __shared__ u64 s_rec[1024], s_cig[1024];
     __shared__ u32 s_kfirst[1024], s_klast[1024], s_khave[1024];
-    __shared__ u32 s_bad;
+    __shared__ u32 s_bad, s_long, s_maxhop, s_live;
     __shared__ u64 s_tail, s_badk;
     const u32 t = threadIdx.x;
-    if (t == 0) { s_bad = 0; s_tail = min(*S.p0, S.N); s_badk = ~0ull; }    // no live segment: everything from p0 on is tail
-    __syncthreads();
     const u32 per = (S.n_seg + 1023u) / 1024u;
-    const u32 k0 = t * per, k1 = min(S.n_seg, k0 + per);
-    u64 nr = 0, nc = 0; u32 bad = 0;
-    u32 kf = 0, kl = 0, khave = 0;      // first / last key over this thread's segments
-    for (u32 k = k0; k < k1; k++) {
-        const SegInfo s = seg[k];
-        if (s.start == ~0ull) continue;
-        if (s.n_hop) {
-            if (s.flags & 2u) bad |= 64u;
-            if (khave && s.first_key < kl) bad |= 64u;
-            if (!khave) kf = s.first_key;
-            kl = s.last_key; khave = 1u;
+    const u32 k0 = min(S.n_seg, t * per), k1 = min(S.n_seg, k0 + per);
+    u32 repaired = 0;
+    for (;;) {
+        if (t == 0) { s_bad = 0; s_tail = min(*S.p0, S.N); s_badk = ~0ull; s_long = 0; s_maxhop = 0; s_live = 0; }    // no live segment: everything from p0 on is tail
+        __syncthreads();
+        u64 nr = 0, nc = 0; u32 bad = 0, nl = 0, mh = 0, live = 0;
+        u32 kf = 0, kl = 0, khave = 0;      // first / last key over this thread's segments
+        for (u32 k = k0; k < k1; k++) {
+            const SegInfo s = seg[k];
+            if (s.start == ~0ull) continue;
+            live++;
+            if (s.n_hop) {
+                if (s.flags & 2u) bad |= 64u;
+                if (khave && s.first_key < kl) bad |= 64u;
+                if (!khave) kf = s.first_key;
+                kl = s.last_key; khave = 1u;
+            }
+            u64 want = S.N; bool last_live = true;
+            for (u32 j = k + 1; j < S.n_seg; j++) { const u64 st = seg[j].start; if (st != ~0ull) { want = st; last_live = false; break; } }
+            if (last_live) {
+                s_tail = s.landed;                                  // exactly one segment is the last live one
+                if (S.final && s.landed != S.N) { bad |= 2u; atomicMin(&s_badk, (u64)k); }
+            } else if (s.landed != want) { bad |= 1u; atomicMin(&s_badk, (u64)k); }
+            nr += s.n_rec; nc += s.n_cig; nl += s.n_long; mh = max(mh, s.n_hop);
         }
-        u64 want = S.N; bool last_live = true;
-        for (u32 j = k + 1; j < S.n_seg; j++) { const u64 st = seg[j].start; if (st != ~0ull) { want = st; last_live = false; break; } }
-        if (last_live) {
-            s_tail = s.landed;                                  // exactly one segment is the last live one
-            if (S.final && s.landed != S.N) { bad |= 2u; atomicMin(&s_badk, (u64)k); }
-        } else if (s.landed != want) { bad |= 1u; atomicMin(&s_badk, (u64)k); }
-        nr += s.n_rec; nc += s.n_cig;
+        if (bad) atomicOr(&s_bad, bad);
+        if (nl) atomicAdd(&s_long, nl);
+        if (mh) atomicMax(&s_maxhop, mh);
+        if (live) atomicAdd(&s_live, live);
+        s_rec[t] = nr; s_cig[t] = nc; s_kfirst[t] = kf; s_klast[t] = kl; s_khave[t] = khave;
+        __syncthreads();
+        // (a truncated last segment is the highest live one: with a mismatch anywhere, s_badk is a mismatching segment)
+        if (!(s_bad & 1u) || repaired == REPAIR_BUDGET) break;
+        if (t == 0) {
+            const u32 k = (u32)s_badk;
+            for (u32 j = k + 1; j < S.n_seg; j++) if (seg[j].start != ~0ull) { seg[j].start = ~0ull; break; }
+            hop_segment(S, seg, k);
+            __threadfence_block();
+        }
+        repaired++;
+        __syncthreads();
     }
-    if (bad) atomicOr(&s_bad, bad);
-    s_rec[t] = nr; s_cig[t] = nc; s_kfirst[t] = kf; s_klast[t] = kl; s_khave[t] = khave;
-    __syncthreads();
     const u64 tail = min(s_tail, S.N), tail_len = S.N - tail;
     const bool tail_fits = tail_len <= carry_cap;
     if (t == 0) {
@@ -1056,6 +1048,7 @@ __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *__restr
         // key of the record the tail begins with (~0 when there is no tail or its tid is not here yet): a span's reader checks
         // that the record cut by the end of its bytes lies beyond its key range
         result[7] = (tail_len >= 8) ? (u64)rec_key((int)ld32(S.u + tail + 4)) : ~0ull;
+        result[8] = s_long; result[9] = repaired; result[10] = s_maxhop; result[11] = s_live;
         *carry_len = tail_fits ? tail_len : 0ull;
     }
     __syncthreads();
@@ -1087,47 +1080,12 @@ struct RecStore {
     int32_t *mtid; u64 *qh1; u32 *qh2;
 };
 
-// Linear aux scan for NM (csrc/host_bam.cpp scan_aux without the CG part).
-__device__ __forceinline__ u32 scan_nm(const uint8_t *p, const uint8_t *end, u32 &nm) {
-    while (p + 3 <= end) {
-        const bool is_nm = p[0] == 'N' && p[1] == 'M';
-        const uint8_t t = p[2];
-        p += 3;
-        u32 sz;
-        if (t == 'A' || t == 'c' || t == 'C') sz = 1;
-        else if (t == 's' || t == 'S') sz = 2;
-        else if (t == 'i' || t == 'I' || t == 'f') sz = 4;
-        else if (t == 'Z' || t == 'H') {
-            if (is_nm) return 2u;
-            while (p < end && *p) p++;
-            if (p >= end) return 0u;
-            p++;
-            continue;
-        } else if (t == 'B') {
-            if (p + 5 > end) return 0u;
-            const uint8_t st = p[0];
-            const u32 cnt = ld32(p + 1);
-            const u32 es = (st == 'c' || st == 'C') ? 1u : (st == 's' || st == 'S') ? 2u : 4u;
-            if (is_nm) return 2u;
-            if ((u64)(end - p - 5) / es < cnt) return 0u;
-            p += 5 + (u64)cnt * es;
-            continue;
-        } else return 0u;
-        if (p + sz > end) return 0u;
-        if (is_nm) {
-            if (t == 'C') { nm = p[0]; return 1u; }
-            if (t == 'S') { nm = ld16(p); return 1u; }
-            if (t == 'I') { nm = ld32(p); return 1u; }
-            return 2u;
-        }
-        p += sz;
-    }
-    return 0u;
-}
-
 // One lane per segment: second hop; every record's fields go straight into the record store.
+// A long record (bamrec::is_long, the test k_bam_hop counted n_long with) gets its fixed columns and its CIGAR range here like any other;
+// its CIGAR copy and NM scan are left to k_bam_extract_long through `longs` (appended at *n_long: the window has exactly result[8] of them).
 __global__ __launch_bounds__(64) void k_bam_extract(BamScan S, const SegInfo *__restrict__ seg, const u64 *__restrict__ rec_base,
-                                                    const u64 *__restrict__ cig_base, RecStore R, u32 *__restrict__ n_bad, u32 parts) {
+                                                    const u64 *__restrict__ cig_base, RecStore R, u32 *__restrict__ n_bad, u32 parts,
+                                                    LongRec *__restrict__ longs, u32 *__restrict__ n_long, u32 long_cap) {
     // one lane per piece of a segment's chain (parts = EXT_PARTS), or per segment (parts = 1: the pieces walked by one lane)
     const u32 kp = blockIdx.x * 64u + threadIdx.x, k = kp / parts, part = parts == 1u ? 0u : kp % parts;
     if (k >= S.n_seg) return;
@@ -1202,12 +1160,19 @@ __global__ __launch_bounds__(64) void k_bam_extract(BamScan S, const SegInfo *__
         const uint8_t *c = r + 36 + l_read_name;
         const uint8_t *aux = c + 4ull * n_cig + ((u64)l_seq + 1ull) / 2 + l_seq;
         u32 words = n_cig;
+        bool is_long = false;
         if (aux > end) { atomicAdd(n_bad, 1u); aux = end; if (ncw) flush_cigar(ci, true); }     // (its words are skipped, not written: what waits goes out first)
         else {
             u32 cnt = 0;
-            const uint8_t *cg = n_cig == 2u ? cg_cigar(r, end, cnt) : nullptr;      // (the same test k_bam_hop counted the words with)
-            if (cg) { words = cnt; c = cg; }
-            if (words <= 4u) {         // short reads: the words wait with those of the lane's neighbouring records
+            const u64 cg = n_cig == 2u ? bamrec::cg_cigar(bamrec::Serial{}, S.u, q, q + 4 + bs, cnt) : bamrec::NONE;      // (the same test k_bam_hop counted the words with)
+            if (cg != bamrec::NONE) { words = cnt; c = S.u + cg; }
+            is_long = bamrec::is_long(words, (u64)(end - aux));
+            if (is_long) {             // a wave's work: k_bam_extract_long
+                if (ncw) flush_cigar(ci, true);
+                const u32 at = atomicAdd(n_long, 1u);
+                if (at < long_cap) { LongRec e; e.off = q; e.ri = ri; e.ci = ci; e.words = words; e.pad = 0; longs[at] = e; }
+                else atomicAdd(n_bad, 1u);      // (cannot happen: the list has k_bam_hop's count of them)
+            } else if (words <= 4u) {         // short reads: the words wait with those of the lane's neighbouring records
                 for (u32 x = 0; x < words; x++) Cw[ncw + x] = ld32(c + 4ull * x);
                 ncw += words;
                 if (ncw >= 4u) flush_cigar(ci + words, false);
@@ -1217,7 +1182,7 @@ __global__ __launch_bounds__(64) void k_bam_extract(BamScan S, const SegInfo *__
             }
         }
         u32 nm = 0;
-        Bk[nb] = (uint8_t)scan_nm(aux, end, nm);
+        Bk[nb] = is_long ? (uint8_t)0 : (uint8_t)bamrec::scan_nm(bamrec::Serial{}, S.u, (u64)(aux - S.u), (u64)(end - S.u), nm);
         B[16 + nb] = nm;
         nb++; ri++; ci += words;
         if (nb == 4u) flush(ri - 4);
@@ -1225,6 +1190,27 @@ __global__ __launch_bounds__(64) void k_bam_extract(BamScan S, const SegInfo *__
     }
     if (nb) flush(ri - nb);
     if (ncw) flush_cigar(ci, true);
+}
+
+// One wave per long record, behind k_bam_extract on its stream: the CIGAR words (the real ones out of CG:B,I, looked up by the wave) leave
+// as coalesced copies, a word per lane and step, and the tags are scanned for NM by the wave (bamrec::scan_nm over WaveNul), whose result
+// replaces the placeholder k_bam_extract stored in nm / nm_kind.
+// (hipcc, gfx950: 48 VGPRs, 79 SGPRs, eight waves per SIMD, no LDS, no scratch.)
+__global__ __launch_bounds__(256) void k_bam_extract_long(BamScan S, const LongRec *__restrict__ longs, u32 n, RecStore R) {
+    const u32 lane = threadIdx.x & 63u;
+    const u32 i = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (threadIdx.x >> 6)));
+    if (i >= n) return;
+    const LongRec e = longs[i];
+    const uint8_t *r = S.u + e.off;
+    const u32 bs = ld32(r), l_read_name = r[12], n_cig = ld16(r + 16), l_seq = ld32(r + 20);
+    const u64 end = e.off + 4 + bs, aux = e.off + 4 + bamrec::fixed_bytes(l_read_name, n_cig, l_seq);
+    u64 c = e.off + 36 + l_read_name;
+    if (n_cig == 2u) { u32 cnt = 0; const u64 cg = bamrec::cg_cigar(WaveNul{}, S.u, e.off, end, cnt); if (cg != bamrec::NONE && cnt == e.words) c = cg; }
+    if (c + 4ull * e.words <= end)
+        for (u32 x = lane; x < e.words; x += 64u) R.cigar[e.ci + x] = ld32(S.u + c + 4ull * x);
+    u32 nm = 0;
+    const u32 kind = bamrec::scan_nm(WaveNul{}, S.u, aux, end, nm);
+    if (lane == 0) { R.nm[e.ri] = nm; R.nm_kind[e.ri] = (uint8_t)kind; }
 }
 
 }  // namespace covi

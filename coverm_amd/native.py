@@ -65,7 +65,7 @@ EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "co
            "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths",
            "cov_set_genomes", "cov_finish_genomes", "cov_fetch_genome_estimates", "cov_fetch_genome_stats",
            "cov_set_genome_runs", "cov_genome_entry_count", "cov_fetch_genome_entries",
-           "cov_sam_begin", "cov_sam_window_bytes", "cov_sam_slot_wait", "cov_sam_feed", "cov_sam_end"]
+           "cov_sam_begin", "cov_sam_window_bytes", "cov_sam_slot_wait", "cov_sam_feed", "cov_sam_end", "cov_ingest_last_stats"]
 
 _lib = None
 

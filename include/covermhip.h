@@ -234,6 +234,14 @@ cov_status cov_ingest_slot_wait(cov_session *s, int slot);
 cov_status cov_ingest_feed(cov_session *s, int slot, const void *host_bytes, uint64_t file_offset, uint64_t n_bytes,
                            const cov_bgzf_block *blocks, uint32_t n_blocks);
 cov_status cov_ingest_end(cov_session *s, uint64_t *n_records);
+/* What the last cov_ingest_end's ingest did (also when it handed the file back): how well the record search cut the stream in pieces. */
+typedef struct {
+    uint64_t windows, segments, segments_with_start, records,
+             max_hop_records,   /* most records any one lane hopped over in k_bam_hop, over all windows */
+             long_records,      /* records that went through k_bam_extract_long */
+             repaired_starts;   /* starts dropped by the repair */
+} cov_ingest_stats;
+cov_status cov_ingest_last_stats(const cov_session *s, cov_ingest_stats *out);  /* of the last cov_ingest_end */
 /* Gives up an ingest that was begun but cannot be ended (a malformed block header met by the driver, a read error): waits for
  * everything queued on the device, appends nothing, leaves the session ready for cov_push_batch.  cov_reset and cov_push_batch
  * call it themselves when an ingest is still open. */
