@@ -33,6 +33,7 @@
 #include "record_store.h"
 #include "store_plan_core.h"
 #include "finish_plan_core.h"
+#include "ingest_plan_core.h"
 
 using namespace covk;
 
@@ -82,6 +83,159 @@ extern "C" int covh_timing_on(void) { return cov_timing_on() ? 1 : 0; }
 //   version 1 (COVERM_INFLATE_V=1): k_inflate, one LANE per block, private Huffman tables per lane in LDS — the second implementation the
 //                        tests compare with; a launch is cut to exactly the blocks resident at once (a lane decodes a block serially).
 struct InflateKernel { int version = 3; int lz_version = 2; u32 round_blocks = 0; u64 carry = 16ull << 20; u64 cwin = 0; u32 ext_parts = covi::EXT_PARTS; };
+
+// Everything the device ingest keeps between its calls.  The rings' depths, the result words and the feed's arithmetic: ingest_plan_core.h.
+struct IngestState {
+    // ---- shared with the SAM text ingest (cov_sam_*)
+    bool active = false;
+    uint32_t batch = 0;                                // rounds (= windows) launched so far
+    uint32_t extracted = 0;                            // windows whose records are in the store (or skipped after a failure)
+    uint64_t rec_total = 0, cig_total = 0;             // records / CIGAR words extracted so far (not committed before cov_ingest_end)
+    uint32_t fail = 0;                                 // sticky ingplan::Status bits: the first window's status that was not 0
+    uint64_t rec_spilled = 0;                          // records of the running ingest that already left the bounded store
+    hipStream_t copy = nullptr;
+    // (ONE upload stream.  Its H2D copies are 0.595 ms per 32 MiB piece = 56 GB/s with a ~38 us gap between two of them: the link is busy
+    // 91 % of the time the file streams, profiles/r06_ingest_copy_trace.json.  A second stream — the halves of a piece on two DMA engines in
+    // round 3, whole pieces in turn in round 6 — is SLOWER both ways: 0.82 s of ingest against 0.50 s at 200 M reads,
+    // profiles/r06_copy_streams_ab_200M.json, profiles/r03_copy_queues_50M.log.)
+    hipEvent_t ev[COV_INGEST_SLOTS] = {};              // a slot's last upload
+    u64 *h_winres = nullptr;                           // page-locked: PARSE_RING x WIN_RESULT_WORDS words, the windows' result blocks
+    std::future<hipError_t> prep;      // COV_WANT_INGEST: create() running on a helper thread since cov_create (ingest_prep_wait)
+
+    // ---- the BGZF ingest: compressed file and inflated stream in HBM, BGZF block table, record-boundary scratch
+    bool was_span = false;           // records of a cov_ingest_span rank are in the store: cov_group_records refuses (cleared by cov_reset alone)
+    DevBuf<uint8_t> g_scratch, g_carry;
+    DevBuf<u32> g_crc_tab;             // k_crc32_wave's tables (crcw::build_tables), uploaded by create() or the next cov_ingest_begin
+    DevBuf<uint8_t> g_cwin[ingplan::CWIN_RING];            // compressed bytes, one buffer per round in flight (file offsets biased by the round's origin)
+    DevBuf<uint8_t> g_win[ingplan::WIN_RING];              // inflated windows (one k_inflate round each): [carry area | blocks]
+    DevBuf<covi::BgzfBlock> g_blocks;
+    DevBuf<u32> g_status;
+    DevBuf<covi::SegInfo> g_seg[ingplan::PARSE_RING];      // per-window parse state
+    DevBuf<u64> g_recbase[ingplan::PARSE_RING], g_cigbase[ingplan::PARSE_RING];
+    DevBuf<u64> g_result;                                  // ingplan::G_WORDS words (GlobalWord, WinWord)
+    DevBuf<covi::LongRec> g_long;                          // the long records of the window being extracted (k_bam_extract -> k_bam_extract_long, one stream)
+    DevBuf<covi::tokpos_t> g_tok[ingplan::TOK_RING];
+    DevBuf<u32> g_ntok[ingplan::TOK_RING];
+    hipStream_t aux = nullptr;                             // k_lz_resolve / k_crc32 of round i run beside k_inflate of round i + 1
+    hipStream_t parse = nullptr;                           // record boundaries of window i run beside both
+    hipStream_t ext = nullptr;       // extraction of verified windows: the parse stream (a stream of its own made no difference, profiles/r03_tail_variants.log)
+    hipEvent_t inf_done[ingplan::TOK_RING] = {}, lz_done[ingplan::TOK_RING] = {};
+    hipEvent_t ver_done[ingplan::PARSE_RING] = {}, ext_done[ingplan::WIN_RING] = {}, cdone[ingplan::CWIN_RING] = {};
+    hipEvent_t fed = nullptr;                              // everything fed so far is on the device
+    ingplan::FeedState feed;                               // the open round, the blocks and bytes so far (ingplan::feed_plan advances it)
+    uint64_t ccap = 0;                                     // compressed bytes a round may span
+    int64_t copy_cleared = -1;                             // highest round whose compressed buffer the copy stream may already write
+    long long key_lo = 0, key_hi = ingplan::KEY_END;       // cov_ingest_span: records outside [key_lo, key_hi) are not taken
+    bool search_first = false, open_end = false;
+    uint64_t span_lo = 0, span_hi = 0;                     // file bytes the span covers (store size estimate)
+    uint64_t tail_key = ~0ull;                             // key of the record cut by the end of the last window (~0: none)
+    struct WinInfo { u64 N = 0; u32 n_seg = 0; u64 comp_end = 0; };
+    WinInfo win[ingplan::PARSE_RING];
+    int check_crc = 1;
+    uint64_t fail_dbg[3] = {0, 0, 0};                      // W_BAD_SEG, W_BAD_START, W_BAD_LANDED of the window that failed
+    uint64_t first_record = 0;
+    uint64_t launched = 0;           // blocks already handed to k_inflate
+    covi::BgzfBlock *h_blocks = nullptr; size_t h_blocks_cap = 0;   // page-locked mirror of the block table (async uploads read from it)
+    std::vector<ingplan::Step> steps;                      // of the piece being fed
+    uint64_t comp = 0;
+    InflateKernel K;
+    cov_ingest_stats stats{}, stats_last{};                // of the running ingest / of the last cov_ingest_end
+    double s_alloc = 0;              // host seconds inside device allocations of the ingest
+    double s_part[4] = {0, 0, 0, 0};         // ... inside ingest_drain / launch_round / the upload calls / event waits (COVERM_CLI_TIMING)
+
+    bool is_span() const { return ingplan::is_span(key_lo, key_hi, search_first, open_end); }
+
+    // The part of cov_ingest_begin that does not depend on the file: three streams (a hardware queue with its 173 MB save area each), two dozen
+    // events, the page-locked result words and block-table mirror, k_crc32_wave's tables — ~50 ms that used to pass between cov_ingest_begin and
+    // the first piece's upload (tools/r06/call39.sh: "first upload after 0.053 s").  With COV_WANT_INGEST cov_create starts it on a helper thread
+    // as soon as the runtime is up, beside its own stream and whatever the caller does next (targets, estimators, the file's header).
+    hipError_t create(int device) {
+        hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess || copy) return e;
+#define PREP(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
+        auto events = [](hipEvent_t *v, u32 n) { hipError_t e = hipSuccess; for (u32 k = 0; k < n && e == hipSuccess; k++) e = hipEventCreateWithFlags(&v[k], hipEventDisableTiming); return e; };
+        PREP(hipStreamCreateWithFlags(&copy, hipStreamNonBlocking));
+        PREP(events(ev, COV_INGEST_SLOTS));
+        PREP(events(&fed, 1));
+        PREP(hipStreamCreateWithFlags(&aux, hipStreamNonBlocking));
+        // (the boundary search on the LZ / CRC stream — the runtime's four hardware queues put the two on one queue anyway — was measured:
+        // ingest 0.650 s against 0.612 s, the extraction of window w then also waits behind the LZ of w + 1, and the exit is no shorter:
+        // profiles/r04_e2e_200M_runs_*.log)
+        PREP(hipStreamCreateWithFlags(&parse, hipStreamNonBlocking));
+        ext = parse;
+        for (u32 k = 0; k < ingplan::TOK_RING; k++) { PREP(events(&inf_done[k], 1)); PREP(events(&lz_done[k], 1)); }
+        PREP(events(ver_done, ingplan::PARSE_RING));
+        for (u32 k = 0; k < ingplan::WIN_RING; k++) { PREP(events(&ext_done[k], 1)); PREP(events(&cdone[k], 1)); }
+        PREP(hipHostMalloc((void **)&h_winres, ingplan::PARSE_RING * ingplan::WIN_RESULT_WORDS * sizeof(u64), hipHostMallocDefault));
+        {   // page-locked mirror of the block table: room for a 25 GB file of ordinary ~20 KB blocks (cov_ingest_begin replaces it for a larger one)
+            const size_t nc = (size_t)3 << 19;
+            PREP(hipHostMalloc((void **)&h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
+            h_blocks_cap = nc;
+        }
+        {
+            static const std::vector<u32> crc_tables = [] { std::vector<u32> t(covi::crcw::TABLE_WORDS); covi::crcw::build_tables(t.data()); return t; }();
+            PREP(g_crc_tab.reserve(covi::crcw::TABLE_WORDS, copy));
+            PREP(hipMemcpyAsync(g_crc_tab.p, crc_tables.data(), covi::crcw::TABLE_WORDS * sizeof(u32), hipMemcpyHostToDevice, copy));
+            PREP(hipStreamSynchronize(copy));
+        }
+#undef PREP
+        return hipSuccess;
+    }
+    static_assert(ingplan::WIN_RING == ingplan::CWIN_RING, "create and destroy walk ext_done and cdone in one loop");
+
+    // The buffers whose size follows the file (cov_ingest_release gives them back between two files; g_result and g_long stay to the end).
+    void free_buffers() {
+        g_scratch.release(); g_carry.release(); g_blocks.release(); g_status.release();
+        g_crc_tab.release();
+        for (auto &b : g_win) b.release();
+        for (auto &b : g_cwin) b.release();
+        for (u32 k = 0; k < ingplan::PARSE_RING; k++) { g_seg[k].release(); g_recbase[k].release(); g_cigbase[k].release(); }
+        for (u32 k = 0; k < ingplan::TOK_RING; k++) { g_tok[k].release(); g_ntok[k].release(); }
+    }
+
+    // What create made and what the files left (cov_destroy, behind the `side` stream: that may be `aux`, borrowed).
+    void destroy() {
+        for (hipStream_t st : {aux, parse, ext}) if (st) (void)hipStreamSynchronize(st);
+        free_buffers();
+        g_result.release(); g_long.release();
+        if (aux) (void)hipStreamDestroy(aux);
+        if (parse) (void)hipStreamDestroy(parse);
+        for (u32 k = 0; k < ingplan::TOK_RING; k++) { if (inf_done[k]) (void)hipEventDestroy(inf_done[k]); if (lz_done[k]) (void)hipEventDestroy(lz_done[k]); }
+        for (hipEvent_t e : ver_done) if (e) (void)hipEventDestroy(e);
+        for (u32 k = 0; k < ingplan::WIN_RING; k++) { if (ext_done[k]) (void)hipEventDestroy(ext_done[k]); if (cdone[k]) (void)hipEventDestroy(cdone[k]); }
+        if (h_winres) (void)hipHostFree(h_winres);
+        h_winres = nullptr;
+        if (h_blocks) (void)hipHostFree(h_blocks);
+        h_blocks = nullptr;
+        if (copy) { (void)hipStreamSynchronize(copy); (void)hipStreamDestroy(copy); }
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (fed) (void)hipEventDestroy(fed);
+    }
+
+    // The one list of what a new file, or the end of an abandoned one, puts back.
+    enum class Reset { BGZF_FILE, SAM_FILE, ABORT };
+    void reset_for_file(Reset why) {
+        // all three: nothing extracted and uncommitted, no failure, no open round
+        rec_total = cig_total = 0; fail = 0; feed.round_n = 0;
+        if (why == Reset::ABORT) {
+            // The abort keeps `batch` and declares every launched window extracted: the drains of a later call find nothing to do, and
+            // cov_ingest_copy_inflated still answers for a file of one window.  rec_spilled stays too: cov_ingest_abort reports it first.
+            extracted = batch;
+            return;
+        }
+        batch = 0; extracted = 0; rec_spilled = 0;
+        // The text ingest has no rounds, spans or window statistics and never reads the fields below: they keep what the last BGZF file left
+        // (cov_ingest_last_stats goes on answering for it).
+        if (why == Reset::SAM_FILE) return;
+        feed = ingplan::FeedState{}; launched = 0; copy_cleared = -1;
+        key_lo = 0; key_hi = ingplan::KEY_END; search_first = false; open_end = false;
+        span_lo = 0; tail_key = ~0ull;
+        s_alloc = 0; for (double &x : s_part) x = 0;
+        stats = cov_ingest_stats{};
+        // (not here: was_span describes the store's content, not the file; fail_dbg and win[] are written before they are read; the file's
+        // own figures — comp, span_hi, ccap, first_record, check_crc, K — are cov_ingest_begin's arguments)
+    }
+};
 
 struct cov_session {
     cov_config cfg{};
@@ -145,7 +299,6 @@ struct cov_session {
     RecordStore store;               // record store (owned, record_store.h) or adopted device batch
     bool want_mates = false;         // cov_ingest_want_mates: the ingest keeps the mate columns, for cov_pair_filter_apply
     bool want_grouping = false;      // cov_ingest_want_grouping: cov_group_records will follow, so decreasing keys are no reason to hand a file back
-    bool ing_was_span = false;       // records of a cov_ingest_span rank are in the store: cov_group_records refuses
     float grp_ms[4] = {};            // the last cov_group_records: whole call on the stream, order check, sort passes, gather
     uint32_t grp_launches = 0;
     bool adopted = false;
@@ -174,7 +327,6 @@ struct cov_session {
     std::vector<uint64_t> merged_hist;      // histogram of the last cov_finish when it merged spilled contigs (cov_fetch_hist serves it)
     bool merged_valid = false;
     uint64_t merged_records = 0;            // records of the whole sample after a merging finish (cov_gather sends it)
-    uint64_t ing_rec_spilled = 0;           // records of the running ingest that already left the store
     uint64_t spill_retry_at = 0;            // after a spill that could move nothing: no further attempt below this many records
 
     DevBuf<uint2> d_runs;
@@ -192,62 +344,10 @@ struct cov_session {
     u64 *h_chist = nullptr; u64 h_chist_cap = 0, hist_prefetched = 0, last_chist_total = 0; bool hist_compacted = false, hist_fetch_seen = false;
     DevBuf<int32_t> d_depth;
 
-    // device ingest (cov_ingest_*): compressed file and inflated stream in HBM, BGZF block table, record-boundary scratch
-    DevBuf<uint8_t> g_scratch, g_carry;
-    DevBuf<u32> g_crc_tab;             // k_crc32_wave's tables (crcw::build_tables), uploaded by the session's first cov_ingest_begin
-    DevBuf<uint8_t> g_cwin[3];                             // compressed bytes, one buffer per round in flight (file offsets biased by the round's origin)
-    DevBuf<uint8_t> g_win[3];                              // inflated windows (one k_inflate round each): [carry area | blocks]
-    DevBuf<covi::BgzfBlock> g_blocks;
-    DevBuf<u32> g_status;
-    DevBuf<covi::SegInfo> g_seg[4];                        // per-window parse state: extract of window w runs up to three windows later
-    DevBuf<u64> g_recbase[4], g_cigbase[4];
-    // g_result: [3] inflate failures (u32) | extract failures (u32), [5] bytes in g_carry, [6] p0 of the window being parsed,
-    // [7] key of the last record of the previous window (bit 63: there is one),
-    // [4] entries in g_long (u32, zeroed in front of every k_bam_extract),
-    // [8 + WIN_RESULT_WORDS * (w % 4) ..] result block of window w (k_bam_verify)
-    DevBuf<u64> g_result;
-    DevBuf<covi::LongRec> g_long;                          // the long records of the window being extracted (k_bam_extract -> k_bam_extract_long, one stream)
-    cov_ingest_stats ing_stats{}, ing_stats_last{};        // of the running ingest / of the last cov_ingest_end
-    DevBuf<covi::tokpos_t> g_tok, g_tok2;
-    DevBuf<u32> g_ntok, g_ntok2;
-    hipStream_t ing_aux = nullptr;                         // k_lz_resolve / k_crc32 of round i run beside k_inflate of round i + 1
-    hipStream_t ing_parse = nullptr;                       // record boundaries of window i run beside both
-    hipStream_t ing_ext = nullptr;   // extraction of verified windows: the parse stream (a stream of its own made no difference, profiles/r03_tail_variants.log)
-    hipEvent_t ing_inf_done[2] = {nullptr, nullptr}, ing_lz_done[2] = {nullptr, nullptr};
-    hipEvent_t ing_ver_done[4] = {}, ing_ext_done[3] = {}, ing_cdone[3] = {};
-    uint64_t ing_round_start = 0, ing_prev_end = 0, ing_ccap = 0;   // accumulating round: file offset its buffer starts at; end of the last payload seen; bytes a round may span
-    uint32_t ing_round_n = 0;                              // blocks of the accumulating round
-    int64_t ing_copy_cleared = -1;                         // highest round whose compressed buffer the copy stream may already write
-    long long ing_key_lo = 0, ing_key_hi = 0x80000000ll;   // cov_ingest_span: records outside [key_lo, key_hi) are not taken
-    bool ing_search_first = false, ing_open_end = false, ing_fed_any = false;
-    uint64_t ing_span_lo = 0, ing_span_hi = 0;             // file bytes the span covers (store size estimate)
-    uint64_t ing_tail_key = ~0ull;                         // key of the record cut by the end of the last window (~0: none)
-    u64 *h_winres = nullptr;                               // page-locked: 4 x WIN_RESULT_WORDS words, the windows' result blocks
-    struct WinInfo { u64 N = 0; u32 n_seg = 0; u64 comp_end = 0; };
-    WinInfo ing_win[4];
-    uint32_t ing_batch = 0; int ing_check_crc = 1;         // ing_batch = rounds (= windows) launched so far
-    uint32_t ing_extracted = 0;                            // windows whose records are in the store (or skipped after a failure)
-    uint64_t ing_rec_total = 0, ing_cig_total = 0;         // records / CIGAR words extracted so far (not committed before cov_ingest_end)
-    uint32_t ing_fail = 0;                                 // sticky status bits of k_bam_verify
-    uint64_t ing_fail_dbg[3] = {0, 0, 0};
-    uint64_t ing_first_record = 0;
-    uint64_t ing_launched = 0;   // blocks already handed to k_inflate
-    covi::BgzfBlock *h_blocks = nullptr; size_t h_blocks_cap = 0;   // page-locked mirror of the block table (async uploads read from it)
-    uint64_t ing_comp = 0, ing_infl = 0, ing_blocks = 0;
-    bool ing_active = false;
-    InflateKernel ing_K;
-    hipStream_t ing_copy = nullptr;
-    std::future<hipError_t> ing_prep;          // COV_WANT_INGEST: the ingest's streams, events and fixed tables, being created since cov_create (ingest_prep_wait)
-    // (ONE upload stream.  Its H2D copies are 0.595 ms per 32 MiB piece = 56 GB/s with a ~38 us gap between two of them: the link is busy
-    // 91 % of the time the file streams, profiles/r06_ingest_copy_trace.json.  A second stream — the halves of a piece on two DMA engines in
-    // round 3, whole pieces in turn in round 6 — is SLOWER both ways: 0.82 s of ingest against 0.50 s at 200 M reads,
-    // profiles/r06_copy_streams_ab_200M.json, profiles/r03_copy_queues_50M.log.)
-    hipEvent_t ing_ev[COV_INGEST_SLOTS] = {}, ing_fed = nullptr;
-    double ing_s_alloc = 0;     // host seconds inside device allocations of the ingest
-    double ing_s_part[4] = {0, 0, 0, 0};     // ... inside ingest_drain / launch_round / the upload calls / event waits (COVERM_CLI_TIMING)
+    IngestState ing;                 // device ingest (cov_ingest_*), and what the SAM text ingest shares with it
 
-    // SAM text ingest (cov_sam_*): an ingest like the BGZF one as far as the session's state goes (ing_active, ing_rec_total, the slots' events,
-    // the upload stream, cov_ingest_abort), with sam_active on top.  Two text buffers of one window each take the uploads in turn; masks and
+    // SAM text ingest (cov_sam_*): an ingest like the BGZF one as far as the session's state goes (ing.active, ing.rec_total, the slots' events,
+    // the upload stream, cov_ingest_abort: the head of IngestState), with sam_active on top.  Two text buffers of one window each take the uploads in turn; masks and
     // line arrays exist once (the windows' kernels run in order on the session stream).
     bool sam_active = false, sam_seen_record = false, sam_decode_timed = false;
     uint64_t sam_window = 0, sam_expected = 0, sam_lines = 0, sam_bytes = 0, sam_err_line = 0;
@@ -532,43 +632,9 @@ int cov_abi_version(void) { return COVERMHIP_ABI_VERSION; }
 
 const char *cov_last_error(const cov_session *s) { return s ? s->err.c_str() : g_create_error.c_str(); }
 
-// The part of cov_ingest_begin that does not depend on the file: three streams (a hardware queue with its 173 MB save area each), two dozen
-// events, the page-locked result words and block-table mirror, k_crc32_wave's tables — ~50 ms that used to pass between cov_ingest_begin and
-// the first piece's upload (tools/r06/call39.sh: "first upload after 0.053 s").  With COV_WANT_INGEST cov_create starts it on a helper thread
-// as soon as the runtime is up, beside its own stream and whatever the caller does next (targets, estimators, the file's header).
-static hipError_t ingest_prepare_(cov_session *s) {
-    hipError_t e = hipSetDevice(s->cfg.device);
-    if (e != hipSuccess || s->ing_copy) return e;
-#define PREP(x) do { e = (x); if (e != hipSuccess) return e; } while (0)
-    PREP(hipStreamCreateWithFlags(&s->ing_copy, hipStreamNonBlocking));
-    for (int k = 0; k < COV_INGEST_SLOTS; k++) PREP(hipEventCreateWithFlags(&s->ing_ev[k], hipEventDisableTiming));
-    PREP(hipEventCreateWithFlags(&s->ing_fed, hipEventDisableTiming));
-    PREP(hipStreamCreateWithFlags(&s->ing_aux, hipStreamNonBlocking));
-    // (the boundary search on the LZ / CRC stream — the runtime's four hardware queues put the two on one queue anyway — was measured:
-    // ingest 0.650 s against 0.612 s, the extraction of window w then also waits behind the LZ of w + 1, and the exit is no shorter:
-    // profiles/r04_e2e_200M_runs_*.log)
-    PREP(hipStreamCreateWithFlags(&s->ing_parse, hipStreamNonBlocking));
-    s->ing_ext = s->ing_parse;
-    for (int k = 0; k < 2; k++) { PREP(hipEventCreateWithFlags(&s->ing_inf_done[k], hipEventDisableTiming)); PREP(hipEventCreateWithFlags(&s->ing_lz_done[k], hipEventDisableTiming)); }
-    for (int k = 0; k < 4; k++) PREP(hipEventCreateWithFlags(&s->ing_ver_done[k], hipEventDisableTiming));
-    for (int k = 0; k < 3; k++) { PREP(hipEventCreateWithFlags(&s->ing_ext_done[k], hipEventDisableTiming)); PREP(hipEventCreateWithFlags(&s->ing_cdone[k], hipEventDisableTiming)); }
-    PREP(hipHostMalloc((void **)&s->h_winres, 4 * covi::WIN_RESULT_WORDS * sizeof(u64), hipHostMallocDefault));
-    {   // page-locked mirror of the block table: room for a 25 GB file of ordinary ~20 KB blocks (cov_ingest_begin replaces it for a larger one)
-        const size_t nc = (size_t)3 << 19;
-        PREP(hipHostMalloc((void **)&s->h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
-        s->h_blocks_cap = nc;
-    }
-    {
-        static const std::vector<u32> crc_tables = [] { std::vector<u32> t(covi::crcw::TABLE_WORDS); covi::crcw::build_tables(t.data()); return t; }();
-        PREP(s->g_crc_tab.reserve(covi::crcw::TABLE_WORDS, s->ing_copy));
-        PREP(hipMemcpyAsync(s->g_crc_tab.p, crc_tables.data(), covi::crcw::TABLE_WORDS * sizeof(u32), hipMemcpyHostToDevice, s->ing_copy));
-        PREP(hipStreamSynchronize(s->ing_copy));
-    }
-#undef PREP
-    return hipSuccess;
-}
+static hipError_t ingest_prepare_(cov_session *s) { return s->ing.create(s->cfg.device); }
 // Everything that looks at the ingest's streams outside cov_ingest_begin waits for the helper first.
-static hipError_t ingest_prep_wait(cov_session *s) { return s->ing_prep.valid() ? s->ing_prep.get() : hipSuccess; }
+static hipError_t ingest_prep_wait(cov_session *s) { return s->ing.prep.valid() ? s->ing.prep.get() : hipSuccess; }
 
 cov_status cov_create(const cov_config *cfg, cov_session **out) {
     if (!cfg || !out) { g_create_error = "null argument"; return COV_ERR_INVALID_ARG; }
@@ -598,7 +664,7 @@ cov_status cov_create(const cov_config *cfg, cov_session **out) {
         if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cfg->device) == hipSuccess && cus > 0) s->n_cus = cus;
         stamp("device attribute");
     }
-    if (cfg->want & COV_WANT_INGEST) s->ing_prep = std::async(std::launch::async, [s] { return ingest_prepare_(s); });
+    if (cfg->want & COV_WANT_INGEST) s->ing.prep = std::async(std::launch::async, [s] { return ingest_prepare_(s); });
     if (const char *el = getenv("COVERM_EST_LANES")) s->est_lanes = atoi(el) ? 1 : 0;
     if (const char *ft = getenv("COVERM_FAST_TABLES")) s->fast_tables = atoi(ft) == 2 ? 2 : 1;
     if (const char *pk = getenv("COVERM_PREP_KERNEL")) s->prep_kernel = atoi(pk) == 7 ? 7 : 0;
@@ -621,11 +687,7 @@ cov_status cov_create(const cov_config *cfg, cov_session **out) {
 }
 
 static void ingest_free_buffers(cov_session *s) {
-    s->g_scratch.release(); s->g_carry.release(); s->g_blocks.release(); s->g_status.release();
-    s->g_crc_tab.release();
-    for (int k = 0; k < 3; k++) { s->g_win[k].release(); s->g_cwin[k].release(); }
-    for (int k = 0; k < 4; k++) { s->g_seg[k].release(); s->g_recbase[k].release(); s->g_cigbase[k].release(); }
-    s->g_tok.release(); s->g_ntok.release(); s->g_tok2.release(); s->g_ntok2.release();
+    s->ing.free_buffers();
     for (auto &b : s->m_text) b.release();      // (the SAM text ingest's window: text, masks, line arrays)
     s->m_nl.release(); s->m_tab.release(); s->m_line_end.release(); s->m_cnt.release(); s->m_rec_idx.release(); s->m_cig_idx.release();
 }
@@ -643,33 +705,17 @@ void cov_destroy(cov_session *s) {
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
     s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
     s->d_cx_list.release(); s->d_cx_cnt.release(); s->d_cx_cur.release(); s->d_cx_scan.release(); s->d_cx_top.release(); s->d_cx_runs.release();
-    if (s->side) {     // before ing_aux goes: `side` may be that very stream (stage_identity_side borrows the idle ingest stream)
+    if (s->side) {     // before ing.aux goes: `side` may be that very stream (stage_identity_side borrows the idle ingest stream)
         (void)hipStreamSynchronize(s->side);
         if (s->side_owned) (void)hipStreamDestroy(s->side);
         s->side = nullptr; s->side_owned = false;
     }
-    if (s->ing_aux) (void)hipStreamSynchronize(s->ing_aux);
-    if (s->ing_parse) (void)hipStreamSynchronize(s->ing_parse);
-    if (s->ing_ext) (void)hipStreamSynchronize(s->ing_ext);
-    ingest_free_buffers(s);
-    s->g_result.release(); s->g_long.release();
-    if (s->ing_aux) (void)hipStreamDestroy(s->ing_aux);
-    if (s->ing_parse) (void)hipStreamDestroy(s->ing_parse);
-    for (int k = 0; k < 2; k++) { if (s->ing_inf_done[k]) (void)hipEventDestroy(s->ing_inf_done[k]); if (s->ing_lz_done[k]) (void)hipEventDestroy(s->ing_lz_done[k]); }
-    for (int k = 0; k < 4; k++) if (s->ing_ver_done[k]) (void)hipEventDestroy(s->ing_ver_done[k]);
-    for (int k = 0; k < 3; k++) { if (s->ing_ext_done[k]) (void)hipEventDestroy(s->ing_ext_done[k]); if (s->ing_cdone[k]) (void)hipEventDestroy(s->ing_cdone[k]); }
-    if (s->h_winres) (void)hipHostFree(s->h_winres);
-    s->h_winres = nullptr;
-    if (s->h_blocks) (void)hipHostFree(s->h_blocks);
-    s->h_blocks = nullptr;
-    if (s->ing_copy) { (void)hipStreamSynchronize(s->ing_copy); (void)hipStreamDestroy(s->ing_copy); }
-    for (int k = 0; k < COV_INGEST_SLOTS; k++) if (s->ing_ev[k]) (void)hipEventDestroy(s->ing_ev[k]);
+    s->ing.destroy();
     for (hipEvent_t e : s->sam_buf_free) if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->sam_ev) if (e) (void)hipEventDestroy(e);
     for (auto &b : s->m_text) b.release();
     s->m_blob.release(); s->m_nl.release(); s->m_tab.release(); s->m_res.release(); s->m_noff.release(); s->m_line_end.release(); s->m_cnt.release();
     s->m_rec_idx.release(); s->m_cig_idx.release(); s->m_slots.release(); for (auto &b : s->m_bsum) b.release();
-    if (s->ing_fed) (void)hipEventDestroy(s->ing_fed);
     s->d_res.release(); s->d_ctg.p = nullptr; s->d_glob.p = nullptr; s->d_desc.release(); s->d_gather.release();
     if (s->h_gather) (void)hipHostFree(s->h_gather);
     s->h_gather = nullptr;
@@ -861,7 +907,7 @@ cov_status cov_set_genome_runs(cov_session *s, const int32_t *gid_of_tid, uint32
 cov_status cov_push_batch(cov_session *s, const cov_batch *b) {
     if (!s || !b) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
-    if (s->ing_active) { const cov_status a = cov_ingest_abort(s); if (a != COV_OK) return a; }   // an ingest left open: its queued work may still write the store
+    if (s->ing.active) { const cov_status a = cov_ingest_abort(s); if (a != COV_OK) return a; }   // an ingest left open: its queued work may still write the store
     { const cov_status st = materialise_adopted(s); if (st) return st; }
     return append(s, b, false);
 }
@@ -891,15 +937,14 @@ cov_status cov_push_batch_device(cov_session *s, const cov_batch *b) {
 // store holds what it held before (extraction only ever writes behind n_records) and may be pushed to again.
 cov_status cov_ingest_abort(cov_session *s) {
     if (!s) return COV_ERR_INVALID_ARG;
-    if (!s->ing_active) return COV_OK;
+    if (!s->ing.active) return COV_OK;
     HIPCHK(hipSetDevice(s->cfg.device));
-    s->ing_active = false; s->sam_active = false;
-    for (hipStream_t st : {s->ing_copy, s->stream, s->ing_aux, s->ing_parse, s->ing_ext})
+    s->ing.active = false; s->sam_active = false;
+    for (hipStream_t st : {s->ing.copy, s->stream, s->ing.aux, s->ing.parse, s->ing.ext})
         if (st) HIPCHK(hipStreamSynchronize(st));
-    s->ing_rec_total = s->ing_cig_total = 0; s->ing_round_n = 0; s->ing_fail = 0;
-    s->ing_extracted = s->ing_batch;
-    if (s->ing_rec_spilled) {     // the store no longer holds what it held before the ingest: only cov_reset brings the session back
-        s->ing_rec_spilled = 0;
+    s->ing.reset_for_file(IngestState::Reset::ABORT);
+    if (s->ing.rec_spilled) {     // the store no longer holds what it held before the ingest: only cov_reset brings the session back
+        s->ing.rec_spilled = 0;
         s->err = "cov_ingest_abort: part of the file had already left the bounded record store; cov_reset the session";
         return COV_ERR_STATE;
     }
@@ -908,16 +953,16 @@ cov_status cov_ingest_abort(cov_session *s) {
 
 cov_status cov_reset(cov_session *s) {
     if (!s) return COV_ERR_INVALID_ARG;
-    if (s->ing_active) {
+    if (s->ing.active) {
         // an ingest that had already spilled part of its file: the abort drains the device and says "cov_reset the session" (COV_ERR_STATE) —
         // this IS that reset, so the status is expected here and everything below still has to be cleared
-        const bool spilled = s->ing_rec_spilled != 0;
+        const bool spilled = s->ing.rec_spilled != 0;
         const cov_status a = cov_ingest_abort(s);
         if (a != COV_OK && !(spilled && a == COV_ERR_STATE)) return a;
         if (a != COV_OK) s->err.clear();
     }
-    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->store.mates_valid = 0; s->ing_was_span = false;
-    s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing_rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
+    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->store.mates_valid = 0; s->ing.was_span = false;
+    s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing.rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
 
@@ -1182,7 +1227,7 @@ static cov_status stage_identity_side(cov_session *s, const PassViews &v) {
     const u32 R = v.R, nT = v.nT;
     if (!s->side) {
         (void)ingest_prep_wait(s);
-        if (s->ing_aux && !s->ing_active) s->side = s->ing_aux;      // idle since cov_ingest_end
+        if (s->ing.aux && !s->ing.active) s->side = s->ing.aux;      // idle since cov_ingest_end
         else { HIPCHK(hipStreamCreateWithFlags(&s->side, hipStreamNonBlocking)); s->side_owned = true; }
     }
     HIPCHK(hipEventRecord(s->ev_prep_done, v.st));
@@ -1721,7 +1766,6 @@ static InflateKernel choose_inflate_kernel(cov_session *s) {
     { long long v; if (covknob::get("ingest_cwin_kb", v) && v >= 256) K.cwin = (u64)v << 10; }
     return K;
 }
-static inline const InflateKernel &inflate_kernel(cov_session *s) { return s->ing_K; }
 
 cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t first_record_offset, int check_crc) {
     if (!s) return COV_ERR_INVALID_ARG;
@@ -1729,46 +1773,43 @@ cov_status cov_ingest_begin(cov_session *s, uint64_t compressed_bytes, uint64_t 
     covr::Range rr("ingest: buffers, streams, events (cov_ingest_begin)");
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(ingest_prep_wait(s));
-    if (!s->ing_copy) HIPCHK(ingest_prepare_(s));
+    if (!s->ing.copy) HIPCHK(ingest_prepare_(s));
     { const cov_status a = materialise_adopted(s); if (a) return a; }
     HIPCHK(hipStreamSynchronize(s->stream));     // the record store is about to be written from the parse stream
-    s->ing_batch = 0; s->ing_extracted = 0; s->ing_rec_total = s->ing_cig_total = 0; s->ing_fail = 0; s->ing_rec_spilled = 0;
-    s->ing_K = choose_inflate_kernel(s);      // (also sets the kernel's dynamic-LDS limit on this session's device)
-    s->ing_first_record = first_record_offset;
-    s->ing_check_crc = check_crc ? 1 : 0;
-    HIPCHK(s->g_result.reserve(8 + 4 * covi::WIN_RESULT_WORDS, s->stream));
-    HIPCHK(s->g_carry.reserve(inflate_kernel(s).carry, s->stream));
-    if (!s->g_crc_tab.p) {      // (cov_ingest_release between two files gave the tables back with the buffers)
+    IngestState &I = s->ing;
+    I.reset_for_file(IngestState::Reset::BGZF_FILE);
+    I.K = choose_inflate_kernel(s);      // (also sets the kernel's dynamic-LDS limit on this session's device)
+    I.first_record = first_record_offset;
+    I.check_crc = check_crc ? 1 : 0;
+    HIPCHK(I.g_result.reserve(ingplan::G_WORDS, s->stream));
+    HIPCHK(I.g_carry.reserve(I.K.carry, s->stream));
+    if (!I.g_crc_tab.p) {      // (cov_ingest_release between two files gave the tables back with the buffers)
         std::vector<u32> t(covi::crcw::TABLE_WORDS);
         covi::crcw::build_tables(t.data());
-        HIPCHK(s->g_crc_tab.reserve(covi::crcw::TABLE_WORDS, s->stream));
-        HIPCHK(hipMemcpy(s->g_crc_tab.p, t.data(), covi::crcw::TABLE_WORDS * sizeof(u32), hipMemcpyHostToDevice));
+        HIPCHK(I.g_crc_tab.reserve(covi::crcw::TABLE_WORDS, s->stream));
+        HIPCHK(hipMemcpy(I.g_crc_tab.p, t.data(), covi::crcw::TABLE_WORDS * sizeof(u32), hipMemcpyHostToDevice));
     }
-    HIPCHK(s->g_blocks.reserve(compressed_bytes / 8192 + 1024, s->stream));
-    HIPCHK(s->g_status.reserve(compressed_bytes / 8192 + 1024, s->stream));
-    if (compressed_bytes / 16384 + 1024 > s->h_blocks_cap) {     // page-locked mirror of the block table: sized once for ordinary ~20 KB blocks (it grows if they are smaller)
-        if (s->h_blocks) { (void)hipHostFree(s->h_blocks); s->h_blocks = nullptr; s->h_blocks_cap = 0; }
+    HIPCHK(I.g_blocks.reserve(compressed_bytes / 8192 + 1024, s->stream));
+    HIPCHK(I.g_status.reserve(compressed_bytes / 8192 + 1024, s->stream));
+    if (compressed_bytes / 16384 + 1024 > I.h_blocks_cap) {     // page-locked mirror of the block table: sized once for ordinary ~20 KB blocks (it grows if they are smaller)
+        if (I.h_blocks) { (void)hipHostFree(I.h_blocks); I.h_blocks = nullptr; I.h_blocks_cap = 0; }
         const size_t nc = compressed_bytes / 16384 + 1024;
-        HIPCHK(hipHostMalloc((void **)&s->h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
-        s->h_blocks_cap = nc;
+        HIPCHK(hipHostMalloc((void **)&I.h_blocks, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
+        I.h_blocks_cap = nc;
     }
-    HIPCHK(hipMemsetAsync(s->g_result.p, 0, (8 + 4 * covi::WIN_RESULT_WORDS) * sizeof(u64), s->stream));
+    HIPCHK(hipMemsetAsync(I.g_result.p, 0, ingplan::G_WORDS * sizeof(u64), s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
-    s->ing_comp = compressed_bytes; s->ing_infl = 0; s->ing_blocks = 0; s->ing_launched = 0; s->ing_active = true;
-    s->ing_round_start = 0; s->ing_prev_end = 0; s->ing_round_n = 0; s->ing_copy_cleared = -1;
-    s->ing_key_lo = 0; s->ing_key_hi = 0x80000000ll; s->ing_search_first = false; s->ing_open_end = false; s->ing_fed_any = false;
-    s->ing_span_lo = 0; s->ing_span_hi = compressed_bytes; s->ing_tail_key = ~0ull;
-    s->ing_ccap = std::min<u64>(inflate_kernel(s).cwin, compressed_bytes + 65536u + 128u);     // a small file is one buffer: the byte rule never fires
-    s->ing_s_alloc = 0; for (double &x : s->ing_s_part) x = 0;
-    s->ing_stats = cov_ingest_stats{};
+    I.comp = compressed_bytes; I.span_hi = compressed_bytes;
+    I.ccap = std::min<u64>(I.K.cwin, compressed_bytes + 65536u + 128u);     // a small file is one buffer: the byte rule never fires
+    I.active = true;
     return COV_OK;
 }
 
 cov_status cov_ingest_span(cov_session *s, int64_t key_lo, int64_t key_hi, int search_first_record, int open_end, uint64_t file_lo, uint64_t file_hi) {
-    if (!s || !s->ing_active || s->ing_fed_any || key_lo < 0 || key_hi < key_lo || file_hi < file_lo || file_hi > s->ing_comp) return COV_ERR_INVALID_ARG;
-    s->ing_key_lo = key_lo; s->ing_key_hi = key_hi; s->ing_search_first = search_first_record != 0; s->ing_open_end = open_end != 0;
-    s->ing_span_lo = file_lo; s->ing_span_hi = file_hi;
-    if (key_lo > 0 || key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end) s->ing_was_span = true;
+    if (!s || !s->ing.active || s->ing.feed.fed_any || key_lo < 0 || key_hi < key_lo || file_hi < file_lo || file_hi > s->ing.comp) return COV_ERR_INVALID_ARG;
+    s->ing.key_lo = key_lo; s->ing.key_hi = key_hi; s->ing.search_first = search_first_record != 0; s->ing.open_end = open_end != 0;
+    s->ing.span_lo = file_lo; s->ing.span_hi = file_hi;
+    if (s->ing.is_span()) s->ing.was_span = true;
     return COV_OK;
 }
 
@@ -1783,20 +1824,20 @@ struct Admitted { u64 R = 0, Cg = 0; bool past_limit = false, room = false; };
 static cov_status admit_window(cov_session *s, u64 nrec, u64 ncig, hipStream_t wr, double scale, Admitted &a) {
     RecordStore &S = s->store;
     a = Admitted{};
-    u64 R = S.n_records + s->ing_rec_total, Cg = S.n_cigar + s->ing_cig_total;
-    if (nrec && stplan::spill_first(R == 0, s->want_mates, s->ing_fail != 0, R + nrec > s->cap_records, Cg + ncig > s->cap_cigar)) {
+    u64 R = S.n_records + s->ing.rec_total, Cg = S.n_cigar + s->ing.cig_total;
+    if (nrec && stplan::spill_first(R == 0, s->want_mates, s->ing.fail != 0, R + nrec > s->cap_records, Cg + ncig > s->cap_cigar)) {
         if (wr != s->stream) HIPCHK(hipStreamSynchronize(wr));
         HIPCHK(S.seal(R, Cg, s->stream));
-        s->ing_rec_spilled += s->ing_rec_total; s->ing_rec_total = 0; s->ing_cig_total = 0;
+        s->ing.rec_spilled += s->ing.rec_total; s->ing.rec_total = 0; s->ing.cig_total = 0;
         bool progress = false; const cov_status sp = spill_store(s, progress);
         if (sp != COV_OK) return sp;
         R = S.n_records; Cg = S.n_cigar;
     }
-    a.R = R; a.Cg = Cg; a.past_limit = !s->ing_fail && (stplan::past_limit(R, nrec) || stplan::past_limit(Cg, ncig));
-    if (s->ing_fail || a.past_limit || !nrec) return COV_OK;
+    a.R = R; a.Cg = Cg; a.past_limit = !s->ing.fail && (stplan::past_limit(R, nrec) || stplan::past_limit(Cg, ncig));
+    if (s->ing.fail || a.past_limit || !nrec) return COV_OK;
     const u64 Nn = scale > 0 ? stplan::first_window_size(R, nrec, 0, scale, s->cap_records) : R + nrec;
     const u64 Cn = scale > 0 ? stplan::first_window_size(Cg, ncig, 1, scale, s->cap_cigar) : Cg + ncig + 1;
-    PartTimer alloc{s->ing_s_alloc};
+    PartTimer alloc{s->ing.s_alloc};
     HIPCHK(S.reserve(Nn, Cn, wr, R, Cg, s->want_mates));
     a.room = true;
     return COV_OK;
@@ -1804,368 +1845,391 @@ static cov_status admit_window(cov_session *s, u64 nrec, u64 ncig, hipStream_t w
 
 // The end of an ingest: what it extracted becomes the store's content.
 static cov_status ingest_commit(cov_session *s) {
-    if (!s->ing_rec_total) return COV_OK;
+    if (!s->ing.rec_total) return COV_OK;
     RecordStore &S = s->store;
-    const u64 Nn = S.n_records + s->ing_rec_total;
+    const u64 Nn = S.n_records + s->ing.rec_total;
     const bool mates_cover = s->want_mates && S.mates_valid == S.n_records;      // the columns cover the whole store as long as every file came through here
-    HIPCHK(S.seal(Nn, S.n_cigar + s->ing_cig_total, s->stream));
+    HIPCHK(S.seal(Nn, S.n_cigar + s->ing.cig_total, s->stream));
     if (mates_cover) S.mates_valid = Nn;
     s->finished = false;
     return COV_OK;
 }
 
-// Records of the windows whose boundaries are verified go into the store: all windows up to `must_upto` (waiting for their
-// k_bam_verify if need be), later ones only if their result is already here.
-static cov_status ingest_drain_(cov_session *s, int64_t must_upto);
-static cov_status ingest_drain(cov_session *s, int64_t must_upto) { PartTimer t{s->ing_s_part[0]}; covr::Range rr("ingest: verify + extract windows"); return ingest_drain_(s, must_upto); }
-static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
-    hipStream_t ps = s->ing_ext;     // the host has seen the window's verification finish: nothing on the device to wait for
-    while (s->ing_extracted < s->ing_batch) {
-        const u32 w = s->ing_extracted, q = w & 3u;
-        if ((int64_t)w > must_upto) { if (hipEventQuery(s->ing_ver_done[q]) != hipSuccess) { (void)hipGetLastError(); break; } }   // not ready is not an error
-        else { PartTimer pt{s->ing_s_part[3]}; HIPCHK(hipEventSynchronize(s->ing_ver_done[q])); }
-        const u64 *res = s->h_winres + covi::WIN_RESULT_WORDS * q;
-        const u64 nrec = res[0], ncig = res[1], nlong = res[8];
-        {
-            cov_ingest_stats &I = s->ing_stats;
-            I.windows++; I.segments += s->ing_win[q].n_seg; I.segments_with_start += res[11]; I.records += nrec;
-            I.max_hop_records = std::max<u64>(I.max_hop_records, res[10]); I.repaired_starts += res[9];
-        }
-        u32 st = (u32)res[2];
-        s->ing_tail_key = res[7];
-        const bool span = s->ing_key_lo > 0 || s->ing_key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end;
-        if (!span && (!s->want_mates || s->want_grouping)) st &= ~64u;       // whole file: cov_finish reports disorder in file order, beside the other per-record errors
-        if (st && !s->ing_fail) { s->ing_fail = st; s->ing_fail_dbg[0] = res[4]; s->ing_fail_dbg[1] = res[5]; s->ing_fail_dbg[2] = res[6]; }
-        // first of several windows (it ends in front of the span's end; not "several launched so far": window 0 may be verified before window 1 is launched)
-        double scale = 0;
-        if (w == 0 && s->ing_win[0].comp_end && s->ing_win[0].comp_end + 65536u < s->ing_span_hi)
-            scale = (double)(s->ing_span_hi - s->ing_span_lo) / (double)std::max<u64>(1, s->ing_win[0].comp_end - std::min<u64>(s->ing_win[0].comp_end, s->ing_span_lo)) * 1.1;
-        Admitted a; { const cov_status ad = admit_window(s, nrec, ncig, ps, scale, a); if (ad != COV_OK) return ad; }
-        if (a.past_limit) s->ing_fail = 16u;
-        if (a.room) {
-            covi::RecStore RS{};
-            s->store.view(RS); RS.rec0 = a.R; RS.cig0 = a.Cg;
-            if (s->want_mates) s->store.view_mates(RS);
-            covi::BamScan S{};
-            S.u = s->g_win[w % 3u].p; S.N = s->ing_win[q].N; S.p0 = s->g_result.p + 6; S.seg_bytes = 32768; S.n_seg = s->ing_win[q].n_seg;
-            S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = 0; S.key_lo = s->ing_key_lo; S.key_hi = s->ing_key_hi; S.search_first = 0;
-            S.walk_cap = s->ing_K.carry;
-            u32 *n_long = reinterpret_cast<u32 *>(s->g_result.p + 4);
-            if (nlong) {      // (sized by the window's own count; the buffer only ever grows)
-                PartTimer alloc{s->ing_s_alloc};
-                HIPCHK(s->g_long.reserve((size_t)nlong, ps));
-                HIPCHK(hipMemsetAsync(n_long, 0, sizeof(u32), ps));
-            }
-            hipLaunchKernelGGL(covi::k_bam_extract, dim3((S.n_seg * s->ing_K.ext_parts + 63) / 64), dim3(64), 0, ps, S, (const covi::SegInfo *)s->g_seg[q].p, (const u64 *)s->g_recbase[q].p,
-                               (const u64 *)s->g_cigbase[q].p, RS, reinterpret_cast<u32 *>(s->g_result.p + 3) + 1, s->ing_K.ext_parts,
-                               s->g_long.p, n_long, (u32)nlong);
-            if (nlong) {
-                hipLaunchKernelGGL(covi::k_bam_extract_long, dim3((u32)((nlong + 3) / 4)), dim3(256), 0, ps, S, (const covi::LongRec *)s->g_long.p, (u32)nlong, RS);
-                s->ing_stats.long_records += nlong;
-            }
-            HIPCHK(hipGetLastError());
-            s->ing_rec_total += nrec; s->ing_cig_total += ncig;
-        }
-        HIPCHK(hipEventRecord(s->ing_ext_done[w % 3u], ps));
-        s->ing_extracted++;
+// What the parse kernels are told about window w: N bytes behind the start of its buffer, carry area included.
+static covi::BamScan window_scan(const cov_session *s, u32 w, u64 N, int final, int search_first) {
+    const IngestState &I = s->ing;
+    covi::BamScan S{};
+    S.u = I.g_win[ingplan::win_slot(w)].p; S.N = N; S.p0 = I.g_result.p + ingplan::G_P0; S.seg_bytes = ingplan::SEG_BYTES; S.n_seg = (u32)((S.N + S.seg_bytes - 1) / S.seg_bytes);
+    S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = final; S.key_lo = I.key_lo; S.key_hi = I.key_hi; S.search_first = search_first;
+    S.walk_cap = I.K.carry;
+    return S;
+}
+
+// ---- the drain: records of the windows whose boundaries are verified go into the store — all windows up to `must_upto` (waiting for
+// their k_bam_verify if need be), later ones only if their result is already here.  Per window: take its result, admit it, extract it.
+struct WindowResult { u64 nrec = 0, ncig = 0, nlong = 0; };
+
+// The result block of verified window w (page-locked; the host has seen ver_done): statistics, the tail's key, the sticky failure.
+static WindowResult take_window_result(cov_session *s, u32 w) {
+    IngestState &I = s->ing;
+    const u32 q = ingplan::parse_slot(w);
+    const u64 *res = I.h_winres + ingplan::WIN_RESULT_WORDS * q;
+    cov_ingest_stats &T = I.stats;
+    T.windows++; T.segments += I.win[q].n_seg; T.segments_with_start += res[ingplan::W_LIVE_SEGS]; T.records += res[ingplan::W_RECORDS];
+    T.max_hop_records = std::max<u64>(T.max_hop_records, res[ingplan::W_MAX_HOP]); T.repaired_starts += res[ingplan::W_REPAIRED];
+    u32 st = (u32)res[ingplan::W_STATUS];
+    I.tail_key = res[ingplan::W_TAIL_KEY];
+    if (!I.is_span() && (!s->want_mates || s->want_grouping)) st &= ~(u32)ingplan::ST_DISORDER;       // whole file: cov_finish reports disorder in file order, beside the other per-record errors
+    if (st && !I.fail) { I.fail = st; I.fail_dbg[0] = res[ingplan::W_BAD_SEG]; I.fail_dbg[1] = res[ingplan::W_BAD_START]; I.fail_dbg[2] = res[ingplan::W_BAD_LANDED]; }
+    WindowResult r; r.nrec = res[ingplan::W_RECORDS]; r.ncig = res[ingplan::W_CIGAR]; r.nlong = res[ingplan::W_LONG];
+    return r;
+}
+
+// The records of admitted window w go into the store from (a.R, a.Cg) on, on the extraction stream.
+static cov_status extract_window(cov_session *s, u32 w, const Admitted &a, const WindowResult &r) {
+    IngestState &I = s->ing;
+    hipStream_t ps = I.ext;
+    const u32 q = ingplan::parse_slot(w);
+    covi::RecStore RS{};
+    s->store.view(RS); RS.rec0 = a.R; RS.cig0 = a.Cg;
+    if (s->want_mates) s->store.view_mates(RS);
+    const covi::BamScan S = window_scan(s, w, I.win[q].N, 0, 0);
+    u32 *n_long = reinterpret_cast<u32 *>(I.g_result.p + ingplan::G_LONG);
+    if (r.nlong) {      // (sized by the window's own count; the buffer only ever grows)
+        PartTimer alloc{I.s_alloc};
+        HIPCHK(I.g_long.reserve((size_t)r.nlong, ps));
+        HIPCHK(hipMemsetAsync(n_long, 0, sizeof(u32), ps));
     }
+    hipLaunchKernelGGL(covi::k_bam_extract, dim3((S.n_seg * I.K.ext_parts + 63) / 64), dim3(64), 0, ps, S, (const covi::SegInfo *)I.g_seg[q].p, (const u64 *)I.g_recbase[q].p,
+                       (const u64 *)I.g_cigbase[q].p, RS, reinterpret_cast<u32 *>(I.g_result.p + ingplan::G_FAILURES) + ingplan::FAIL_EXTRACT, I.K.ext_parts,
+                       I.g_long.p, n_long, (u32)r.nlong);
+    if (r.nlong) {
+        hipLaunchKernelGGL(covi::k_bam_extract_long, dim3((u32)((r.nlong + 3) / 4)), dim3(256), 0, ps, S, (const covi::LongRec *)I.g_long.p, (u32)r.nlong, RS);
+        I.stats.long_records += r.nlong;
+    }
+    HIPCHK(hipGetLastError());
+    I.rec_total += r.nrec; I.cig_total += r.ncig;
     return COV_OK;
 }
 
-// One round = one window: k_inflate over the next `n` blocks fed but not yet launched (main stream), k_lz_resolve + k_crc32
+static cov_status ingest_drain_(cov_session *s, int64_t must_upto) {
+    IngestState &I = s->ing;
+    hipStream_t ps = I.ext;     // the host has seen the window's verification finish: nothing on the device to wait for
+    while (I.extracted < I.batch) {
+        const u32 w = I.extracted, q = ingplan::parse_slot(w);
+        if ((int64_t)w > must_upto) { if (hipEventQuery(I.ver_done[q]) != hipSuccess) { (void)hipGetLastError(); break; } }   // not ready is not an error
+        else { PartTimer pt{I.s_part[3]}; HIPCHK(hipEventSynchronize(I.ver_done[q])); }
+        const WindowResult r = take_window_result(s, w);
+        const double scale = w == 0 ? ingplan::first_window_scale(I.win[0].comp_end, I.span_lo, I.span_hi) : 0;
+        Admitted a; { const cov_status ad = admit_window(s, r.nrec, r.ncig, ps, scale, a); if (ad != COV_OK) return ad; }
+        if (a.past_limit) I.fail = ingplan::ST_PAST_LIMIT;
+        if (a.room) { const cov_status e = extract_window(s, w, a, r); if (e != COV_OK) return e; }
+        HIPCHK(hipEventRecord(I.ext_done[ingplan::win_slot(w)], ps));
+        I.extracted++;
+    }
+    return COV_OK;
+}
+static cov_status ingest_drain(cov_session *s, int64_t must_upto) { PartTimer t{s->ing.s_part[0]}; covr::Range rr("ingest: verify + extract windows"); return ingest_drain_(s, must_upto); }
+
+// ---- one round = one window: k_inflate over the next `n` blocks fed but not yet launched (main stream), k_lz_resolve + k_crc32
 // behind it (aux stream, beside the next round's k_inflate), then the window's record boundaries (parse stream).
 // A lane decodes a whole block serially and every block takes about the same time T, so a launch costs T per started ROUND
 // of resident waves: launches are cut to exactly the number of blocks the device holds at once (a launch of 1.05 rounds
 // costs 2 T — measured: 46 ms per launch of ~51 k blocks against 23.5 ms per round of 49 152).
 // Windows bound the memory: the inflated stream of a 200 M-read BAM is 62 GB, and device allocations cost ~30 ms per GB.
-static cov_status launch_round_(cov_session *s, uint64_t n64, bool final);
-static cov_status launch_round(cov_session *s, uint64_t n64, bool final) { PartTimer t{s->ing_s_part[1]}; covr::Range rr("ingest: inflate round launch"); return launch_round_(s, n64, final); }
-static cov_status launch_round_(cov_session *s, uint64_t n64, bool final) {
-    const uint64_t b0 = s->ing_launched;
-    n64 = std::min<uint64_t>(n64, s->ing_blocks - b0);
-    const InflateKernel &K = inflate_kernel(s);
-    const u32 n = (u32)n64, w = s->ing_batch, q = w & 3u;
-    if (w >= 3) { const cov_status d = ingest_drain(s, (int64_t)w - 3); if (d != COV_OK) return d; }   // this window's buffer and parse state are free again
-    const int bb = (int)(w & 1u);
-    DevBuf<covi::tokpos_t> &tokb = bb ? s->g_tok2 : s->g_tok;
-    DevBuf<u32> &ntokb = bb ? s->g_ntok2 : s->g_ntok;
-    DevBuf<uint8_t> &win = s->g_win[w % 3u];
-    // sized for a full round at once (no regrowth between rounds) — or for the blocks a SMALL file can be expected to have: a 200 MB file does not
-    // need three 4 GB windows and two 2.7 GB token lists, and a process that starts right after another one has given tens of GB back waits
-    // for the driver in its large allocations (0.06 s for these in a 2 M-read run, tools/r06/call43.sh).  The estimate is one block per
-    // 4 KiB of compressed bytes; a file of smaller blocks takes the regrowth path below.
-    const size_t est_blocks = (size_t)((s->ing_span_hi - std::min(s->ing_span_lo, s->ing_span_hi)) / 4096u + 256u);
-    const size_t full = std::max<size_t>(n, std::min<size_t>(K.round_blocks, est_blocks));
-    const size_t win_bytes = (size_t)K.carry + full * 65536u + 64u;
-    const u32 seg_cap = (u32)((win_bytes + 32767u) / 32768u);
-    {
-        // A buffer that has to GROW may still be in use: drain the device first.  First-time allocations need no such thing —
-        // and must not wait, or the first four windows (three window buffers, four parse-state sets) would run one after the other.
-        const size_t scr = (full + 63) / 64 * 64u * covi::INF_SCRATCH_BYTES;
-        auto grows = [](size_t need, size_t cap) { return cap != 0 && need > cap; };
-        if (grows(full * covi::INF_TOK_CAP, tokb.cap) || grows(full, ntokb.cap) || grows(scr, s->g_scratch.cap) || grows(win_bytes, win.cap) ||
-            grows(seg_cap, s->g_seg[q].cap)) {
-            HIPCHK(hipStreamSynchronize(s->ing_aux)); HIPCHK(hipStreamSynchronize(s->ing_parse)); HIPCHK(hipStreamSynchronize(s->ing_ext)); HIPCHK(hipStreamSynchronize(s->stream));
-        }
-        const auto ta0 = std::chrono::steady_clock::now();
-        HIPCHK(s->g_scratch.reserve(scr, s->stream));
-        HIPCHK(tokb.reserve(full * covi::INF_TOK_CAP, s->stream));
-        HIPCHK(ntokb.reserve(full, s->stream));
-        HIPCHK(win.reserve(win_bytes, s->stream));
-        HIPCHK(s->g_seg[q].reserve(seg_cap, s->stream)); HIPCHK(s->g_recbase[q].reserve(seg_cap, s->stream)); HIPCHK(s->g_cigbase[q].reserve(seg_cap, s->stream));
-        s->ing_s_alloc += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta0).count();
-    }
-    const u64 out_off0 = n ? s->h_blocks[b0].out_off : s->ing_infl;
-    const u64 wbytes = n ? s->h_blocks[b0 + n - 1].out_off + s->h_blocks[b0 + n - 1].isize - out_off0 : 0;
-    uint8_t *out_bias = win.p + K.carry - out_off0;     // blocks carry absolute offsets of the inflated stream
-    if (w == 0 && s->ing_first_record > wbytes && !s->ing_fail) s->ing_fail = 32u;    // the BAM header does not end inside the first window
-    if (n) {
-        HIPCHK(hipStreamWaitEvent(s->stream, s->ing_fed, 0));
-        // token buffers alternate: this k_inflate may not start before the k_lz_resolve that read the same buffer two rounds ago is done;
-        // the window buffer is free once the extraction of the window three rounds ago is done
-        if (w >= 2) HIPCHK(hipStreamWaitEvent(s->stream, s->ing_lz_done[bb], 0));
-        if (w >= 3) HIPCHK(hipStreamWaitEvent(s->stream, s->ing_ext_done[w % 3u], 0));
-        const u32 grid = (n + 63u) / 64u;
-        const uint8_t *comp_bias = s->g_cwin[w % 3u].p - s->ing_round_start;     // blocks carry absolute file offsets
-        if (K.version == 3)
-            hipLaunchKernelGGL(covi::k_inflate_wave, dim3(n), dim3(64), 0, s->stream, comp_bias, (const covi::BgzfBlock *)(s->g_blocks.p + b0), n, out_bias,
-                               tokb.p, ntokb.p, s->g_status.p + b0, reinterpret_cast<u32 *>(s->g_result.p + 3), 0u);
-        else
-            hipLaunchKernelGGL((covi::k_inflate<INF1_LB, INF1_DB, false>), dim3(grid), dim3(64), covi::inflate_smem_bytes(INF1_LB, INF1_DB), s->stream, comp_bias,
-                               (const covi::BgzfBlock *)(s->g_blocks.p + b0), n, out_bias, s->g_scratch.p, tokb.p, ntokb.p,
-                               s->g_status.p + b0, reinterpret_cast<u32 *>(s->g_result.p + 3));
-        HIPCHK(hipEventRecord(s->ing_inf_done[bb], s->stream));
-        HIPCHK(hipEventRecord(s->ing_cdone[w % 3u], s->stream));      // this round's compressed buffer may be overwritten (three rounds on)
-        HIPCHK(hipStreamWaitEvent(s->ing_aux, s->ing_inf_done[bb], 0));
-        if (K.lz_version == 1)
-            hipLaunchKernelGGL(covi::k_lz_resolve, dim3((n + 3u) / 4u), dim3(256), 0, s->ing_aux, (const covi::BgzfBlock *)(s->g_blocks.p + b0), n, out_bias,
-                               (const covi::tokpos_t *)tokb.p, (const u32 *)ntokb.p);
-        else
-            hipLaunchKernelGGL(covi::k_lz_stage, dim3((n + 3u) / 4u), dim3(256), 0, s->ing_aux, (const covi::BgzfBlock *)(s->g_blocks.p + b0), n, out_bias,
-                               (const covi::tokpos_t *)tokb.p, (const u32 *)ntokb.p);
-        // the window's bytes are final once the matches are resolved: the boundary search (parse stream) starts here, beside the
-        // CRC-32 pass, whose verdict is only looked at in cov_ingest_end (the aux stream is in order, so CRC(w) is done before LZ(w + 1)
-        // and with it before anything may overwrite window w)
-        HIPCHK(hipEventRecord(s->ing_lz_done[bb], s->ing_aux));
-        if (s->ing_check_crc) {
-            if (K.version == 3)      // a wave per block, coalesced; resident workgroups stride over the window's blocks
-                hipLaunchKernelGGL(covi::k_crc32_wave, dim3(std::min<u32>((n + 7u) / 8u, (u32)s->n_cus * 4u)), dim3(512), 0, s->ing_aux,
-                                   (const covi::BgzfBlock *)(s->g_blocks.p + b0), n, (const uint8_t *)out_bias, s->g_status.p + b0,
-                                   reinterpret_cast<u32 *>(s->g_result.p + 3), (const u32 *)s->g_crc_tab.p);
-            else                     // the lane-per-block combination keeps the lane-per-block CRC
-                hipLaunchKernelGGL(covi::k_crc32, dim3((n + 255u) / 256u), dim3(256), 0, s->ing_aux, (const covi::BgzfBlock *)(s->g_blocks.p + b0), n,
-                                   (const uint8_t *)out_bias, s->g_status.p + b0, reinterpret_cast<u32 *>(s->g_result.p + 3));
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipStreamWaitEvent(s->ing_parse, s->ing_lz_done[bb], 0));
-    }
-    // ---- the window's records: tail of the previous window in front, boundaries, counts, the new tail
-    covi::BamScan S{};
-    S.u = win.p; S.N = K.carry + wbytes; S.p0 = s->g_result.p + 6; S.seg_bytes = 32768; S.n_seg = (u32)((S.N + S.seg_bytes - 1) / S.seg_bytes);
-    S.n_ref = (int)s->n_targets; S.ref_len = s->d_tlen.p; S.final = (final && !s->ing_open_end) ? 1 : 0;
-    S.key_lo = s->ing_key_lo; S.key_hi = s->ing_key_hi; S.search_first = (w == 0 && s->ing_search_first) ? 1 : 0;
-    S.walk_cap = K.carry;
-    s->ing_win[q].N = S.N; s->ing_win[q].n_seg = S.n_seg; s->ing_win[q].comp_end = n ? s->h_blocks[b0 + n - 1].in_off + s->h_blocks[b0 + n - 1].in_len + 8 : s->ing_comp;
-    hipStream_t ps = s->ing_parse;
-    if (w >= 3) HIPCHK(hipStreamWaitEvent(ps, s->ing_ext_done[w % 3u], 0));     // the carried tail goes in front of a buffer whose records must be out
-    hipLaunchKernelGGL(covi::k_carry_in, dim3(1), dim3(1024), 0, ps, win.p, K.carry, (const uint8_t *)s->g_carry.p, (const u64 *)(s->g_result.p + 5),
-                       w == 0 ? s->ing_first_record : 0ull, s->g_result.p + 6);
-    hipLaunchKernelGGL(covi::k_bam_find, dim3((S.n_seg + 3) / 4), dim3(256), 0, ps, S, s->g_seg[q].p);
-    hipLaunchKernelGGL(covi::k_bam_hop, dim3((S.n_seg + 63) / 64), dim3(64), 0, ps, S, s->g_seg[q].p);
-    hipLaunchKernelGGL(covi::k_bam_verify, dim3(1), dim3(1024), 0, ps, S, s->g_seg[q].p, s->g_recbase[q].p, s->g_cigbase[q].p, s->g_result.p + 8 + covi::WIN_RESULT_WORDS * q,
-                       s->g_carry.p, (u64)K.carry, s->g_result.p + 5, s->g_result.p + 7);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(s->h_winres + covi::WIN_RESULT_WORDS * q, s->g_result.p + 8 + covi::WIN_RESULT_WORDS * q, covi::WIN_RESULT_WORDS * sizeof(u64), hipMemcpyDeviceToHost, ps));
-    HIPCHK(hipEventRecord(s->ing_ver_done[q], ps));
-    s->ing_launched += n;
-    s->ing_batch++;
-    return ingest_drain(s, -1);      // whatever is verified already
-}
+struct Round {
+    u32 w = 0, n = 0;             // window, its blocks
+    u64 b0 = 0;                   // first of them in the block table
+    u64 origin = 0;               // file offset of the first byte of its compressed buffer (from the feed plan's launch step)
+    bool final = false;
+    u64 wbytes = 0;               // inflated bytes of the blocks
+    uint8_t *out_bias = nullptr;  // blocks carry absolute offsets of the inflated stream
+    u64 header_left = 0;          // bytes of the BAM header in front of the window's first record (0 once the header has ended)
+};
 
-cov_status cov_ingest_slot_wait(cov_session *s, int slot) {
-    if (!s || slot < 0 || slot >= COV_INGEST_SLOTS || !s->ing_ev[slot]) return COV_ERR_INVALID_ARG;      // (also valid after cov_ingest_end: the slot's last upload)
-    HIPCHK(hipSetDevice(s->cfg.device));
-    HIPCHK(hipEventSynchronize(s->ing_ev[slot]));
+// The round's buffers, sized by ingplan::window_geometry (a process that starts right after another one has given tens of GB back waits
+// for the driver in its large allocations: 0.06 s in a 2 M-read run, tools/r06/call43.sh).
+static cov_status size_round_buffers(cov_session *s, const Round &R) {
+    IngestState &I = s->ing;
+    const u32 q = ingplan::parse_slot(R.w), tb = ingplan::tok_slot(R.w);
+    DevBuf<uint8_t> &win = I.g_win[ingplan::win_slot(R.w)];
+    const ingplan::WindowGeometry g = ingplan::window_geometry(I.span_lo, I.span_hi, R.n, I.K.round_blocks, I.K.carry, covi::INF_SCRATCH_BYTES, covi::INF_TOK_CAP);
+    // A buffer that has to GROW may still be in use: drain the device first.  First-time allocations need no such thing —
+    // and must not wait, or the first four windows (three window buffers, four parse-state sets) would run one after the other.
+    auto grows = [](size_t need, size_t cap) { return cap != 0 && need > cap; };
+    if (grows(g.tok_cap, I.g_tok[tb].cap) || grows(g.full, I.g_ntok[tb].cap) || grows(g.scratch_bytes, I.g_scratch.cap) || grows(g.win_bytes, win.cap) ||
+        grows(g.seg_cap, I.g_seg[q].cap)) {
+        HIPCHK(hipStreamSynchronize(I.aux)); HIPCHK(hipStreamSynchronize(I.parse)); HIPCHK(hipStreamSynchronize(I.ext)); HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    PartTimer alloc{I.s_alloc};
+    HIPCHK(I.g_scratch.reserve(g.scratch_bytes, s->stream));
+    HIPCHK(I.g_tok[tb].reserve(g.tok_cap, s->stream));
+    HIPCHK(I.g_ntok[tb].reserve(g.full, s->stream));
+    HIPCHK(win.reserve(g.win_bytes, s->stream));
+    HIPCHK(I.g_seg[q].reserve(g.seg_cap, s->stream)); HIPCHK(I.g_recbase[q].reserve(g.seg_cap, s->stream)); HIPCHK(I.g_cigbase[q].reserve(g.seg_cap, s->stream));
     return COV_OK;
 }
 
+// k_inflate on the main stream, LZ and CRC-32 on the aux stream; the parse stream is told when the window's bytes are final.
+static cov_status launch_inflate(cov_session *s, const Round &R) {
+    IngestState &I = s->ing;
+    const InflateKernel &K = I.K;
+    const u32 n = R.n, tb = ingplan::tok_slot(R.w), cs = ingplan::cwin_slot(R.w);
+    const covi::BgzfBlock *blocks = I.g_blocks.p + R.b0;
+    u32 *status = I.g_status.p + R.b0, *n_failed = reinterpret_cast<u32 *>(I.g_result.p + ingplan::G_FAILURES) + ingplan::FAIL_INFLATE;
+    covi::tokpos_t *tok = I.g_tok[tb].p; u32 *ntok = I.g_ntok[tb].p;
+    HIPCHK(hipStreamWaitEvent(s->stream, I.fed, 0));
+    // token buffers alternate: this k_inflate may not start before the k_lz_resolve that read the same buffer two rounds ago is done;
+    // the window buffer is free once the extraction of the window three rounds ago is done
+    if (ingplan::tok_reused(R.w)) HIPCHK(hipStreamWaitEvent(s->stream, I.lz_done[tb], 0));
+    if (ingplan::win_reused(R.w)) HIPCHK(hipStreamWaitEvent(s->stream, I.ext_done[ingplan::win_slot(R.w)], 0));
+    const uint8_t *comp_bias = I.g_cwin[cs].p - R.origin;     // blocks carry absolute file offsets
+    if (K.version == 3)
+        hipLaunchKernelGGL(covi::k_inflate_wave, dim3(n), dim3(64), 0, s->stream, comp_bias, blocks, n, R.out_bias, tok, ntok, status, n_failed, 0u);
+    else
+        hipLaunchKernelGGL((covi::k_inflate<INF1_LB, INF1_DB, false>), dim3((n + 63u) / 64u), dim3(64), covi::inflate_smem_bytes(INF1_LB, INF1_DB), s->stream, comp_bias,
+                           blocks, n, R.out_bias, I.g_scratch.p, tok, ntok, status, n_failed);
+    HIPCHK(hipEventRecord(I.inf_done[tb], s->stream));
+    HIPCHK(hipEventRecord(I.cdone[cs], s->stream));      // this round's compressed buffer may be overwritten (three rounds on)
+    HIPCHK(hipStreamWaitEvent(I.aux, I.inf_done[tb], 0));
+    if (K.lz_version == 1)
+        hipLaunchKernelGGL(covi::k_lz_resolve, dim3((n + 3u) / 4u), dim3(256), 0, I.aux, blocks, n, R.out_bias, (const covi::tokpos_t *)tok, (const u32 *)ntok);
+    else
+        hipLaunchKernelGGL(covi::k_lz_stage, dim3((n + 3u) / 4u), dim3(256), 0, I.aux, blocks, n, R.out_bias, (const covi::tokpos_t *)tok, (const u32 *)ntok);
+    // the window's bytes are final once the matches are resolved: the boundary search (parse stream) starts here, beside the
+    // CRC-32 pass, whose verdict is only looked at in cov_ingest_end (the aux stream is in order, so CRC(w) is done before LZ(w + 1)
+    // and with it before anything may overwrite window w)
+    HIPCHK(hipEventRecord(I.lz_done[tb], I.aux));
+    if (I.check_crc) {
+        if (K.version == 3)      // a wave per block, coalesced; resident workgroups stride over the window's blocks
+            hipLaunchKernelGGL(covi::k_crc32_wave, dim3(std::min<u32>((n + 7u) / 8u, (u32)s->n_cus * 4u)), dim3(512), 0, I.aux,
+                               blocks, n, (const uint8_t *)R.out_bias, status, n_failed, (const u32 *)I.g_crc_tab.p);
+        else                     // the lane-per-block combination keeps the lane-per-block CRC
+            hipLaunchKernelGGL(covi::k_crc32, dim3((n + 255u) / 256u), dim3(256), 0, I.aux, blocks, n, (const uint8_t *)R.out_bias, status, n_failed);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamWaitEvent(I.parse, I.lz_done[tb], 0));
+    return COV_OK;
+}
+
+// The window's records on the parse stream: tail of the previous window in front, boundaries, counts, the new tail; its result block
+// follows to the host.
+static cov_status launch_parse(cov_session *s, const Round &R) {
+    IngestState &I = s->ing;
+    const u32 w = R.w, q = ingplan::parse_slot(w);
+    const covi::BamScan S = window_scan(s, w, I.K.carry + R.wbytes, (R.final && !I.open_end) ? 1 : 0, (w == 0 && I.search_first) ? 1 : 0);
+    const covi::BgzfBlock *last = R.n ? &I.h_blocks[R.b0 + R.n - 1] : nullptr;
+    I.win[q].N = S.N; I.win[q].n_seg = S.n_seg; I.win[q].comp_end = last ? last->in_off + last->in_len + 8 : I.comp;
+    hipStream_t ps = I.parse;
+    u64 *G = I.g_result.p, *res = G + ingplan::win_result_at(w);
+    uint8_t *win = I.g_win[ingplan::win_slot(w)].p;
+    if (ingplan::win_reused(w)) HIPCHK(hipStreamWaitEvent(ps, I.ext_done[ingplan::win_slot(w)], 0));     // the carried tail goes in front of a buffer whose records must be out
+    hipLaunchKernelGGL(covi::k_carry_in, dim3(1), dim3(1024), 0, ps, win, I.K.carry, (const uint8_t *)I.g_carry.p, (const u64 *)(G + ingplan::G_CARRY_LEN),
+                       R.header_left, G + ingplan::G_P0);
+    hipLaunchKernelGGL(covi::k_bam_find, dim3((S.n_seg + 3) / 4), dim3(256), 0, ps, S, I.g_seg[q].p);
+    hipLaunchKernelGGL(covi::k_bam_hop, dim3((S.n_seg + 63) / 64), dim3(64), 0, ps, S, I.g_seg[q].p);
+    hipLaunchKernelGGL(covi::k_bam_verify, dim3(1), dim3(1024), 0, ps, S, I.g_seg[q].p, I.g_recbase[q].p, I.g_cigbase[q].p, res,
+                       I.g_carry.p, (u64)I.K.carry, G + ingplan::G_CARRY_LEN, G + ingplan::G_PREV_KEY);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(I.h_winres + ingplan::WIN_RESULT_WORDS * q, res, ingplan::WIN_RESULT_WORDS * sizeof(u64), hipMemcpyDeviceToHost, ps));
+    HIPCHK(hipEventRecord(I.ver_done[q], ps));
+    return COV_OK;
+}
+
+// The next `n64` blocks fed but not launched become window ing.batch; `origin`: where the round's compressed buffer starts in the file.
+static cov_status launch_round_(cov_session *s, uint64_t n64, uint64_t origin, bool final) {
+    IngestState &I = s->ing;
+    Round R;
+    R.b0 = I.launched; R.n = (u32)std::min<uint64_t>(n64, I.feed.blocks - R.b0); R.w = I.batch; R.origin = origin; R.final = final;
+    if (ingplan::win_reused(R.w)) {      // this window's buffer and parse state are free again
+        const cov_status d = ingest_drain(s, ingplan::extracted_before_launch(R.w)); if (d != COV_OK) return d;
+    }
+    { const cov_status b = size_round_buffers(s, R); if (b != COV_OK) return b; }
+    const covi::BgzfBlock *first = R.n ? &I.h_blocks[R.b0] : nullptr, *last = R.n ? &I.h_blocks[R.b0 + R.n - 1] : nullptr;
+    const u64 out_off0 = first ? first->out_off : I.feed.infl;
+    R.wbytes = last ? last->out_off + last->isize - out_off0 : 0;
+    R.out_bias = I.g_win[ingplan::win_slot(R.w)].p + I.K.carry - out_off0;
+    // The BAM header may run over the first windows: such a window parses to no record and no tail (p0 lies behind its end), and the next one
+    // is told how much of the header is left.  Only a header that does not end inside the stream's last window is a failure.
+    R.header_left = ingplan::header_left(I.first_record, out_off0);
+    if (R.final && R.header_left > R.wbytes && !I.fail) I.fail = ingplan::ST_HEADER_LONG;
+    if (R.n) { const cov_status c = launch_inflate(s, R); if (c != COV_OK) return c; }
+    { const cov_status c = launch_parse(s, R); if (c != COV_OK) return c; }
+    I.launched += R.n;
+    I.batch++;
+    return ingest_drain(s, -1);      // whatever is verified already
+}
+static cov_status launch_round(cov_session *s, uint64_t n64, uint64_t origin, bool final) { PartTimer t{s->ing.s_part[1]}; covr::Range rr("ingest: inflate round launch"); return launch_round_(s, n64, origin, final); }
+
+cov_status cov_ingest_slot_wait(cov_session *s, int slot) {
+    if (!s || slot < 0 || slot >= COV_INGEST_SLOTS || !s->ing.ev[slot]) return COV_ERR_INVALID_ARG;      // (also valid after cov_ingest_end: the slot's last upload)
+    HIPCHK(hipSetDevice(s->cfg.device));
+    HIPCHK(hipEventSynchronize(s->ing.ev[slot]));
+    return COV_OK;
+}
+
+// ---- the feed: ingplan::feed_plan says which bytes and table entries of a piece go where and which rounds they complete; the three
+// functions below execute its steps.
 // Bytes [a, b) of the file (present in the staging piece that starts at file offset `piece_off`) go to the compressed buffer of
 // round r, whose first byte is file offset `origin`.
 static cov_status ingest_copy_range(cov_session *s, u32 r, u64 origin, u64 a, u64 b, const uint8_t *piece, u64 piece_off) {
-    if (b <= a) return COV_OK;
-    PartTimer pt{s->ing_s_part[2]};
-    DevBuf<uint8_t> &cw = s->g_cwin[r % 3u];
-    const size_t need = (size_t)s->ing_ccap + 2 * 65536u + 256u;
+    IngestState &I = s->ing;
+    PartTimer pt{I.s_part[2]};
+    DevBuf<uint8_t> &cw = I.g_cwin[ingplan::cwin_slot(r)];
+    const size_t need = (size_t)ingplan::cwin_bytes(I.ccap);
     if (cw.cap < need) {
-        if (cw.cap) { HIPCHK(hipStreamSynchronize(s->ing_copy)); HIPCHK(hipStreamSynchronize(s->stream)); }      // replaced while possibly in use
-        const auto ta0 = std::chrono::steady_clock::now();
+        if (cw.cap) { HIPCHK(hipStreamSynchronize(I.copy)); HIPCHK(hipStreamSynchronize(s->stream)); }      // replaced while possibly in use
+        PartTimer alloc{I.s_alloc};
         HIPCHK(cw.reserve(need, s->stream));
-        s->ing_s_alloc += std::chrono::duration<double>(std::chrono::steady_clock::now() - ta0).count();
     }
-    if ((int64_t)r > s->ing_copy_cleared) {     // first bytes of this round: the k_inflate that read this buffer three rounds ago must be done
-        if (r >= 3) HIPCHK(hipStreamWaitEvent(s->ing_copy, s->ing_cdone[r % 3u], 0));
-        s->ing_copy_cleared = (int64_t)r;
+    if ((int64_t)r > I.copy_cleared) {     // first bytes of this round: the k_inflate that read this buffer three rounds ago must be done
+        if (ingplan::cwin_reused(r)) HIPCHK(hipStreamWaitEvent(I.copy, I.cdone[ingplan::cwin_slot(r)], 0));
+        I.copy_cleared = (int64_t)r;
     }
     if (a < origin || b - origin > cw.cap) { s->err = "cov_ingest_feed: internal error, bytes outside their round's buffer"; return COV_ERR_STATE; }
-    const u64 len = b - a;
-    HIPCHK(hipMemcpyAsync(cw.p + (a - origin), piece + (a - piece_off), len, hipMemcpyHostToDevice, s->ing_copy));
+    HIPCHK(hipMemcpyAsync(cw.p + (a - origin), piece + (a - piece_off), b - a, hipMemcpyHostToDevice, I.copy));
     return COV_OK;
 }
 
-// Table entries [from, ing_blocks) follow the bytes on the copy stream; ing_fed marks "everything fed so far is on the device"
+// Table entries [from, to) follow the bytes on the copy stream; ing.fed marks "everything fed so far is on the device"
 // (recorded even without new entries: the bytes in front of it may complete a round).
-static cov_status ingest_upload_table(cov_session *s, u64 from) {
-    if (from < s->ing_blocks)
-        HIPCHK(hipMemcpyAsync(s->g_blocks.p + from, s->h_blocks + from, (size_t)(s->ing_blocks - from) * sizeof(covi::BgzfBlock), hipMemcpyHostToDevice, s->ing_copy));
-    HIPCHK(hipEventRecord(s->ing_fed, s->ing_copy));
+static cov_status ingest_upload_table(cov_session *s, u64 from, u64 to) {
+    if (from < to)
+        HIPCHK(hipMemcpyAsync(s->ing.g_blocks.p + from, s->ing.h_blocks + from, (size_t)(to - from) * sizeof(covi::BgzfBlock), hipMemcpyHostToDevice, s->ing.copy));
+    HIPCHK(hipEventRecord(s->ing.fed, s->ing.copy));
+    return COV_OK;
+}
+
+static cov_status ingest_run_step(cov_session *s, const ingplan::Step &st, const uint8_t *piece, u64 piece_off) {
+    switch (st.kind) {
+    case ingplan::Step::COPY: return ingest_copy_range(s, st.round, st.origin, st.a, st.b, piece, piece_off);
+    case ingplan::Step::UPLOAD: return ingest_upload_table(s, st.a, st.b);
+    default: return launch_round(s, st.n, st.origin, false);
+    }
+}
+
+// Room for `n_blocks` more table entries: the page-locked mirror (the async uploads read it later) and the device copy with its status words.
+static cov_status ingest_grow_tables(cov_session *s, uint32_t n_blocks) {
+    IngestState &I = s->ing;
+    const u64 need = I.feed.blocks + n_blocks;
+    if (need > I.h_blocks_cap) {
+        const size_t nc = std::max<size_t>(need, I.h_blocks_cap * 2 + 4096);
+        covi::BgzfBlock *nb = nullptr;
+        HIPCHK(hipHostMalloc((void **)&nb, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
+        HIPCHK(hipStreamSynchronize(I.copy));      // earlier uploads still read the old mirror
+        if (I.h_blocks) { memcpy(nb, I.h_blocks, I.feed.blocks * sizeof(covi::BgzfBlock)); (void)hipHostFree(I.h_blocks); }
+        I.h_blocks = nb; I.h_blocks_cap = nc;
+    }
+    if (need > I.g_blocks.cap || need > I.g_status.cap) {
+        HIPCHK(hipStreamSynchronize(I.copy)); HIPCHK(hipStreamSynchronize(I.aux)); HIPCHK(hipStreamSynchronize(s->stream));
+        HIPCHK(I.g_blocks.reserve(need, s->stream, I.feed.blocks));
+        HIPCHK(I.g_status.reserve(need, s->stream, I.feed.blocks));
+    }
     return COV_OK;
 }
 
 cov_status cov_ingest_feed(cov_session *s, int slot, const void *host_bytes, uint64_t file_offset, uint64_t n_bytes,
                            const cov_bgzf_block *blocks, uint32_t n_blocks) {
-    if (!s || !s->ing_active || slot < 0 || slot >= COV_INGEST_SLOTS || (n_bytes && !host_bytes) || (n_blocks && !blocks)) return COV_ERR_INVALID_ARG;
+    if (!s || !s->ing.active || slot < 0 || slot >= COV_INGEST_SLOTS || (n_bytes && !host_bytes) || (n_blocks && !blocks)) return COV_ERR_INVALID_ARG;
     if (s->sam_active) { s->err = "cov_ingest_feed: a SAM text ingest is open (cov_sam_feed / cov_sam_end)"; return COV_ERR_STATE; }
-    if (file_offset + n_bytes > s->ing_comp) { s->err = "cov_ingest_feed: bytes beyond the size given to cov_ingest_begin"; return COV_ERR_INVALID_ARG; }
+    if (file_offset + n_bytes > s->ing.comp) { s->err = "cov_ingest_feed: bytes beyond the size given to cov_ingest_begin"; return COV_ERR_INVALID_ARG; }
     covr::Range rr("ingest: window upload (cov_ingest_feed)");
     HIPCHK(hipSetDevice(s->cfg.device));
     { const cov_status d = ingest_drain(s, -1); if (d != COV_OK) return d; }      // extraction of whatever got verified meanwhile
-    const InflateKernel &K = inflate_kernel(s);
-    // block table: page-locked mirror (the async upload reads it later), then the device copy
-    if (s->ing_blocks + n_blocks > s->h_blocks_cap) {
-        const size_t nc = std::max<size_t>(s->ing_blocks + n_blocks, s->h_blocks_cap * 2 + 4096);
-        covi::BgzfBlock *nb = nullptr;
-        HIPCHK(hipHostMalloc((void **)&nb, nc * sizeof(covi::BgzfBlock), hipHostMallocDefault));
-        HIPCHK(hipStreamSynchronize(s->ing_copy));      // earlier uploads still read the old mirror
-        if (s->h_blocks) { memcpy(nb, s->h_blocks, s->ing_blocks * sizeof(covi::BgzfBlock)); (void)hipHostFree(s->h_blocks); }
-        s->h_blocks = nb; s->h_blocks_cap = nc;
-    }
-    if (s->ing_blocks + n_blocks > s->g_blocks.cap || s->ing_blocks + n_blocks > s->g_status.cap) {
-        HIPCHK(hipStreamSynchronize(s->ing_copy)); HIPCHK(hipStreamSynchronize(s->ing_aux)); HIPCHK(hipStreamSynchronize(s->stream));
-        HIPCHK(s->g_blocks.reserve(s->ing_blocks + n_blocks, s->stream, s->ing_blocks));
-        HIPCHK(s->g_status.reserve(s->ing_blocks + n_blocks, s->stream, s->ing_blocks));
-    }
-    // A round (= the blocks of one k_inflate launch, decoded into one window) closes when it holds as many blocks as the device
-    // keeps resident, or when the next block might no longer fit its compressed buffer.  The decision only looks at where the
-    // previous payload ended, so the bytes of a block that is still incomplete at the end of a piece already go to the buffer of
-    // the round the block will join.
-    if (!s->ing_fed_any) { s->ing_fed_any = true; s->ing_round_start = file_offset; s->ing_prev_end = file_offset; }     // a span starts somewhere inside the file
-    const uint8_t *piece = (const uint8_t *)host_bytes;
-    const u64 piece_end = file_offset + n_bytes;
-    u64 cursor = file_offset, tbl_from = s->ing_blocks;
+    { const cov_status g = ingest_grow_tables(s, n_blocks); if (g != COV_OK) return g; }
+    IngestState &I = s->ing;
     // (Short first rounds — an eighth, a quarter, half a window, so that the device starts on 0.2 GB instead of 1.8 — were measured on one box,
     // alternating: ingest 0.726 s against 0.677 s with full rounds from the start, profiles/r04_ramp_ab_200M.log.  Removed.)
     // (Short LAST rounds — a quarter of the blocks over the file's last 450 / 900 / 1800 MB, to shorten what the device still has to do when the
     // last byte has arrived — measured in round 6: ingest 0.498 / 0.505 / 0.500 s against 0.494 s with full rounds to the end; the device is
     // only just faster than the link, so the lag behind the feed does not shrink with the rounds and their launches wait for the drains.
     // profiles/r06_tail_rounds_ab_200M.json.  Removed.)
-    auto round_full = [&](u64 proxy) { return s->ing_round_n > 0 && (s->ing_round_n >= K.round_blocks || proxy + 65536u + 64u - s->ing_round_start > s->ing_ccap); };
-    for (uint32_t i = 0; i < n_blocks; i++) {
-        const cov_bgzf_block &b = blocks[i];
-        if (b.in_off < s->ing_prev_end || b.in_off + b.in_len > piece_end || b.isize > 65536u || b.in_len > 65536u || b.out_off != s->ing_infl) {
-            s->err = "cov_ingest_feed: block outside the bytes fed so far, out of order, or not contiguous in the inflated stream"; return COV_ERR_INVALID_ARG;
-        }
-        const u64 proxy = s->ing_prev_end;
-        if (round_full(proxy)) {
-            if (proxy > cursor) { const cov_status c = ingest_copy_range(s, s->ing_batch, s->ing_round_start, cursor, proxy, piece, file_offset); if (c != COV_OK) return c; cursor = proxy; }
-            { const cov_status c = ingest_upload_table(s, tbl_from); if (c != COV_OK) return c; tbl_from = s->ing_blocks; }
-            const cov_status lrc = launch_round(s, s->ing_round_n, false);
-            if (lrc != COV_OK) return lrc;
-            s->ing_round_start = proxy; s->ing_round_n = 0;
-        }
+    const u64 blocks0 = I.feed.blocks;
+    I.steps.clear();
+    const bool blocks_ok = ingplan::feed_plan(I.feed, ingplan::FeedRule{I.K.round_blocks, I.ccap}, I.batch, file_offset, n_bytes, blocks, n_blocks,
+                                              [&I](const ingplan::Step &st) { I.steps.push_back(st); });
+    for (u64 i = blocks0; i < I.feed.blocks; i++) {      // the accepted entries, in the mirror before any step uploads them
+        const cov_bgzf_block &b = blocks[i - blocks0];
         covi::BgzfBlock d; d.in_off = b.in_off; d.out_off = b.out_off; d.in_len = b.in_len; d.isize = b.isize; d.crc = b.crc; d.pad = 0;
-        s->h_blocks[s->ing_blocks] = d;
-        s->ing_blocks++; s->ing_round_n++;
-        s->ing_prev_end = b.in_off + b.in_len; s->ing_infl = b.out_off + b.isize;
+        I.h_blocks[i] = d;
     }
-    {   // what is left of the piece: the rest of the current round, and the beginning of a block that may open the next one
-        const u64 proxy = s->ing_prev_end;
-        if (round_full(proxy)) {
-            const u64 cut = std::min(std::max(cursor, proxy), piece_end);
-            cov_status c = ingest_copy_range(s, s->ing_batch, s->ing_round_start, cursor, cut, piece, file_offset);
-            if (c == COV_OK) c = ingest_copy_range(s, s->ing_batch + 1u, proxy, cut, piece_end, piece, file_offset);
-            if (c != COV_OK) return c;
-        } else {
-            const cov_status c = ingest_copy_range(s, s->ing_batch, s->ing_round_start, cursor, piece_end, piece, file_offset);
-            if (c != COV_OK) return c;
-        }
+    for (const ingplan::Step &st : I.steps) { const cov_status c = ingest_run_step(s, st, (const uint8_t *)host_bytes, file_offset); if (c != COV_OK) return c; }
+    if (!blocks_ok) {      // (the rounds completed by the blocks in front of the offending one have been launched, as ever)
+        s->err = "cov_ingest_feed: block outside the bytes fed so far, out of order, or not contiguous in the inflated stream"; return COV_ERR_INVALID_ARG;
     }
-    { const cov_status c = ingest_upload_table(s, tbl_from); if (c != COV_OK) return c; }
-    HIPCHK(hipEventRecord(s->ing_ev[slot], s->ing_copy));
+    HIPCHK(hipEventRecord(I.ev[slot], I.copy));
     return COV_OK;
 }
 
 cov_status cov_ingest_last_stats(const cov_session *s, cov_ingest_stats *out) {
     if (!s || !out) return COV_ERR_INVALID_ARG;
-    *out = s->ing_stats_last;
+    *out = s->ing.stats_last;
     return COV_OK;
 }
 
-static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out);
-cov_status cov_ingest_end(cov_session *s, uint64_t *n_records_out) {
-    const cov_status rc = ingest_end_(s, n_records_out);
-    if (s && s->ing_rec_spilled) {
-        if (rc == COV_OK && n_records_out) *n_records_out += s->ing_rec_spilled;
-        if (rc == COV_ERR_INGEST_FALLBACK) {     // "nothing was appended" no longer holds: part of the file is already in the spilled results
-            s->err += " (after part of the file had left the bounded record store: it cannot be handed to the CPU reader on this session any more)";
-            return COV_ERR_STATE;
-        }
-    }
-    return rc;
+// ---- the end: last round, drain, the ingest's own result words, the verdict (ingplan::outcome) and its text.
+static cov_status ingest_read_globals(cov_session *s, u64 (&glob)[ingplan::G_WINDOWS]) {
+    IngestState &I = s->ing;
+    HIPCHK(hipStreamSynchronize(I.ext));
+    HIPCHK(hipStreamSynchronize(I.aux));        // the CRC pass of the last window runs beside its boundary search: its failure count is read below
+    HIPCHK(hipMemcpyAsync(glob, I.g_result.p, sizeof glob, hipMemcpyDeviceToHost, I.parse));
+    HIPCHK(hipStreamSynchronize(I.parse));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return COV_OK;
 }
-static cov_status ingest_end_(cov_session *s, uint64_t *n_records_out) {
-    if (!s || !s->ing_active) return COV_ERR_INVALID_ARG;
+
+static std::string outcome_text(const IngestState &I, ingplan::Outcome o, u32 inflate_failures) {
+    switch (o) {
+    case ingplan::INFLATE_FAILED: return "device ingest: " + std::to_string(inflate_failures) + " BGZF blocks failed to inflate or their CRC-32 (handing the file to the CPU reader)";
+    // only looked at because mates were asked for: the device pair filter takes "same tid" for "same run of one reference"
+    case ingplan::DISORDER_FILE: return "device ingest: record keys (tid) decrease somewhere in the file; the pair filter of such a file runs on the host (handing the file to the CPU reader)";
+    // contig.rs:129-132: the reference stops at the first record whose tid is lower than its predecessor's
+    case ingplan::UNSORTED: return "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
+    case ingplan::PAST_LIMIT: return "more than 2^32 records or CIGAR words of one reference in the record store";
+    case ingplan::HEADER_LONG: return "device ingest: the BAM header is longer than the first window of the inflated stream (handing the file to the CPU reader)";
+    case ingplan::CG_CIGAR: return "device ingest: a record keeps its CIGAR in CG:B,I (handing the file to the CPU reader)";
+    case ingplan::TAIL_LARGE: return "device ingest: a record larger than the carry buffer between windows (handing the file to the CPU reader)";
+    case ingplan::TRUNCATED: return "device ingest: truncated BAM record";
+    case ingplan::CHAIN: return "device ingest: record boundaries did not verify at segment " + std::to_string(I.fail_dbg[0]) + " (start " + std::to_string(I.fail_dbg[1]) +
+                                ", landed " + std::to_string(I.fail_dbg[2]) + "; handing the file to the CPU reader)";
+    case ingplan::CORRUPT_RECORD: return "device ingest: corrupt BAM record";
+    case ingplan::SPAN_CUTS_RECORD: return "device ingest: the bytes fed for this span end inside one of its own records (handing the span to the CPU reader)";
+    case ingplan::SPAN_END_UNSEEN: return "device ingest: the bytes fed for this span end before a record of the next span (handing the span to the CPU reader)";
+    default: return std::string();
+    }
+}
+
+cov_status cov_ingest_end(cov_session *s, uint64_t *n_records_out) {
+    if (!s || !s->ing.active) return COV_ERR_INVALID_ARG;
     if (s->sam_active) { s->err = "cov_ingest_end: a SAM text ingest is open (cov_sam_end)"; return COV_ERR_STATE; }
     covr::Range rr("ingest: last rounds + parse (cov_ingest_end)");
-    s->ing_active = false;
+    IngestState &I = s->ing;
+    I.active = false;
     HIPCHK(hipSetDevice(s->cfg.device));
     if (n_records_out) *n_records_out = 0;
-    const InflateKernel &K = inflate_kernel(s);
-    { const cov_status lrc = launch_round(s, s->ing_round_n, true); if (lrc != COV_OK) return lrc; }     // the last round: whatever the open one holds
-    { const cov_status d = ingest_drain(s, (int64_t)s->ing_batch); if (d != COV_OK) return d; }
-    u64 glob[8];
-    HIPCHK(hipStreamSynchronize(s->ing_ext));
-    HIPCHK(hipStreamSynchronize(s->ing_aux));        // the CRC pass of the last window runs beside its boundary search: its failure count is read below
-    HIPCHK(hipMemcpyAsync(glob, s->g_result.p, sizeof glob, hipMemcpyDeviceToHost, s->ing_parse));
-    HIPCHK(hipStreamSynchronize(s->ing_parse));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    s->ing_stats_last = s->ing_stats;
+    { const cov_status lrc = launch_round(s, I.feed.round_n, I.feed.round_start, true); if (lrc != COV_OK) return lrc; }     // the last round: whatever the open one holds
+    { const cov_status d = ingest_drain(s, (int64_t)I.batch); if (d != COV_OK) return d; }
+    u64 glob[ingplan::G_WINDOWS];
+    { const cov_status g = ingest_read_globals(s, glob); if (g != COV_OK) return g; }
+    I.stats_last = I.stats;
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] ingest: %llu blocks in %u windows of %u, device allocations %.3fs; host time in drain %.3fs (waiting for a verification %.3fs), in launches %.3fs (drains inside included), in upload calls %.3fs\n",
-                (unsigned long long)s->ing_blocks, s->ing_batch, K.round_blocks, s->ing_s_alloc, s->ing_s_part[0], s->ing_s_part[3], s->ing_s_part[1], s->ing_s_part[2]);
-    const u32 inflate_fail = (u32)(glob[3] & 0xffffffffu);
-    if (inflate_fail) { s->err = "device ingest: " + std::to_string(inflate_fail) + " BGZF blocks failed to inflate or their CRC-32 (handing the file to the CPU reader)"; return COV_ERR_INGEST_FALLBACK; }
-    if (s->ing_fail) {
-        const u32 f = s->ing_fail;
-        const bool span = s->ing_key_lo > 0 || s->ing_key_hi < 0x80000000ll || s->ing_search_first || s->ing_open_end;
-        if ((f & 64u) && !span) {     // only looked at because mates were asked for: the device pair filter takes "same tid" for "same run of one reference"
-            s->err = "device ingest: record keys (tid) decrease somewhere in the file; the pair filter of such a file runs on the host (handing the file to the CPU reader)";
-            return COV_ERR_INGEST_FALLBACK;
-        }
-        if (f & 64u) {    // contig.rs:129-132: the reference stops at the first record whose tid is lower than its predecessor's
-            s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
-            return COV_ERR_UNSORTED;
-        }
-        s->err = (f & 16u) ? "more than 2^32 records or CIGAR words of one reference in the record store"
-               : (f & 32u) ? "device ingest: the BAM header is longer than the first window of the inflated stream (handing the file to the CPU reader)"
-               : (f & 4u) ? "device ingest: a record keeps its CIGAR in CG:B,I (handing the file to the CPU reader)"
-               : (f & 8u) ? "device ingest: a record larger than the carry buffer between windows (handing the file to the CPU reader)"
-               : (f & 2u) ? "device ingest: truncated BAM record"
-               : "device ingest: record boundaries did not verify at segment " + std::to_string(s->ing_fail_dbg[0]) + " (start " + std::to_string(s->ing_fail_dbg[1]) +
-                 ", landed " + std::to_string(s->ing_fail_dbg[2]) + "; handing the file to the CPU reader)";
-        return (f & 16u) ? COV_ERR_INVALID_ARG : COV_ERR_INGEST_FALLBACK;
-    }
-    if ((u32)(glob[3] >> 32)) { s->err = "device ingest: corrupt BAM record"; return COV_ERR_INGEST_FALLBACK; }
-    if (s->ing_open_end && s->ing_tail_key != ~0ull && (long long)s->ing_tail_key < s->ing_key_hi) {
-        s->err = "device ingest: the bytes fed for this span end inside one of its own records (handing the span to the CPU reader)"; return COV_ERR_INGEST_FALLBACK;
-    }
-    if (s->ing_open_end) {
-        // an open end is only trusted when a record from beyond the span was actually seen (complete, or cut by the end of the bytes):
-        // otherwise the span's last records may lie behind the bytes that were fed
-        const bool seen_beyond = ((glob[7] >> 63) && (long long)(u32)glob[7] >= s->ing_key_hi) || (s->ing_tail_key != ~0ull && (long long)s->ing_tail_key >= s->ing_key_hi);
-        if (!seen_beyond) { s->err = "device ingest: the bytes fed for this span end before a record of the next span (handing the span to the CPU reader)"; return COV_ERR_INGEST_FALLBACK; }
+                (unsigned long long)I.feed.blocks, I.batch, I.K.round_blocks, I.s_alloc, I.s_part[0], I.s_part[3], I.s_part[1], I.s_part[2]);
+    ingplan::EndFacts f;
+    f.fail = I.fail; f.inflate_failures = ingplan::inflate_failures(glob[ingplan::G_FAILURES]); f.extract_failures = ingplan::extract_failures(glob[ingplan::G_FAILURES]);
+    f.span = I.is_span(); f.open_end = I.open_end; f.tail_key = I.tail_key; f.prev_key = glob[ingplan::G_PREV_KEY]; f.key_hi = I.key_hi; f.spilled = I.rec_spilled != 0;
+    const ingplan::Outcome o = ingplan::outcome(f);
+    switch (ingplan::ending(o, f.spilled)) {
+    case ingplan::END_OK: break;
+    case ingplan::END_UNSORTED: s->err = outcome_text(I, o, f.inflate_failures); return COV_ERR_UNSORTED;
+    case ingplan::END_INVALID: s->err = outcome_text(I, o, f.inflate_failures); return COV_ERR_INVALID_ARG;
+    case ingplan::END_HAND_BACK: s->err = outcome_text(I, o, f.inflate_failures); return COV_ERR_INGEST_FALLBACK;
+    case ingplan::END_LOST:      // "nothing was appended" no longer holds: part of the file is already in the spilled results
+        s->err = outcome_text(I, o, f.inflate_failures) + " (after part of the file had left the bounded record store: it cannot be handed to the CPU reader on this session any more)";
+        return COV_ERR_STATE;
     }
     { const cov_status c = ingest_commit(s); if (c != COV_OK) return c; }
-    if (n_records_out) *n_records_out = s->ing_rec_total;
+    if (n_records_out) *n_records_out = I.rec_total + I.rec_spilled;
     return COV_OK;
 }
 
@@ -2190,10 +2254,10 @@ uint64_t cov_sam_window_bytes(const cov_session *s) { return s ? s->sam_window :
 
 cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t *name_off, uint32_t n_names, uint64_t expected_bytes) {
     if (!s || (n_names && (!names_blob || !name_off))) return COV_ERR_INVALID_ARG;
-    if (s->ing_active) { s->err = "cov_sam_begin: an ingest is still open (cov_ingest_end / cov_sam_end or cov_ingest_abort first)"; return COV_ERR_STATE; }
+    if (s->ing.active) { s->err = "cov_sam_begin: an ingest is still open (cov_ingest_end / cov_sam_end or cov_ingest_abort first)"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(ingest_prep_wait(s));
-    if (!s->ing_copy) HIPCHK(ingest_prepare_(s));
+    if (!s->ing.copy) HIPCHK(ingest_prepare_(s));
     { const cov_status a = materialise_adopted(s); if (a) return a; }
     hipStream_t st = s->stream;
     HIPCHK(hipStreamSynchronize(st));
@@ -2223,10 +2287,10 @@ cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t 
         HIPCHK(hipStreamSynchronize(st));
         s->m_names = samc::Table{s->m_slots.p, slots - 1u, s->m_blob.p, s->m_noff.p};
     }
-    s->ing_batch = 0; s->ing_extracted = 0; s->ing_rec_total = s->ing_cig_total = 0; s->ing_fail = 0; s->ing_rec_spilled = 0; s->ing_round_n = 0;
+    s->ing.reset_for_file(IngestState::Reset::SAM_FILE);
     s->sam_expected = expected_bytes; s->sam_lines = 0; s->sam_bytes = 0; s->sam_err = 0; s->sam_err_line = 0; s->sam_k = 0;
     s->sam_seen_record = false; s->sam_decode_timed = false; s->sam_ms = 0.f; s->sam_launches = 0;
-    s->ing_active = true; s->sam_active = true;
+    s->ing.active = true; s->sam_active = true;
     return COV_OK;
 }
 
@@ -2250,13 +2314,13 @@ cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64
     }
     const u32 j = s->sam_k & 1u;
     uint8_t *text = s->m_text[j].p;
-    hipStream_t st = s->stream, cp = s->ing_copy;
+    hipStream_t st = s->stream, cp = s->ing.copy;
     if (s->sam_k >= 2) HIPCHK(hipStreamWaitEvent(cp, s->sam_buf_free[j], 0));      // the decode of window k - 2 has read this buffer
     HIPCHK(hipMemcpyAsync(text, hb, n_bytes, hipMemcpyHostToDevice, cp));
     u64 n = n_bytes;
     if (open_end) { HIPCHK(hipMemsetAsync(text + n, '\n', 1, cp)); n++; }      // a last line without its line end is a record
-    HIPCHK(hipEventRecord(s->ing_ev[slot], cp));
-    HIPCHK(hipStreamWaitEvent(st, s->ing_ev[slot], 0));
+    HIPCHK(hipEventRecord(s->ing.ev[slot], cp));
+    HIPCHK(hipStreamWaitEvent(st, s->ing.ev[slot], 0));
     u64 *res = s->m_res.p;
     HIPCHK(hipMemsetAsync(res, 0xff, covs::RES_WORDS * sizeof(u64), st));
     HIPCHK(hipMemsetAsync(res + covs::RES_LAST_AT, 0, sizeof(u64), st));
@@ -2267,7 +2331,7 @@ cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64
     hipLaunchKernelGGL((covp::k_scan_sums<covs::NlPop>), dim3(nbw), dim3(256), 0, st, nlp, n_words, s->m_bsum[0].p);
     hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[0].p, nbw, res + covs::RES_LINES);
     HIPCHK(hipGetLastError());
-    u64 *h = s->h_winres;
+    u64 *h = s->ing.h_winres;
     HIPCHK(hipMemcpyAsync(h, res, covs::RES_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     const u32 n_lines = (u32)h[covs::RES_LINES], nbl = (n_lines + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
@@ -2315,7 +2379,7 @@ cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(s->sam_ev[3], st));
         s->sam_decode_timed = true; s->sam_launches++;
-        s->ing_rec_total += nrec; s->ing_cig_total += ncig;
+        s->ing.rec_total += nrec; s->ing.cig_total += ncig;
     }
     HIPCHK(hipEventRecord(s->sam_buf_free[j], st));
     s->sam_k++;
@@ -2327,26 +2391,26 @@ cov_status cov_sam_end(cov_session *s, uint64_t *n_records_out) {
     if (n_records_out) *n_records_out = 0;
     if (!s->sam_active) { s->err = "cov_sam_end: no SAM text ingest is open (cov_sam_begin)"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
-    s->ing_active = false; s->sam_active = false;
-    HIPCHK(hipStreamSynchronize(s->ing_copy));
+    s->ing.active = false; s->sam_active = false;
+    HIPCHK(hipStreamSynchronize(s->ing.copy));
     HIPCHK(hipStreamSynchronize(s->stream));
     if (s->sam_decode_timed) { s->sam_ms += sam_elapsed(s->sam_ev[2], s->sam_ev[3]); s->sam_decode_timed = false; }
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] sam: device SAM decode: %llu bytes in %u windows of %llu, %llu lines, %llu records, kernels %.3f ms\n", (unsigned long long)s->sam_bytes, s->sam_k,
-                (unsigned long long)s->sam_window, (unsigned long long)s->sam_lines, (unsigned long long)(s->ing_rec_total + s->ing_rec_spilled), s->sam_ms);
+                (unsigned long long)s->sam_window, (unsigned long long)s->sam_lines, (unsigned long long)(s->ing.rec_total + s->ing.rec_spilled), s->sam_ms);
     { const cov_status c = ingest_commit(s); if (c != COV_OK) return c; }
-    if (n_records_out) *n_records_out = s->ing_rec_total + s->ing_rec_spilled;
+    if (n_records_out) *n_records_out = s->ing.rec_total + s->ing.rec_spilled;
     return COV_OK;
 }
 
 cov_status cov_ingest_want_mates(cov_session *s, int on) {
-    if (!s || s->ing_active) return COV_ERR_INVALID_ARG;
+    if (!s || s->ing.active) return COV_ERR_INVALID_ARG;
     s->want_mates = on != 0;
     return COV_OK;
 }
 
 cov_status cov_ingest_want_grouping(cov_session *s, int on) {
-    if (!s || s->ing_active) return COV_ERR_INVALID_ARG;
+    if (!s || s->ing.active) return COV_ERR_INVALID_ARG;
     s->want_grouping = on != 0;
     return COV_OK;
 }
@@ -2388,7 +2452,7 @@ static cov_status gather_store(cov_session *s, const u32 *order, u32 S, bool wit
 cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint64_t *n_selected, uint64_t *n_primary) {
     if (!s || !f) return COV_ERR_INVALID_ARG;
     covr::Range rr("pair filter (cov_pair_filter_apply)");
-    if (s->adopted || s->ing_active) { s->err = "cov_pair_filter_apply: needs the session's own record store, filled by the device ingest"; return COV_ERR_STATE; }
+    if (s->adopted || s->ing.active) { s->err = "cov_pair_filter_apply: needs the session's own record store, filled by the device ingest"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_pair_filter_apply: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
     if (s->store.mates_valid != s->store.n_records) { s->err = "cov_pair_filter_apply: the store holds records without mate columns (cov_ingest_want_mates before every ingest, no cov_push_batch)"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
@@ -2533,9 +2597,9 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
     if (!s) return COV_ERR_INVALID_ARG;
     covr::Range rr("group records by reference (cov_group_records)");
     if (n_moved) *n_moved = 0;
-    if (s->ing_active) { s->err = "cov_group_records: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->ing.active) { s->err = "cov_group_records: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
     if (s->adopted) { s->err = "cov_group_records: needs the session's own record store, not an adopted device batch (cov_push_batch_device)"; return COV_ERR_STATE; }
-    if (s->ing_was_span) { s->err = "cov_group_records: the store holds one tid span of a file (cov_ingest_span), which is cut where a file sorted by reference changes tid"; return COV_ERR_STATE; }
+    if (s->ing.was_span) { s->err = "cov_group_records: the store holds one tid span of a file (cov_ingest_span), which is cut where a file sorted by reference changes tid"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_group_records: a sample that is not sorted by reference must fit the record store (part of it already left the bounded store, judged in file order)"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
@@ -2648,9 +2712,9 @@ cov_status cov_ingest_release(cov_session *s) {
     if (!s) return COV_ERR_INVALID_ARG;
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->ing_aux) HIPCHK(hipStreamSynchronize(s->ing_aux));
-    if (s->ing_parse) HIPCHK(hipStreamSynchronize(s->ing_parse));
-    if (s->ing_ext) HIPCHK(hipStreamSynchronize(s->ing_ext));
+    if (s->ing.aux) HIPCHK(hipStreamSynchronize(s->ing.aux));
+    if (s->ing.parse) HIPCHK(hipStreamSynchronize(s->ing.parse));
+    if (s->ing.ext) HIPCHK(hipStreamSynchronize(s->ing.ext));
     ingest_free_buffers(s);
     return COV_OK;
 }
@@ -2658,10 +2722,10 @@ cov_status cov_ingest_release(cov_session *s) {
 // Test hook: the inflated stream of the last ingest (bytes [offset, offset + n) copied to `out`) — kept only when the whole file
 // was a single window.
 cov_status cov_ingest_copy_inflated(cov_session *s, uint64_t offset, uint64_t n, void *out) {
-    if (!s || offset + n > s->ing_infl || (n && !out)) return COV_ERR_INVALID_ARG;
-    if (s->ing_batch != 1) { s->err = "cov_ingest_copy_inflated: the file was parsed in several windows, the stream is gone"; return COV_ERR_STATE; }
+    if (!s || offset + n > s->ing.feed.infl || (n && !out)) return COV_ERR_INVALID_ARG;
+    if (s->ing.batch != 1) { s->err = "cov_ingest_copy_inflated: the file was parsed in several windows, the stream is gone"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
-    HIPCHK(hipMemcpyAsync(out, s->g_win[0].p + inflate_kernel(s).carry + offset, n, hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipMemcpyAsync(out, s->ing.g_win[0].p + s->ing.K.carry + offset, n, hipMemcpyDeviceToHost, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     return COV_OK;
 }

@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "pair_kernels.hip.h"
+#include "ingest_plan_core.h"
 
 namespace covi {
 
@@ -869,7 +870,7 @@ struct SegInfo {
     u64 start;     // first record start found in the segment (~0 = none)
     u64 landed;    // where the hop from `start` ended (first record start at or beyond the segment end, or N)
     u32 n_rec, n_cig;
-    u32 flags;     // bit 1: keys decrease inside the hop (bit 0 was: a CG:B,I record, now resolved by the extraction)
+    u32 flags;     // SEG_DISORDER: keys decrease inside the hop (bit 0 was: a CG:B,I record, now resolved by the extraction)
     u32 first_key, last_key;     // keys of the first / last record hopped over (any record, not only the span's); valid when n_hop != 0
     u32 n_hop;                   // records hopped over
     // The hop's chain cut in EXT_PARTS pieces for the extraction (a lane per piece instead of a lane per segment: k_bam_extract is a chain of
@@ -881,6 +882,7 @@ struct SegInfo {
 };
 static_assert(sizeof(SegInfo) == 80, "SegInfo: 80 bytes per segment");
 constexpr u32 EXT_PARTS = 4, EXT_PIECE = 8192;
+constexpr u32 SEG_DISORDER = 2u;      // SegInfo::flags
 constexpr u32 REPAIR_BUDGET = 64;      // false starts k_bam_verify drops per window before it gives the file up
 // A long record waiting for its wave.
 struct LongRec { u64 off, ri, ci; u32 words, pad; };      // the record's offset in the window, its index in the store, where its CIGAR words go, how many
@@ -939,7 +941,7 @@ __device__ __forceinline__ void hop_segment(const BamScan &S, SegInfo *seg, u32 
         if (bs < 32u || q + 4 + (u64)bs > S.N) break;
         const u32 ncig = ld16(r + 16);
         const long long key = rec_key((int)ld32(r + 4));
-        if (nh == 0u) k_first = (u32)key; else if ((u32)key < k_last) fl |= 2u;
+        if (nh == 0u) k_first = (u32)key; else if ((u32)key < k_last) fl |= SEG_DISORDER;
         k_last = (u32)key; nh++;
         if (key >= S.key_lo && key < S.key_hi) {
             u32 words = ncig;
@@ -964,18 +966,12 @@ __global__ __launch_bounds__(64) void k_bam_hop(BamScan S, SegInfo *seg) {
 }
 
 // Single workgroup: chain verification, the repair of false starts, exclusive scans over segments (records, CIGAR words) + the tail.
-// result[0] = records of this window, [1] = CIGAR words, [2] = status (0 ok, 1 chain mismatch, 2 truncated, 4 needs the CPU
-// reader, 8 tail larger than the carry buffer, 64 record keys (tid) decrease somewhere in the window — looked at for spans
-// only: a span trusts the file's order when it drops its neighbours' records, the whole-file path reports disorder from
-// cov_finish in file order with the other per-record errors), [3] = offset where the tail starts (first byte no record of this window owns),
-// [4..6] = first bad segment / its start / where its hop landed, [7] = key of the tail's record, [8] = long records (k_bam_extract_long's
-// list entries), [9] = starts dropped by the repair, [10] = most records one hop went over, [11] = segments with a start.
-// The tail [result[3], N) goes to `carry`, its length to *carry_len.
+// `result` is the window's result block: its words and the status bits are named in ingest_plan_core.h (WinWord, Status).
+// The tail [result[W_TAIL], N) goes to `carry`, its length to *carry_len.
 // The repair: a segment whose hop does not land on the next live segment's start has met a false start there — eight record-shaped images
 // inside a B array, say.  The chain in front of it comes from p0 through verified starts, so the suspect is the start it missed: thread 0
 // marks that start dead, hops the segment in front again up to the following live start (counts, keys, disorder flag and extraction
-// pieces are the hop's own), and the pass over the segments runs again — REPAIR_BUDGET times per window at the most, then status 1 as ever.
-constexpr u32 WIN_RESULT_WORDS = 12;
+// pieces are the hop's own), and the pass over the segments runs again — REPAIR_BUDGET times per window at the most, then ST_CHAIN as ever.
 __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u64 *__restrict__ rec_base, u64 *__restrict__ cig_base,
                                                      u64 *__restrict__ result, uint8_t *__restrict__ carry, u64 carry_cap, u64 *__restrict__ carry_len,
                                                      u64 *__restrict__ prev_key) {
@@ -997,8 +993,8 @@ __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u6
             if (s.start == ~0ull) continue;
             live++;
             if (s.n_hop) {
-                if (s.flags & 2u) bad |= 64u;
-                if (khave && s.first_key < kl) bad |= 64u;
+                if (s.flags & SEG_DISORDER) bad |= ingplan::ST_DISORDER;
+                if (khave && s.first_key < kl) bad |= ingplan::ST_DISORDER;
                 if (!khave) kf = s.first_key;
                 kl = s.last_key; khave = 1u;
             }
@@ -1006,8 +1002,8 @@ __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u6
             for (u32 j = k + 1; j < S.n_seg; j++) { const u64 st = seg[j].start; if (st != ~0ull) { want = st; last_live = false; break; } }
             if (last_live) {
                 s_tail = s.landed;                                  // exactly one segment is the last live one
-                if (S.final && s.landed != S.N) { bad |= 2u; atomicMin(&s_badk, (u64)k); }
-            } else if (s.landed != want) { bad |= 1u; atomicMin(&s_badk, (u64)k); }
+                if (S.final && s.landed != S.N) { bad |= ingplan::ST_TRUNCATED; atomicMin(&s_badk, (u64)k); }
+            } else if (s.landed != want) { bad |= ingplan::ST_CHAIN; atomicMin(&s_badk, (u64)k); }
             nr += s.n_rec; nc += s.n_cig; nl += s.n_long; mh = max(mh, s.n_hop);
         }
         if (bad) atomicOr(&s_bad, bad);
@@ -1017,7 +1013,7 @@ __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u6
         s_rec[t] = nr; s_cig[t] = nc; s_kfirst[t] = kf; s_klast[t] = kl; s_khave[t] = khave;
         __syncthreads();
         // (a truncated last segment is the highest live one: with a mismatch anywhere, s_badk is a mismatching segment)
-        if (!(s_bad & 1u) || repaired == REPAIR_BUDGET) break;
+        if (!(s_bad & ingplan::ST_CHAIN) || repaired == REPAIR_BUDGET) break;
         if (t == 0) {
             const u32 k = (u32)s_badk;
             for (u32 j = k + 1; j < S.n_seg; j++) if (seg[j].start != ~0ull) { seg[j].start = ~0ull; break; }
@@ -1036,19 +1032,19 @@ __global__ __launch_bounds__(1024) void k_bam_verify(BamScan S, SegInfo *seg, u6
         {   // order across the threads' runs of segments, and against the last key of the previous window (*prev_key, bit 63 = valid)
             const u64 pk = *prev_key;
             u32 prev = (u32)pk, have = (u32)(pk >> 63);
-            for (u32 i = 0; i < 1024; i++) if (s_khave[i]) { if (have && s_kfirst[i] < prev) st |= 64u; prev = s_klast[i]; have = 1u; }
+            for (u32 i = 0; i < 1024; i++) if (s_khave[i]) { if (have && s_kfirst[i] < prev) st |= ingplan::ST_DISORDER; prev = s_klast[i]; have = 1u; }
             *prev_key = (u64)prev | ((u64)have << 63);
         }
-        if (S.final && tail_len != 0) st |= 2u;
-        if (!tail_fits) st |= 8u;
-        result[0] = a; result[1] = c; result[2] = st; result[3] = tail;
+        if (S.final && tail_len != 0) st |= ingplan::ST_TRUNCATED;
+        if (!tail_fits) st |= ingplan::ST_TAIL_LARGE;
+        result[ingplan::W_RECORDS] = a; result[ingplan::W_CIGAR] = c; result[ingplan::W_STATUS] = st; result[ingplan::W_TAIL] = tail;
         const u64 kb = s_badk;
-        result[4] = kb;
-        if (kb < S.n_seg) { result[5] = seg[kb].start; result[6] = seg[kb].landed; }
+        result[ingplan::W_BAD_SEG] = kb;
+        if (kb < S.n_seg) { result[ingplan::W_BAD_START] = seg[kb].start; result[ingplan::W_BAD_LANDED] = seg[kb].landed; }
         // key of the record the tail begins with (~0 when there is no tail or its tid is not here yet): a span's reader checks
         // that the record cut by the end of its bytes lies beyond its key range
-        result[7] = (tail_len >= 8) ? (u64)rec_key((int)ld32(S.u + tail + 4)) : ~0ull;
-        result[8] = s_long; result[9] = repaired; result[10] = s_maxhop; result[11] = s_live;
+        result[ingplan::W_TAIL_KEY] = (tail_len >= 8) ? (u64)rec_key((int)ld32(S.u + tail + 4)) : ~0ull;
+        result[ingplan::W_LONG] = s_long; result[ingplan::W_REPAIRED] = repaired; result[ingplan::W_MAX_HOP] = s_maxhop; result[ingplan::W_LIVE_SEGS] = s_live;
         *carry_len = tail_fits ? tail_len : 0ull;
     }
     __syncthreads();
@@ -1082,7 +1078,7 @@ struct RecStore {
 
 // One lane per segment: second hop; every record's fields go straight into the record store.
 // A long record (bamrec::is_long, the test k_bam_hop counted n_long with) gets its fixed columns and its CIGAR range here like any other;
-// its CIGAR copy and NM scan are left to k_bam_extract_long through `longs` (appended at *n_long: the window has exactly result[8] of them).
+// its CIGAR copy and NM scan are left to k_bam_extract_long through `longs` (appended at *n_long: the window has exactly result[W_LONG] of them).
 __global__ __launch_bounds__(64) void k_bam_extract(BamScan S, const SegInfo *__restrict__ seg, const u64 *__restrict__ rec_base,
                                                     const u64 *__restrict__ cig_base, RecStore R, u32 *__restrict__ n_bad, u32 parts,
                                                     LongRec *__restrict__ longs, u32 *__restrict__ n_long, u32 long_cap) {

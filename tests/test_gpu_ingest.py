@@ -236,6 +236,24 @@ def test_device_ingest_in_many_windows(tmp_path, mode, round_blocks, carry_kb, c
     assert "WINDOWS_OK " + mode in r.stdout
 
 
+def test_device_ingest_rounds_close_where_the_plan_says(tmp_path):
+    """The fixture eg2.bam in BGZF blocks of at most 700 inflated bytes is 11 841 blocks (the EOF block included) of at most 257 bytes,
+    2.2 MB in all: with 1024 blocks per round the rounds close on the block count, and the feed plan (csrc/ingest_plan_core.h, checked on
+    the CPU in test_ingest_plan_core.py) makes ceil(11 841 / 1024) = ceil(11 840 / 1024) = 12 of them, whether or not the feeder tables the
+    EOF block.  The device must have run exactly those 12 windows — every ring comes round at least three times — and deliver the CPU
+    reader's records, field for field (the worker compares them).
+
+    eg2.bam names 54 579 references: its BAM header is 4 974 980 inflated bytes and runs over the first six windows of 716 800, which
+    parse to no record and no tail (ingplan::header_left tells each window how much of the header is still in front of it)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "tests", "ingest_windows_worker.py"), "eg2_small_blocks", str(tmp_path)], capture_output=True, text=True,
+                       env=with_knobs(os.environ, ingest_round_blocks=1024), cwd=root, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    assert "WINDOWS_OK eg2_small_blocks blocks=11841 records=11200 windows=12\n" in r.stdout
+
+
 @pytest.mark.parametrize("count", [2, 3, 5])
 def test_device_ingest_of_tid_spans_partitions_the_file(tmp_path, count):
     """covh_bam_gpu_ingest_span: each span reads only its part of the file (bisection for its end), the device drops the neighbours'
