@@ -247,7 +247,7 @@ struct cov_session {
                            // 16 -> 0.642, 32 -> 0.866.  With the statistics derived from the histogram a chunk end only moves bins and the better balance of short
                            // chunks wins: profiles/hist_derived_stats_ab.json.)  COVERM_KNOBS pileup_chunk_tiles overrides it.
     int prep_kernel = 0;   // 0 = k_prep_lean (prep_lean.hip.h); COVERM_PREP_KERNEL=7 forces k_prep7s, the second implementation (tests)
-    int est_lanes = -1;        // k_estimate_lanes (a lane per contig) from 65 536 contigs on; COVERM_EST_LANES=1 | 0 forces it on / off (tests)
+    int est_lanes = -1;        // k_estimate_lanes / k_genome_estimate_lanes (a lane per contig / genome) from 65 536 of them on; COVERM_EST_LANES=1 | 0 forces it on / off (tests)
     int fast_tables = 1;       // k_pileup_fast (one table of biased deltas: the default) or k_pileup_fast2t (two count tables; COVERM_FAST_TABLES=2)
     int n_cus = 256;
 
@@ -1401,7 +1401,7 @@ static cov_status stage_genomes(cov_session *s, const FinishPlan &p, const PassV
     }
     DevGenomeStats *gstats = reinterpret_cast<DevGenomeStats *>(s->d_gout.p);
     float *gest = reinterpret_cast<float *>(s->d_gout.p + (size_t)nG * sizeof(DevGenomeStats));
-    const bool lanes = nG >= 65536u;      // a lane per genome, as for the contigs of an assembly
+    const bool lanes = nG >= p.genome_lanes_from;      // a lane per genome, as for the contigs of an assembly
     const auto estimate = lanes ? &k_genome_estimate_lanes : &k_genome_estimate;
     hipLaunchKernelGGL(estimate, dim3(lanes ? (nG + 255u) / 256u : (nG + 3u) / 4u), dim3(256), 0, st, (const DevGenome *)s->d_genomes.p, nG, (const u64 *)s->d_ghist.p, s->est, gest, gstats);
     time_end(s, COV_K_GENOME);

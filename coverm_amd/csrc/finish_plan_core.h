@@ -37,6 +37,9 @@ struct FinishPlan {
     u32 n_steps = 0, gen_grid = 0;
     bool gen_all = false;
     bool est_lanes = false;              // an assembly: a lane per contig (pileup_kernels.hip.h, estimate_body)
+    // the genome entries' count is the pass's own when the separator scan builds them (stage 9), so the plan holds the count from which
+    // a lane per genome runs (genome_kernels.hip.h, genome_estimate_body): 65 536 as for the contigs, the knob forces it on (0) / off
+    u32 genome_lanes_from = 65536u;
     bool run_pileup = false;             // scans, ranges, histogram layout, pileup: there are records and tiles
     bool identity_side = false;          // the identity kernels run on the side stream, beside k_ranges / k_pileup
     bool id_primary = false, id_nonsupp = false;      // identity streams actually needed (the others: skipped by k_prep and the k_id_* kernels)
@@ -62,6 +65,7 @@ inline FinishPlan plan(const Facts &f) {
     p.want_hist = want_hist; p.want_id = want_id; p.lean = f.lean_finish; p.ncig = f.ncig;
     p.run_prep = R != 0; p.prep7 = f.prep_kernel == 7;
     p.est_lanes = f.est_lanes_knob < 0 ? nT >= 65536u : f.est_lanes_knob == 1;
+    p.genome_lanes_from = f.est_lanes_knob < 0 ? 65536u : f.est_lanes_knob == 1 ? 0u : ~0u;
     p.long_cigars = R && f.ncig / R >= 16;
     p.prep_passes = p.long_cigars ? 1 : LEAN_PASSES;
     p.prep_chunk = (u32)(256 * p.prep_b * p.prep_passes);

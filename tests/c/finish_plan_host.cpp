@@ -18,14 +18,14 @@ constexpr int PREP_PASSES = 8;      // pileup_kernels.hip.h
 struct Flat {
     u64 long_cigars, prep_passes, prep_chunk, prep_grid, n_steps, gen_all, gen_grid, est_lanes, run_prep, prep7, run_pileup, identity_side,
         id_primary, id_nonsupp, compacted, derive_in_est, hist_stats_launch, hist_prefetch, nf, runs, genomes, genome_identity, lean_error, ncig,
-        want_hist, want_id, lean;
+        want_hist, want_id, lean, genome_lanes_from;
 };
 constexpr int N_FIELDS = sizeof(Flat) / sizeof(u64);
 
 static Flat flat_of(const finplan::FinishPlan &p) {
     return Flat{p.long_cigars, (u64)p.prep_passes, p.prep_chunk, p.prep_grid, p.n_steps, p.gen_all, p.gen_grid, p.est_lanes, p.run_prep, p.prep7,
                 p.run_pileup, p.identity_side, p.id_primary, p.id_nonsupp, p.compacted, p.derive_in_est, p.hist_stats_launch, p.hist_prefetch,
-                p.nf, p.runs, p.genomes, p.genome_identity, p.lean_without_genomes, p.ncig, p.want_hist, p.want_id, p.lean};
+                p.nf, p.runs, p.genomes, p.genome_identity, p.lean_without_genomes, p.ncig, p.want_hist, p.want_id, p.lean, p.genome_lanes_from};
 }
 
 // finish_once as it stood: only the lines that decide, in their order; `s->x` became `F.x`, a launch or a branch became the flag that says it ran.
@@ -77,6 +77,9 @@ static Flat frozen(const finplan::Facts &F) {
     o.long_cigars = long_cigars; o.prep_passes = (u64)prep_passes; o.prep_chunk = prep_chunk; o.prep_grid = prep_grid; o.est_lanes = est_lanes;
     o.compacted = compacted; o.derive_in_est = derive_in_est; o.nf = nf; o.runs = runs; o.genomes = genomes; o.ncig = ncig_all;
     o.want_hist = want_hist; o.want_id = want_id; o.lean = lean;
+    // stage_genomes as it stood: `const bool lanes = nG >= 65536u;` — the count it compared nG with; the knob (new with the plan's field)
+    // replaces the count by "always" / "never"
+    o.genome_lanes_from = F.est_lanes_knob < 0 ? 65536u : F.est_lanes_knob == 1 ? 0u : 0xffffffffu;
     // the side stream's launch and its join always came together
     if (o.identity_side == 1 || o.identity_side == 2) o.identity_side = ~0ull;
     else o.identity_side = o.identity_side == 3;

@@ -13,8 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "c", "finish_plan_host.cpp")
 FIELDS = ("long_cigars", "prep_passes", "prep_chunk", "prep_grid", "n_steps", "gen_all", "gen_grid", "est_lanes", "run_prep", "prep7", "run_pileup",
           "identity_side", "id_primary", "id_nonsupp", "compacted", "derive_in_est", "hist_stats_launch", "hist_prefetch", "nf", "runs", "genomes",
-          "genome_identity", "lean_error", "ncig", "want_hist", "want_id", "lean")
-NUMBERS = ("prep_passes", "prep_chunk", "prep_grid", "n_steps", "gen_grid", "nf", "ncig")
+          "genome_identity", "lean_error", "ncig", "want_hist", "want_id", "lean", "genome_lanes_from")
+NUMBERS = ("prep_passes", "prep_chunk", "prep_grid", "n_steps", "gen_grid", "nf", "ncig", "genome_lanes_from")
 BOOLS = tuple(f for f in FIELDS if f not in NUMBERS)
 # R x nT x tiles x CIGAR words x est.n x knob x prep kernel x CUs x want bits x boolean facts
 CASES = 11 * 5 * 3 * 3 * 2 * 3 * 2 * 2 * 16 * 128
@@ -76,6 +76,9 @@ def test_thresholds_written_out(host):
     assert plan(host, R=12800, nT=1, n_cus=1)["gen_grid"] == 8 and plan(host, R=12800, nT=1000, n_cus=1)["gen_grid"] == 50      # 200 steps: 8 x CUs, or 64 x CUs and (200 + 3) / 4
     assert plan(host, nT=65535)["est_lanes"] == 0 and plan(host, nT=65536)["est_lanes"] == 1
     assert plan(host, nT=65536, knob=0)["est_lanes"] == 0 and plan(host, nT=1, knob=1)["est_lanes"] == 1
+    # a lane per genome: from 65 536 entries on whatever the contigs' count (nG >= genome_lanes_from), the knob forces it on / off
+    assert plan(host, nT=1)["genome_lanes_from"] == 65536 and plan(host, nT=65536)["genome_lanes_from"] == 65536
+    assert plan(host, nT=65536, knob=1)["genome_lanes_from"] == 0 and plan(host, nT=65536, knob=0)["genome_lanes_from"] == 0xffffffff
     assert plan(host, nT=3, est_n=1)["nf"] == 3 and plan(host, nT=3, est_n=1, flags=MASK)["nf"] == 0 and plan(host, nT=3, est_n=1, flags=RUNS)["nf"] == 0
 
 
