@@ -367,6 +367,7 @@ struct cov_session {
     DevContig *h_ctg = nullptr;
     DevGlobal h_glob{};
     bool last_gen_all = false;         // the last finish ran k_prep_generic over every step (cov_last_paths)
+    uint32_t last_passes = 0;          // how often the last finish ran the pipeline over the store: 2 when the bucket buffer was too small (cov_last_paths)
     uint64_t algo_bytes = 0;
 
     hipEvent_t ev[COV_K_COUNT][2] = {};
@@ -1104,7 +1105,8 @@ static cov_status finish_once(cov_session *s, cov_contig_stats *stats, cov_summa
 static cov_status finish_store(cov_session *s, cov_contig_stats *stats, cov_summary *summary) {
     bool again = false;
     cov_status st = finish_once(s, stats, summary, again);
-    if (st == COV_OK && again) st = finish_once(s, stats, summary, again);
+    if (s) s->last_passes = 1;
+    if (st == COV_OK && again) { st = finish_once(s, stats, summary, again); s->last_passes = 2; }
     if (st == COV_OK && again) { s->err = "internal error: bucket sizing did not converge"; return COV_ERR_STATE; }
     return st;
 }
@@ -2882,6 +2884,21 @@ cov_status cov_last_paths(const cov_session *s, cov_path_counts *out) {
     if (!s || !out) return COV_ERR_INVALID_ARG;
     out->listed_steps = s->h_glob.n_gen; out->generic_only = s->last_gen_all ? 1u : 0u;
     out->slow_tiles = s->h_glob.n_slow; out->bucket_records = s->h_glob.n_cx;
+    out->bucket_entries = (uint32_t)std::min<uint64_t>(s->h_glob.cx_total, 0xffffffffull); out->passes = s->last_passes;
+    return COV_OK;
+}
+
+// Test hook: the run words the last finish's k_prep left, one per record of the store (x | y << 32, see "Run word" in pileup_kernels.hip.h).
+cov_status cov_copy_run_words(const cov_session *cs, uint64_t *out) {
+    cov_session *s = const_cast<cov_session *>(cs);      // (nothing of the session changes but the text of a HIP error)
+    if (!s || !s->finished) return COV_ERR_STATE;
+    // no run words for the whole store: part of it left in a spill, the records are an adopted device batch, or there are none
+    if (s->spill.active || s->adopted || s->store.n_records == 0 || s->d_runs.cap < s->store.n_records) return COV_ERR_STATE;
+    if (!out) return COV_ERR_INVALID_ARG;
+    static_assert(sizeof(uint2) == sizeof(uint64_t), "a run word is eight bytes, x first");
+    HIPCHK(hipSetDevice(s->cfg.device));
+    HIPCHK(hipMemcpyAsync(out, s->d_runs.p, (size_t)s->store.n_records * sizeof(uint2), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
     return COV_OK;
 }
 

@@ -309,9 +309,19 @@ class Session:
 
     def last_paths(self):
         """cov_last_paths: which branches of the device pipeline the last finish took (diagnostics for the parity tests)."""
-        v = (C.c_uint32 * 4)()
+        v = (C.c_uint32 * 6)()
         self._check(self._lib.cov_last_paths(self._h, C.byref(v)))
-        return dict(listed_steps=int(v[0]), generic_only=bool(v[1]), slow_tiles=int(v[2]), bucket_records=int(v[3]))
+        return dict(listed_steps=int(v[0]), generic_only=bool(v[1]), slow_tiles=int(v[2]), bucket_records=int(v[3]),
+                    bucket_entries=int(v[4]), passes=int(v[5]))
+
+    def run_words(self):
+        """cov_copy_run_words: the run word k_prep left for every record of the store in the last finish, as uint64 (x | y << 32).  Raises
+        CovError (COV_ERR_STATE) when there are none for the whole store: no records, an adopted device batch, a spilled store."""
+        n = C.c_uint64(0)
+        self._check(self._lib.cov_copy_records(self._h, None, C.byref(n), None))      # (how many records the store holds)
+        out = np.zeros(max(1, int(n.value)), dtype=np.uint64)
+        self._check(self._lib.cov_copy_run_words(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out[:int(n.value)]
 
     def algorithmic_bytes(self):
         b = C.c_uint64(0)

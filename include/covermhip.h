@@ -335,9 +335,16 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
 /* Which paths the last cov_finish took — diagnostics, so that a parity case built for one branch of the device pipeline can assert that the
  * branch ran (tests/test_gpu_step_shapes.py).  listed_steps: steps of 64 records k_prep_lean left to k_prep_generic (generic_only = 1: a
  * sample of fewer than 128 records per contig, k_prep_generic walked all of them and nothing was listed); slow_tiles: tiles k_pileup_fast
- * left to k_pileup_stream; bucket_records: records whose CIGAR went through the bucket list (CX_MIN_OPS operations and more). */
-typedef struct { uint32_t listed_steps, generic_only, slow_tiles, bucket_records; } cov_path_counts;
+ * left to k_pileup_stream; bucket_records: records whose CIGAR went through the bucket list (more than CX_MIN_OPS operations);
+ * bucket_entries: the (operation, tile) pairs those records expanded to (saturated at 2^32 - 1); passes: how often the finish ran the
+ * pipeline over the store (2: the bucket buffer was too small for bucket_entries, it was grown and the pass repeated). */
+typedef struct { uint32_t listed_steps, generic_only, slow_tiles, bucket_records, bucket_entries, passes; } cov_path_counts;
 cov_status cov_last_paths(const cov_session *s, cov_path_counts *out);
+/* Test hook: the 8-byte run words k_prep left in the last cov_finish, one per record of the store in store order, as x | (uint64_t)y << 32
+ * (x = start of the first merged M/=/X run, y = 0 or type << 30 | fields: SINGLE 0, DOUBLE 1 with len1 | gap << 10 | len2 << 18, COMPLEX 2,
+ * BUCKET 3).  COV_ERR_STATE when the last finish did not leave run words for the whole store: no finish, no records, an adopted device
+ * batch (cov_push_batch_device), or part of the sample already left the bounded record store. */
+cov_status cov_copy_run_words(const cov_session *s, uint64_t *out);
 /* Algorithmic HBM bytes of the last cov_finish (DESIGN.md "Algorithmic bytes"): record SoA + CIGAR
  * words read once, plus result structs written. */
 cov_status cov_algorithmic_bytes(const cov_session *s, uint64_t *bytes);

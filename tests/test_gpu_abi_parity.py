@@ -30,7 +30,7 @@ def to_bamdata(batch: RecordBatch, ref_lens, names=None) -> BamData:
                    [b"r%d" % i for i in range(n)] if n < 100000 else [], "")
 
 
-def compare(b: BamData, ff=(True, True, False), fp=None, excl=75, mask=None, check_depth=(), chunks=1, paths_out=None):
+def compare(b: BamData, ff=(True, True, False), fp=None, excl=75, mask=None, check_depth=(), chunks=1, paths_out=None, run_words_out=None):
     off = O.FlagFilter(*ff)
     ofp = None
     filt = FilterConfig(*ff)
@@ -53,6 +53,8 @@ def compare(b: BamData, ff=(True, True, False), fp=None, excl=75, mask=None, che
         st, summ = s.finish()
         if paths_out is not None:
             paths_out.update(s.last_paths())        # cov_last_paths: which branches of the pipeline this finish took
+        if run_words_out is not None:
+            run_words_out.append(s.run_words())     # cov_copy_run_words: what k_prep made of every record's CIGAR
         hist = s.hist()
         assert summ.num_detected_primary_alignments == prim
         live = exp["seen"] == 1 if mask is None else (exp["seen"] == 1) & (np.asarray(mask) != 0)

@@ -11,30 +11,12 @@ that take the other one.
 import numpy as np
 import pytest
 
-from coverm_amd.engine import RecordBatch
+from tests.cigar_cases import _batch, op
 from tests.test_gpu_abi_parity import compare, to_bamdata
 
 pytestmark = pytest.mark.gpu
 
 FILTER = dict(min_percent_identity_single=0.95, min_aligned_length_single=50, min_aligned_percent_single=0.5)
-
-
-def _batch(tid, pos, cigars, flag=None, nm=None, nm_kind=None, mapq=None, l_seq=None):
-    n = len(tid)
-    lens = np.fromiter((len(c) for c in cigars), dtype=np.int64, count=n)
-    coff = np.zeros(n + 1, dtype=np.uint32)
-    coff[1:] = np.cumsum(lens)
-    cig = np.concatenate([np.asarray(c, dtype=np.uint32) for c in cigars]) if n else np.zeros(0, np.uint32)
-    flag = np.zeros(n, np.uint16) if flag is None else np.asarray(flag, np.uint16)
-    nm = np.ones(n, np.uint32) if nm is None else np.asarray(nm, np.uint32)
-    nm_kind = np.ones(n, np.uint8) if nm_kind is None else np.asarray(nm_kind, np.uint8)
-    mapq = np.full(n, 30, np.uint8) if mapq is None else np.asarray(mapq, np.uint8)
-    l_seq = np.full(n, 100, np.int64) if l_seq is None else np.asarray(l_seq)
-    return RecordBatch.from_arrays(np.asarray(tid, np.int32), np.asarray(pos, np.int32), flag, mapq, nm, nm_kind, l_seq, coff, cig)
-
-
-def op(n, code):
-    return (int(n) << 4) | "MIDNSHP=X".index(code)
 
 
 M100 = [op(100, "M")]
