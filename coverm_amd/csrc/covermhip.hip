@@ -9,6 +9,7 @@
 #include "ingest_kernels.hip.h"
 #include "group_kernels.hip.h"
 #include "sam_kernels.hip.h"
+#include "gene_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -48,6 +49,9 @@ static_assert(sizeof(cov_contig_stats) == 128 && offsetof(cov_contig_stats, sum_
 static_assert(sizeof(cov_ingest_stats) == 56 && offsetof(cov_ingest_stats, max_hop_records) == 32 && offsetof(cov_ingest_stats, repaired_starts) == 48, "cov_ingest_stats layout");
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
+static_assert(sizeof(cov_interval_reads) == 32 && sizeof(cov_interval_reads) == sizeof(covgn::Out) && offsetof(cov_interval_reads, sum_identity) == offsetof(covgn::Out, sum_identity) &&
+              offsetof(cov_interval_reads, contig_taken) == offsetof(covgn::Out, contig_taken) && sizeof(cov_interval) == sizeof(gnrc::Interval) &&
+              offsetof(cov_interval, start) == offsetof(gnrc::Interval, start), "cov_interval_reads mirrors the device struct");
 static_assert(sizeof(cov_genome_stats) == 24 && sizeof(cov_genome_stats) == sizeof(covk::DevGenomeStats) && offsetof(cov_genome_stats, genome_len) == offsetof(covk::DevGenomeStats, genome_len) &&
               offsetof(cov_genome_stats, any_nonzero) == offsetof(covk::DevGenomeStats, any_nonzero), "cov_genome_stats mirrors the device struct");
 static_assert(sizeof(cov_genome_entry) == 24 && offsetof(cov_genome_entry, first_tid) == 8 && offsetof(cov_genome_entry, gid) == 12 && offsetof(cov_genome_entry, n_contigs_seen) == 16 &&
@@ -266,6 +270,11 @@ struct cov_session {
     // per-interval statistics (cov_interval_stats_compute): depth of every target, materialised on demand
     DevBuf<int32_t> d_depth_all; DevBuf<u64> d_depth_off; bool depth_all_valid = false;
     DevBuf<DevInterval> d_iv; DevBuf<DevIntervalStats> d_ivst; DevBuf<unsigned long long> d_ivhist; uint64_t ivhist_total = 0;
+    // per-interval read aggregates (cov_interval_reads_compute, gene_kernels.hip.h): work arrays per record and per taken record, the tiles'
+    // sums, the checkpoints of the identity prefix; sized from the record and interval counts, kept for the next call
+    DevBuf<uint8_t> gr_code; DevBuf<u32> gr_mism, gr_trec, gr_pprim, gr_tids; DevBuf<int32_t> gr_ttid, gr_tpos; DevBuf<double> gr_ident, gr_tident, gr_ck;
+    DevBuf<u64> gr_bcnt, gr_bmism, gr_pmism, gr_glob; DevBuf<gnrc::Interval> gr_iv; DevBuf<covgn::Out> gr_out; DevBuf<covgn::Bounds> gr_bounds;
+    float gene_ms = 0.f; uint32_t gene_launches = 0;      // the last cov_interval_reads_compute (COV_K_GENE_READS)
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
     bool have_mask = false;
@@ -705,6 +714,8 @@ void cov_destroy(cov_session *s) {
     s->d_gout.release(); if (s->h_gout) (void)hipHostFree(s->h_gout); s->h_gout = nullptr;
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
     s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
+    s->gr_code.release(); s->gr_mism.release(); s->gr_trec.release(); s->gr_pprim.release(); s->gr_tids.release(); s->gr_ttid.release(); s->gr_tpos.release(); s->gr_ident.release();
+    s->gr_tident.release(); s->gr_ck.release(); s->gr_bcnt.release(); s->gr_bmism.release(); s->gr_pmism.release(); s->gr_glob.release(); s->gr_iv.release(); s->gr_out.release(); s->gr_bounds.release();
     s->d_cx_list.release(); s->d_cx_cnt.release(); s->d_cx_cur.release(); s->d_cx_scan.release(); s->d_cx_top.release(); s->d_cx_runs.release();
     if (s->side) {     // before ing.aux goes: `side` may be that very stream (stage_identity_side borrows the idle ingest stream)
         (void)hipStreamSynchronize(s->side);
@@ -2853,6 +2864,105 @@ cov_status cov_interval_stats_compute(cov_session *s, const cov_interval *iv, ui
     return COV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- per-interval read aggregates (gene_kernels.hip.h)
+// What covh_gene_coverage's record pass computes from the records on the host, from the store itself: 32 bytes per interval come back.
+cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *iv, uint64_t n, int want_identity, cov_interval_reads *out,
+                                      uint64_t *mapped_total, int *sorted_by_start) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_interval_reads_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_interval_reads_compute: part of the sample's records already left the bounded record store (per-gene coverage needs them all: raise COVERM_STORE_CAP_*)"; return COV_ERR_STATE; }
+    if ((n && (!iv || !out)) || !sorted_by_start) return COV_ERR_INVALID_ARG;
+    for (uint64_t i = 0; i < n; i++)
+        if (iv[i].tid >= s->n_targets || iv[i].start >= iv[i].end || iv[i].end > s->h_tlen[iv[i].tid]) { s->err = "interval outside its target"; return COV_ERR_INVALID_ARG; }
+    covr::Range rr("per-interval read aggregates (cov_interval_reads_compute)");
+    *sorted_by_start = 0;
+    if (mapped_total) *mapped_total = 0;
+    s->gene_ms = 0.f; s->gene_launches = 0;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    const Records r = records_of(s);
+    const u32 R = r.n, nb = (R + covgn::TILE - 1) / covgn::TILE;
+    const bool ident = want_identity != 0;
+    // the contigs with intervals, ascending, and each interval's contig by its number among them (where its checkpoints lie)
+    std::vector<u32> tids(n);
+    for (uint64_t i = 0; i < n; i++) tids[i] = iv[i].tid;
+    std::sort(tids.begin(), tids.end());
+    tids.erase(std::unique(tids.begin(), tids.end()), tids.end());
+    std::vector<gnrc::Interval> hiv(n);
+    for (uint64_t i = 0; i < n; i++) {
+        hiv[i].tid = iv[i].tid; hiv[i].start = iv[i].start; hiv[i].end = iv[i].end;
+        hiv[i].pad = (u32)(std::lower_bound(tids.begin(), tids.end(), iv[i].tid) - tids.begin());
+    }
+    const u32 nC = (u32)tids.size();
+    HIPCHK(s->gr_code.reserve(std::max<size_t>(R, 1), st)); HIPCHK(s->gr_mism.reserve(std::max<size_t>(R, 1), st));
+    HIPCHK(s->gr_bcnt.reserve((size_t)nb + 1, st)); HIPCHK(s->gr_bmism.reserve((size_t)nb + 1, st));
+    HIPCHK(s->gr_ttid.reserve(std::max<size_t>(R, 1), st)); HIPCHK(s->gr_tpos.reserve(std::max<size_t>(R, 1), st)); HIPCHK(s->gr_trec.reserve(std::max<size_t>(R, 1), st));
+    HIPCHK(s->gr_pprim.reserve((size_t)R + 1, st)); HIPCHK(s->gr_pmism.reserve((size_t)R + 1, st)); HIPCHK(s->gr_glob.reserve(covgn::G_COUNT, st));
+    if (ident) { HIPCHK(s->gr_ident.reserve(std::max<size_t>(R, 1), st)); HIPCHK(s->gr_tident.reserve(std::max<size_t>(R, 1), st)); HIPCHK(s->gr_ck.reserve((size_t)gnrc::ck_slots(R, nC), st)); }
+    HIPCHK(s->gr_iv.reserve(std::max<size_t>(n, 1), st)); HIPCHK(s->gr_out.reserve(std::max<size_t>(n, 1), st)); HIPCHK(s->gr_bounds.reserve(std::max<size_t>(n, 1), st));
+    HIPCHK(s->gr_tids.reserve(std::max<size_t>(nC, 1), st));
+    covgn::Work w{};
+    w.code = s->gr_code.p; w.mism = s->gr_mism.p; w.ident = ident ? s->gr_ident.p : nullptr; w.b_cnt = s->gr_bcnt.p; w.b_mism = s->gr_bmism.p;
+    w.t_tid = s->gr_ttid.p; w.t_pos = s->gr_tpos.p; w.t_rec = s->gr_trec.p; w.pprim = s->gr_pprim.p; w.pmism = s->gr_pmism.p;
+    w.t_ident = ident ? s->gr_tident.p : nullptr; w.glob = s->gr_glob.p;
+    const FilterCfg fc = filter_of(s->cfg);
+    gnrc::Filter f{};
+    f.include_improper_pairs = fc.include_improper_pairs; f.include_supplementary = fc.include_supplementary; f.include_secondary = fc.include_secondary;
+    f.filter_single = fc.filter_single; f.min_mapq = fc.min_mapq; f.min_aligned_length = fc.min_aligned_length;
+    f.min_percent_identity = fc.min_percent_identity; f.min_aligned_percent = fc.min_aligned_percent;
+    const u64 glob0[covgn::G_COUNT] = {gnrc::NO_VERDICT, 0, 0, 0};
+    u64 glob[covgn::G_COUNT];
+    hipEvent_t *ev = s->ev[COV_K_GENE_READS];      // events of its own: the call is not part of a finish
+    HIPCHK(hipMemcpyAsync(s->gr_glob.p, glob0, sizeof glob0, hipMemcpyHostToDevice, st));
+    if (n) HIPCHK(hipMemcpyAsync(s->gr_iv.p, hiv.data(), n * sizeof(gnrc::Interval), hipMemcpyHostToDevice, st));
+    if (nC) HIPCHK(hipMemcpyAsync(s->gr_tids.p, tids.data(), (size_t)nC * sizeof(u32), hipMemcpyHostToDevice, st));
+    HIPCHK(hipEventRecord(ev[0], st));
+    if (nb) { hipLaunchKernelGGL(covgn::k_gene_classify, dim3(nb), dim3(256), 0, st, r, f, w); s->gene_launches++; }
+    hipLaunchKernelGGL(covgn::k_gene_offsets, dim3(1), dim3(1024), 0, st, w, nb);
+    if (nb) { hipLaunchKernelGGL(covgn::k_gene_scatter, dim3(nb), dim3(256), 0, st, r, w); s->gene_launches++; }
+    hipLaunchKernelGGL(covgn::k_gene_order, dim3(std::max(1u, std::min(nb, (u32)s->n_cus * 8u))), dim3(256), 0, st, w, s->n_targets);
+    s->gene_launches += 2;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], st));
+    HIPCHK(hipMemcpyAsync(glob, s->gr_glob.p, sizeof glob, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    s->gene_ms = ms; s->ev_fresh = -1;
+    if (glob[covgn::G_VERDICT] != gnrc::NO_VERDICT) {      // the reference's panic at the first offending record in file order
+        switch ((u32)(glob[covgn::G_VERDICT] & 3u)) {
+        case gnrc::RULE_NM_MISSING: s->err = "Mapping record encountered that does not have an 'NM' auxiliary tag in the SAM/BAM format"; return COV_ERR_NM_MISSING;
+        case gnrc::RULE_NM_BADTYPE: s->err = "Unexpected data type of NM aux tag"; return COV_ERR_NM_BADTYPE;
+        case gnrc::RULE_UNSORTED: s->err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)"; return COV_ERR_UNSORTED;
+        default: s->err = "record refers to a reference id outside the header (Corrupt BAM file?)"; return COV_ERR_BAD_TID;
+        }
+    }
+    if (mapped_total) *mapped_total = glob[covgn::G_MAPPED];
+    if (glob[covgn::G_UNSORTED]) return COV_OK;      // lower_bound over unsorted starts is the host loop's own probe sequence: its path
+    *sorted_by_start = 1;
+    if (n == 0) return COV_OK;
+    HIPCHK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(covgn::k_gene_bounds, dim3((u32)std::min<uint64_t>((n + 255) / 256, (uint64_t)s->n_cus * 8)), dim3(256), 0, st, w, (const gnrc::Interval *)s->gr_iv.p, (u64)n, s->gr_out.p, s->gr_bounds.p);
+    s->gene_launches++;
+    if (ident) {
+        if (n >= 0x7fffffffull) { s->err = "cov_interval_reads_compute: more than 2^31 intervals"; return COV_ERR_INVALID_ARG; }
+        hipLaunchKernelGGL(covgn::k_gene_ckpt, dim3(nC), dim3(64), 0, st, w, (const u32 *)s->gr_tids.p, nC, s->gr_ck.p);
+        hipLaunchKernelGGL(covgn::k_gene_ident, dim3((u32)n), dim3(64), 0, st, w, (const covgn::Bounds *)s->gr_bounds.p, (u64)n, (const double *)s->gr_ck.p, s->gr_out.p);
+        s->gene_launches += 2;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], st));
+    HIPCHK(hipMemcpyAsync(out, s->gr_out.p, n * sizeof(cov_interval_reads), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    s->gene_ms += ms;
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] interval reads: %u records, %llu taken, %llu intervals on %u contigs, identity %s; %u launches, %.3f ms\n", R,
+                (unsigned long long)glob[covgn::G_TAKEN], (unsigned long long)n, nC, ident ? "on" : "off", s->gene_launches, s->gene_ms);
+    return COV_OK;
+}
+
 cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist) {
     if (!s || !s->finished) return COV_ERR_STATE;
     if (s->ivhist_total == 0) return COV_OK;
@@ -2868,6 +2978,11 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
     if (k == COV_K_SAM) {        // not part of a finish: the decode kernels of the last cov_sam_* ingest, summed over its windows
         if (ms_total) *ms_total = s->sam_ms;
         if (launches) *launches = s->sam_launches;
+        return COV_OK;
+    }
+    if (k == COV_K_GENE_READS) {      // not part of a finish: the last cov_interval_reads_compute
+        if (ms_total) *ms_total = s->gene_ms;
+        if (launches) *launches = s->gene_launches;
         return COV_OK;
     }
     if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records

@@ -616,8 +616,14 @@ void records_back(cov_session *s, HostRecords &hr, cov_batch &batch) {
     if (n == 0) hr.coff[0] = 0;
 }
 
-// genes.rs:182-344: per-gene reductions over this sample's depth, while the session holds it
-void gene_coverage(Run &R, cov_session *s, Sample &S, const cov_batch &batch) {
+// COVERM_GENE_READS_ON_HOST: behind a device reader the records come back and the gene driver's record pass runs on the host, as it did
+// before cov_interval_reads_compute — the cross-check of the device aggregates
+bool gene_reads_on_host() { static const bool v = getenv("COVERM_GENE_READS_ON_HOST") != nullptr; return v; }
+
+// genes.rs:182-344: per-gene reductions over this sample's depth, while the session holds it.  device_reads: the store holds the sample
+// (a device reader filled it) and the per-read numbers of every gene come from there, 32 bytes per gene; the records come back only
+// when their starts decrease inside a contig (--unsorted) or COVERM_GENE_READS_ON_HOST asks for it.
+void gene_coverage(Run &R, cov_session *s, Sample &S, cov_batch &batch, HostRecords &hr, bool device_reads, bool report) {
     const Args &a = R.a;
     std::lock_guard<std::mutex> lk(R.taker_mutex);
     const covh_header gh = S.header();
@@ -630,7 +636,32 @@ void gene_coverage(Run &R, cov_session *s, Sample &S, const cov_batch &batch) {
         nm.genome_of_tid = S.genome_of_tid.data(); nm.genome_names = gn.data();
     }
     auto depth_cb = [](void *ctx, uint32_t tid, int32_t *out) -> int { return (int)cov_copy_depth((cov_session *)ctx, tid, out); };
-    const int grc = covh_gene_coverage(&gh, R.genes, &nm, S.stoit.c_str(), &batch, &R.cfg, getenv("COVERM_GENES_ON_HOST") ? nullptr : s, depth_cb, s,
+    cov_session *const reductions = getenv("COVERM_GENES_ON_HOST") ? nullptr : s;
+    if (device_reads) {
+        const char *why = "COVERM_GENE_READS_ON_HOST";
+        if (!gene_reads_on_host()) {
+            int sorted = 0;
+            const int grc = covh_gene_coverage_reads(&gh, R.genes, &nm, S.stoit.c_str(), covh_session_interval_reads, s, reductions, depth_cb, s, S.prim, R.taker,
+                                                     R.est.data(), R.est.size(), !a.no_zeros, &S.gene_rm, &sorted);
+            if (grc == COV_ERR_HIP || grc == COV_ERR_STATE) die(cov_last_error(s));
+            if (grc == COV_ERR_NM_MISSING || grc == COV_ERR_NM_BADTYPE) die(cov_last_error(s));
+            if (grc != COV_OK) die(covh_last_error());
+            if (sorted) {
+                if (report) {
+                    double ms = 0; uint32_t launches = 0;
+                    (void)cov_kernel_ms(s, COV_K_GENE_READS, &ms, &launches);
+                    fprintf(stderr, "[coverm-amd] %s: --gff over the device ingest: per-gene read aggregates on the device (%zu genes, %.3f kernels ms)\n", S.stoit.c_str(),
+                            covh_genes_count(R.genes), ms);
+                }
+                return;
+            }
+            why = "starts decrease inside a reference";      // nothing was written: the record pass takes the sample
+        }
+        records_back(s, hr, batch);
+        if (report)
+            fprintf(stderr, "[coverm-amd] %s: --gff over the device ingest: %llu records came back from the store (%s)\n", S.stoit.c_str(), (unsigned long long)batch.n_records, why);
+    }
+    const int grc = covh_gene_coverage(&gh, R.genes, &nm, S.stoit.c_str(), &batch, &R.cfg, reductions, depth_cb, s,
                                        S.prim, R.taker, R.est.data(), R.est.size(), !a.no_zeros, &S.gene_rm);
     if (grc == COV_ERR_HIP || grc == COV_ERR_STATE) die(cov_last_error(s));
     if (grc != COV_OK) die(covh_last_error());
@@ -691,18 +722,13 @@ void ingest(Run &R, cov_session *s, Sample &S, int threads, uint32_t span_index,
     if (d.route == Route::DeviceBgzf || d.route == Route::DeviceSam) {
         S.n_records = fed.nrec; S.device_ingest = true;
         if (timing_on()) report_device_reader(s, S, d.route, fed, span_index, span_count);
-        if (R.per_gene) {
-            records_back(s, hr, batch);
-            if (timing_on() && d.route == Route::DeviceBgzf)
-                fprintf(stderr, "[coverm-amd] %s: --gff over the device ingest: %llu records came back from the store\n", S.stoit.c_str(), (unsigned long long)batch.n_records);
-        }
     }
     S.t_ingest = now() - t0;
     cov_summary summ;
     finish_sample(R, s, S, summ);
     fetch_results(R, s, S, summ);
     S.prim = fed.have_prim ? fed.prim : summ.num_detected_primary_alignments;
-    if (R.per_gene) gene_coverage(R, s, S, batch);
+    if (R.per_gene) gene_coverage(R, s, S, batch, hr, S.device_ingest, timing_on());
     S.t_finish = now() - t0 - S.t_ingest;
 }
 

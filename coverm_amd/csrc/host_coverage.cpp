@@ -1307,11 +1307,17 @@ void covh_genes_get(const covh_genes *g, size_t i, const char **id, const char *
 }
 void covh_genes_free(covh_genes *g) { delete g; }
 
-int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh_genome_namer *namer, const char *stoit_name,
-                       const cov_batch *rec, const cov_config *cfg, cov_session *device_session, covh_depth_fn depth_fn,
-                       void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
-                       size_t n_est, int print_zero, covh_reads_mapped *rm_out) {
-    if (!h || !genes || !rec || !cfg || (!depth_fn && !device_session) || !taker || (!est && n_est)) return COV_ERR_INVALID_ARG;
+}  // extern "C"
+
+// The gene driver, one body for its two sources of the per-read numbers (n_reads / mismatches / sum_identity / "the scan saw this contig"):
+// `rec` — the record pass below, over the sample's records on the host; or `reads_fn` — one cov_interval_reads per resolved gene, in
+// entry order, from whoever holds the records (cov_interval_reads_compute in the product).
+static int gene_coverage_body(const covh_header *h, const covh_genes *genes, const covh_genome_namer *namer, const char *stoit_name,
+                              const cov_batch *rec, const cov_config *cfg, covh_interval_reads_fn reads_fn, void *reads_ctx, int *sorted_by_start,
+                              cov_session *device_session, covh_depth_fn depth_fn,
+                              void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
+                              size_t n_est, int print_zero, covh_reads_mapped *rm_out) {
+    if (!h || !genes || (!rec && !reads_fn) || (rec && !cfg) || (!depth_fn && !device_session) || !taker || (!est && n_est)) return COV_ERR_INVALID_ARG;
     if (!check_excl(est, n_est)) { g_err = "estimators disagree on contig_end_exclusion"; return COV_ERR_INVALID_ARG; }
     const u64 excl = session_excl(est, n_est);
     const u64 zero = 0;
@@ -1355,10 +1361,28 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
     // ---- device path: every resolved gene is one interval, reduced on the GPU over the materialised depth
     std::vector<cov_interval_stats> dstats;
     std::vector<uint64_t> dhist;
-    if (device_session) {
-        std::vector<cov_interval> ivs;
+    std::vector<cov_interval> ivs;      // in entry order: ivs[g.entry_id] is gene g
+    if (device_session || reads_fn)
         for (u32 t = 0; t < nT; t++)
             for (const ResolvedGene &g : by_tid[t]) { cov_interval iv; iv.tid = t; iv.pad = 0; iv.start = g.start; iv.end = g.end; ivs.push_back(iv); }
+    // ---- the per-read numbers of every gene from the holder of the records.  Its verdicts are the record pass's own (the first offending
+    // record in file order), returned before anything is written; starts that decrease inside a contig leave the work to the record pass.
+    std::vector<cov_interval_reads> reads;
+    u64 reads_mapped_total = 0;
+    if (reads_fn) {
+        bool want_identity = false;
+        for (size_t k = 0; k < n_est; k++) want_identity |= est[k].kind == COVH_ANIR;
+        reads.resize(ivs.size());
+        int sorted = 0;
+        const int rc = reads_fn(reads_ctx, ivs.data(), ivs.size(), want_identity ? 1 : 0, reads.data(), &reads_mapped_total, &sorted);
+        if (rc == COV_ERR_UNSORTED) g_err = "BAM file appears to be unsorted. Input BAM files must be sorted by reference (i.e. by samtools sort)";
+        else if (rc == COV_ERR_BAD_TID) g_err = "record refers to a reference id outside the header (Corrupt BAM file?)";
+        else if (rc != COV_OK && rc != COV_ERR_NM_MISSING && rc != COV_ERR_NM_BADTYPE) g_err = "per-gene read aggregates failed";      // (the record pass leaves the text alone for the NM errors)
+        if (rc != COV_OK) return rc;
+        if (sorted_by_start) *sorted_by_start = sorted;
+        if (!sorted) return COV_OK;
+    }
+    if (device_session) {
         bool want_hist = false;
         for (size_t k = 0; k < n_est; k++) want_hist |= est[k].kind == COVH_TRIMMED_MEAN || est[k].kind == COVH_PILEUP_COUNTS;
         dstats.resize(ivs.size());
@@ -1421,11 +1445,16 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
                 for (u64 p = s + excl; p < e - excl; p++) acc.hist[(u32)depth[p]]++;
             }
             }
+            if (reads_fn) {
+                const cov_interval_reads &Rd = reads[g.entry_id];
+                acc.n_reads = Rd.n_reads; acc.mismatches = Rd.mismatches; acc.sum_identity = Rd.sum_identity;
+            } else {
             const size_t lo = std::lower_bound(starts.begin(), starts.end(), s) - starts.begin();
             const size_t hi = std::lower_bound(starts.begin(), starts.end(), e) - starts.begin();
             acc.n_reads = pprim[hi] - pprim[lo];
             acc.mismatches = pmism[hi] - pmism[lo];
             acc.sum_identity = pident[hi] - pident[lo];       // difference of the running f64 prefix sums, as :526 does
+            }
             bool nonzero = false;
             for (size_t k = 0; k < n_est; k++) { cov[k] = calculate(est[k], acc, &zero, 1); nonzero |= cov[k] > 0.0f; }
             if (print_zero || nonzero) {
@@ -1439,6 +1468,20 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
         if (last != -2) emit((u32)last);
         if (print_zero) for (int64_t t = last == -2 ? 0 : last + 1; t < cur; t++) zero_genes((u32)t);
     };
+
+    if (reads_fn) {
+        // The record pass below calls previous() at every contig it sees, in tid order, and once behind the last: a contig with genes is
+        // emitted when the scan saw it (contig_taken > 0, the same for all of its genes) and is a zero row otherwise; contigs without
+        // genes write nothing either way.
+        for (u32 t = 0; t < nT; t++) {
+            if (by_tid[t].empty()) continue;
+            if (reads[by_tid[t][0].entry_id].contig_taken > 0) emit(t);
+            else if (print_zero) zero_genes(t);
+            if (rc_err) return rc_err;
+        }
+        if (rm_out) { rm_out->num_mapped_reads = reads_mapped_total; rm_out->num_reads = num_detected_primary_alignments; }
+        return COV_OK;
+    }
 
     int64_t last_tid = -2;
     u64 mapped_total = 0;
@@ -1525,6 +1568,32 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
     if (rc_err) return rc_err;
     if (rm_out) { rm_out->num_mapped_reads = mapped_total; rm_out->num_reads = num_detected_primary_alignments; }
     return COV_OK;
+}
+
+extern "C" {
+
+int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh_genome_namer *namer, const char *stoit_name,
+                       const cov_batch *rec, const cov_config *cfg, cov_session *device_session, covh_depth_fn depth_fn,
+                       void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
+                       size_t n_est, int print_zero, covh_reads_mapped *rm_out) {
+    if (!rec || !cfg) return COV_ERR_INVALID_ARG;
+    return gene_coverage_body(h, genes, namer, stoit_name, rec, cfg, nullptr, nullptr, nullptr, device_session, depth_fn, depth_ctx, num_detected_primary_alignments, taker, est,
+                              n_est, print_zero, rm_out);
+}
+
+int covh_gene_coverage_reads(const covh_header *h, const covh_genes *genes, const covh_genome_namer *namer, const char *stoit_name,
+                             covh_interval_reads_fn reads, void *reads_ctx, cov_session *device_session, covh_depth_fn depth_fn,
+                             void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
+                             size_t n_est, int print_zero, covh_reads_mapped *rm_out, int *sorted_by_start) {
+    if (!reads || !sorted_by_start) return COV_ERR_INVALID_ARG;
+    *sorted_by_start = 0;
+    return gene_coverage_body(h, genes, namer, stoit_name, nullptr, nullptr, reads, reads_ctx, sorted_by_start, device_session, depth_fn, depth_ctx, num_detected_primary_alignments,
+                              taker, est, n_est, print_zero, rm_out);
+}
+
+// covh_interval_reads_fn over a session: cov_interval_reads_compute (ctx = the cov_session holding the sample's records)
+int covh_session_interval_reads(void *ctx, const cov_interval *iv, uint64_t n, int want_identity, cov_interval_reads *out, uint64_t *mapped_total, int *sorted_by_start) {
+    return (int)cov_interval_reads_compute((cov_session *)ctx, iv, n, want_identity, out, mapped_total, sorted_by_start);
 }
 
 }  // extern "C"

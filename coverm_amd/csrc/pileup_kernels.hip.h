@@ -1239,6 +1239,37 @@ __device__ __forceinline__ bool id_fast_add(double &S, int e, u64 T) {
     return true;
 }
 
+// Exact in-order addition of 64 values (lane order) to S.  While S stays in one binade every addition is an
+// integer addition of round(x/ulp) to the mantissa, so a wave prefix sum applies all values up to the first one
+// that leaves the binade, is an exact rounding tie, or is not in [0, 1]; that one value takes a true f64 add (the
+// reference's own operation) and the rest continue in the new binade.  Replaces a 64-step dependent add chain.
+// One body for k_id_combine and the per-gene sums of gene_kernels.hip.h; the whole wave calls it, S is wave-uniform.
+__device__ __forceinline__ void id_block_add(double &S, const double xv, const int lane) {
+    const bool irregular = !(xv >= 0.0 && xv <= 1.0);
+    u32 q = 0;
+    while (q < 64u) {
+        const u64 bits = (u64)__double_as_longlong(S);
+        const int e_cur = (int)((bits >> 52) & 0x7ff) - 1023;
+        if (e_cur < 1 || (bits >> 63)) { S += bcast_f64(xv, (int)q); q++; continue; }   // |S| < 2 or S < 0 (negative identities: NM > aligned): plain adds
+        const u64 m = (bits & 0xfffffffffffffull) | (1ull << 52);
+        bool tie = false;
+        const u64 t = irregular ? 0ull : id_units(xv, e_cur, tie);        // <= 2^52 for x <= 1, e >= 1
+        const bool in_range = (u32)lane >= q;
+        u64 P = in_range ? t : 0ull;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const u64 u = __shfl_up(P, o); if (lane >= o) P += u; }
+        const bool fits = in_range && !tie && !irregular && m + P < (1ull << 53);
+        const u64 failm = __ballot(in_range && !fits);
+        const u32 jstar = failm ? (u32)(__ffsll((long long)failm) - 1) : 64u;
+        if (jstar > q) {
+            const u64 T = bcast_u64(P, (int)(jstar - 1));
+            S = __longlong_as_double((long long)((bits & 0xfff0000000000000ull) | ((m + T) & 0xfffffffffffffull)));
+        }
+        if (jstar < 64u) S += bcast_f64(xv, (int)jstar);
+        q = jstar + 1;
+    }
+}
+
 __global__ __launch_bounds__(64) void k_id_combine(DevContig *ctg, u32 n_targets, const double *__restrict__ identp,
                                                    const double *__restrict__ identn, const int32_t *__restrict__ tidv,
                                                    const IdChunk *__restrict__ ch) {
@@ -1250,35 +1281,7 @@ __global__ __launch_bounds__(64) void k_id_combine(DevContig *ctg, u32 n_targets
     const bool generic = C->n_groups != 1u;
     const int lane = lane_id();
     double Sp = 0.0, Sn = 0.0;
-    // Exact in-order addition of 64 values (lane order) to S.  While S stays in one binade every addition is an
-    // integer addition of round(x/ulp) to the mantissa, so a wave prefix sum applies all values up to the first one
-    // that leaves the binade, is an exact rounding tie, or is not in [0, 1]; that one value takes a true f64 add (the
-    // reference's own operation) and the rest continue in the new binade.  Replaces a 64-step dependent add chain.
-    auto block_add = [&](double &S, const double xv) {
-        const bool irregular = !(xv >= 0.0 && xv <= 1.0);
-        u32 q = 0;
-        while (q < 64u) {
-            const u64 bits = (u64)__double_as_longlong(S);
-            const int e_cur = (int)((bits >> 52) & 0x7ff) - 1023;
-            if (e_cur < 1 || (bits >> 63)) { S += bcast_f64(xv, (int)q); q++; continue; }   // |S| < 2 or S < 0 (negative identities: NM > aligned): plain adds
-            const u64 m = (bits & 0xfffffffffffffull) | (1ull << 52);
-            bool tie = false;
-            const u64 t = irregular ? 0ull : id_units(xv, e_cur, tie);        // <= 2^52 for x <= 1, e >= 1
-            const bool in_range = (u32)lane >= q;
-            u64 P = in_range ? t : 0ull;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const u64 u = __shfl_up(P, o); if (lane >= o) P += u; }
-            const bool fits = in_range && !tie && !irregular && m + P < (1ull << 53);
-            const u64 failm = __ballot(in_range && !fits);
-            const u32 jstar = failm ? (u32)(__ffsll((long long)failm) - 1) : 64u;
-            if (jstar > q) {
-                const u64 T = bcast_u64(P, (int)(jstar - 1));
-                S = __longlong_as_double((long long)((bits & 0xfff0000000000000ull) | ((m + T) & 0xfffffffffffffull)));
-            }
-            if (jstar < 64u) S += bcast_f64(xv, (int)jstar);
-            q = jstar + 1;
-        }
-    };
+    auto block_add = [&](double &S, const double xv) { id_block_add(S, xv, lane); };
     auto serial = [&](u32 from, u32 to, bool need_p, bool need_n) {   // the reference's serial chain over [from, to)
         auto fetch = [&](u32 b, double &xp, double &xn) {
             const u32 i = b + (u32)lane;

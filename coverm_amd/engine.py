@@ -282,6 +282,28 @@ class Session:
         self._check(self._lib.cov_kernel_ms(self._h, native.K_GROUP, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def interval_reads(self, intervals, want_identity=False):
+        """cov_interval_reads_compute: the per-gene read aggregates of --gff from the session's own record store (before or after finish).
+        `intervals`: (tid, start, end) triples, 0-based half-open.  Returns (reads, mapped_total, sorted_by_start): `reads` a
+        native.INTERVAL_READS_DTYPE array (n_reads, mismatches, sum_identity, contig_taken), or None when sorted_by_start is False (a start
+        decreases inside a reference: nothing was computed, the host's record pass takes such a sample).  Raises CovError with the
+        reference's own verdicts (COV_ERR_NM_* / COV_ERR_UNSORTED / COV_ERR_BAD_TID) and COV_ERR_STATE after a spill."""
+        iv = np.zeros(len(intervals), dtype=native.INTERVAL_DTYPE)
+        for k, (t, a, b) in enumerate(intervals):
+            iv[k] = (t, 0, a, b)
+        out = np.zeros(len(iv), dtype=native.INTERVAL_READS_DTYPE)
+        mapped, srt = C.c_uint64(0), C.c_int(0)
+        self._check(self._lib.cov_interval_reads_compute(self._h, iv.ctypes.data if len(iv) else None, C.c_uint64(len(iv)), C.c_int(1 if want_identity else 0),
+                                                         out.ctypes.data if len(iv) else None, C.byref(mapped), C.byref(srt)))
+        return (out if srt.value else None), int(mapped.value), bool(srt.value)
+
+    def gene_reads_kernel_ms(self):
+        """(ms, launches) of the kernels of the last interval_reads (COV_K_GENE_READS)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_GENE_READS, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def sam_ingest(self, path_or_fileobj, mates=False, group=False):
         """SAM text decoded on the device into this session's store (cov_sam_*): a path, "-" for standard input, or an object with fileno().
         Sets the targets from the @SQ lines; returns (ref_names, ref_lens, n_records, timing dict) — see coverm_amd.bam.sam_ingest."""

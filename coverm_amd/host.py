@@ -559,6 +559,77 @@ def gene_coverage(names, target_len, genes: Genes, stoit_name: str, records, cfg
     return ReadsMapped(int(rm.num_mapped_reads), int(rm.num_reads))
 
 
+_READS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_int))
+
+
+def gene_coverage_reads(names, target_len, genes: Genes, stoit_name: str, reads_of, depth_of, num_detected_primary: int,
+                        coverage_taker: CoverageTaker, coverage_estimators, print_zero_coverage_genes: bool,
+                        namer_mode: int = 0, separator: str = "~", genome_of_tid=None, genome_names=None, session=None, reads_session=None):
+    """covh_gene_coverage_reads: gene_coverage with the per-read numbers of every gene in place of the records.  `reads_of(intervals,
+    want_identity)` gets the resolved genes as a native.INTERVAL_DTYPE array (entry order) and returns (status, reads, mapped_total,
+    sorted_by_start) with `reads` a native.INTERVAL_READS_DTYPE array (engine.Session.interval_reads' numbers); reads_of = None asks
+    `reads_session` (default: `session`) itself (cov_interval_reads_compute).  Returns (ReadsMapped, sorted_by_start); sorted_by_start False: nothing was written."""
+    from .native import INTERVAL_DTYPE, INTERVAL_READS_DTYPE
+    L = _lib()
+    h, k1 = _header(names, target_len)
+    errs = []
+
+    def _depth(ctx, tid, out):
+        try:
+            d = np.ascontiguousarray(depth_of(int(tid)), dtype=np.int32)
+            C.memmove(out, d.ctypes.data, d.nbytes)
+            return 0
+        except Exception as e:   # reported by the caller
+            errs.append(e)
+            return 18
+
+    def _reads(ctx, iv, n, want_identity, out, mapped_total, sorted_by_start):
+        try:
+            ivs = np.frombuffer(C.string_at(iv, int(n) * INTERVAL_DTYPE.itemsize), dtype=INTERVAL_DTYPE) if n else np.zeros(0, INTERVAL_DTYPE)
+            st, reads, mapped, srt = reads_of(ivs, bool(want_identity))
+            if st:
+                return int(st)
+            mapped_total[0] = int(mapped)
+            sorted_by_start[0] = 1 if srt else 0
+            if srt and n:
+                r = np.ascontiguousarray(reads, dtype=INTERVAL_READS_DTYPE)
+                assert len(r) == n
+                C.memmove(out, r.ctypes.data, r.nbytes)
+            return 0
+        except Exception as e:
+            errs.append(e)
+            return 18
+    cbk = _DEPTH_FN(_depth)
+    nm = _GenomeNamer()
+    nm.mode = namer_mode
+    nm.separator = ord(separator) if separator else 0
+    keep = None
+    if namer_mode == 3:
+        g = np.ascontiguousarray(genome_of_tid, dtype=np.int32)
+        gn = (C.c_char_p * max(1, len(genome_names)))(*[x.encode() for x in genome_names])
+        nm.genome_of_tid = g.ctypes.data
+        nm.genome_names = gn
+        keep = (g, gn)
+    rm = _ReadsMapped()
+    srt = C.c_int(0)
+    if reads_of is None:
+        rfn, rctx = C.cast(L.covh_session_interval_reads, _READS_FN), (reads_session or session)._h
+    else:
+        rfn, rctx = _READS_FN(_reads), None
+    L.covh_gene_coverage_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, _READS_FN, C.c_void_p, C.c_void_p, _DEPTH_FN,
+                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    rc = L.covh_gene_coverage_reads(C.byref(h), genes._h, C.byref(nm), stoit_name.encode(), rfn, rctx,
+                                    session._h if session is not None else None, cbk, None,
+                                    int(num_detected_primary), coverage_taker._h, _est_array(coverage_estimators),
+                                    len(coverage_estimators), int(print_zero_coverage_genes), C.byref(rm), C.byref(srt))
+    del keep
+    if errs:
+        raise errs[0]
+    if rc:
+        raise HostError(rc, _lib().covh_last_error().decode())
+    return ReadsMapped(int(rm.num_mapped_reads), int(rm.num_reads)), bool(srt.value)
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # Genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; genome_parsing.rs:10-70) through
 # covh_genome_fasta_paths and covh_genome_set_*.

@@ -333,6 +333,21 @@ int covh_gene_coverage(const covh_header *h, const covh_genes *genes, const covh
                        const cov_batch *records, const cov_config *cfg, cov_session *device_session, covh_depth_fn depth,
                        void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
                        size_t n_est, int print_zero_coverage_genes, covh_reads_mapped *reads_mapped_out);
+/* The same scan with the per-read numbers of every gene from whoever holds the records, in place of the records: `reads` is called once,
+ * before anything is written, with every resolved gene as an interval (tid ascending, inside a tid by start: the order of the entries) and
+ * fills one cov_interval_reads per interval, *mapped_total and *sorted_by_start as cov_interval_reads_compute does — which is what the
+ * product passes (covh_session_interval_reads, ctx = the session).  Its status is returned as it is (COV_ERR_NM_* / COV_ERR_UNSORTED /
+ * COV_ERR_BAD_TID with covh_gene_coverage's texts).  *sorted_by_start = 0 on return: starts decrease inside a contig, NOTHING was written to
+ * the taker and COV_OK is returned: run covh_gene_coverage over the records.  Contigs are emitted in tid order, those with
+ * contig_taken > 0 as the scan emits a contig it saw, the others as zero rows.  Everything else as covh_gene_coverage. */
+typedef int (*covh_interval_reads_fn)(void *ctx, const cov_interval *intervals, uint64_t n, int want_identity, cov_interval_reads *out,
+                                      uint64_t *mapped_total, int *sorted_by_start);
+int covh_gene_coverage_reads(const covh_header *h, const covh_genes *genes, const covh_genome_namer *namer, const char *stoit_name,
+                             covh_interval_reads_fn reads, void *reads_ctx, cov_session *device_session, covh_depth_fn depth,
+                             void *depth_ctx, uint64_t num_detected_primary_alignments, covh_taker *taker, const covh_estimator *est,
+                             size_t n_est, int print_zero_coverage_genes, covh_reads_mapped *reads_mapped_out, int *sorted_by_start);
+int covh_session_interval_reads(void *ctx, const cov_interval *intervals, uint64_t n, int want_identity, cov_interval_reads *out,
+                                uint64_t *mapped_total, int *sorted_by_start);
 
 /* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
  * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.

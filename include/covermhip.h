@@ -153,7 +153,8 @@ typedef enum {
     COV_K_GROUP = 8,    /* cov_group_records: order check, sort passes and gather of the last call, summed (not part of a finish) */
     COV_K_SAM = 9,      /* cov_sam_*: the decode kernels of the last SAM text ingest, summed over its windows (not part of a finish) */
     COV_K_SEP = 10,     /* cov_set_genome_runs: the table entry -> targets of the finish (scans, compaction, segments), in front of COV_K_GENOME */
-    COV_K_COUNT = 11
+    COV_K_GENE_READS = 11, /* cov_interval_reads_compute: the kernels of the last call, summed (not part of a finish) */
+    COV_K_COUNT = 12
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -445,7 +446,7 @@ cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
  * the host, the records from the first considered record of the contig in flight onwards move to the front of the store and the call
  * goes on ("a spill"); cov_finish / cov_fetch_hist / cov_gather then return the whole sample (record indices count from the sample's first
  * record).  What remains: ONE reference's records must fit (2^32 - 16 records and CIGAR words); after a spill cov_copy_depth,
- * cov_interval_stats_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
+ * cov_interval_stats_compute, cov_interval_reads_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
  * that has to hand its file to the CPU reader fails with COV_ERR_STATE instead of COV_ERR_INGEST_FALLBACK; a store that carries mate
  * columns (cov_ingest_want_mates) or an adopted device batch is never spilled.  cov_store_spills: spills since the last cov_reset. */
 uint32_t cov_store_spills(const cov_session *s);
@@ -465,6 +466,24 @@ typedef struct {
 cov_status cov_interval_stats_compute(cov_session *s, const cov_interval *intervals, uint64_t n, uint64_t contig_end_exclusion,
                                       int want_hist, cov_interval_stats *out, uint64_t *hist_total);
 cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist);
+
+/* ---- per-interval read aggregates (per-gene coverage, the reference's src/genes.rs:206-304, 493-524): what the gene scan keeps per read
+ * — num_mapped_reads, mismatches = NM.saturating_sub(I + D) and the identity of the reads whose leftmost position lies inside the interval
+ * — computed from the session's own record store; 32 bytes per interval come back and no record.  Callable while the store holds the
+ * sample, before or after cov_finish.  The records pass cov_config's filter as covh_gene_coverage applies it (the single-read reader stage
+ * when filter_single, the flag filter, mapped, NM present); the target mask does not apply (the reference's gene scan has none).
+ *   n_reads       primary records among them               mismatches    sum of NM.saturating_sub(I + D)
+ *   sum_identity  P[hi] - P[lo], P the serial f64 running sum of the primary reads' (aligned - NM) / aligned from the first record of the
+ *                 interval's target on (genes.rs:500-526; replayed in file order, bit for bit); 0 unless want_identity
+ *   contig_taken  records of the interval's target that passed: 0 = the scan never saw that target
+ * *mapped_total = the primary records that passed, over the whole store (ReadsMapped.num_mapped_reads).
+ * *sorted_by_start = 0: some start decreases inside a target (a file grouped by reference but not sorted); `out` was NOT written — the
+ * reference's partition_point over such starts depends on its probe sequence, run covh_gene_coverage over cov_copy_records then.
+ * COV_ERR_NM_MISSING / COV_ERR_NM_BADTYPE / COV_ERR_UNSORTED / COV_ERR_BAD_TID for the first offending record in file order, as the host
+ * scan reports them; COV_ERR_STATE after a spill of the bounded record store; COV_ERR_INVALID_ARG for an interval outside its target. */
+typedef struct { uint64_t n_reads, mismatches; double sum_identity; uint64_t contig_taken; } cov_interval_reads; /* 32 B */
+cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *intervals, uint64_t n, int want_identity,
+                                      cov_interval_reads *out, uint64_t *mapped_total, int *sorted_by_start);
 
 /* Page-locked host memory for record batches, pooled: a freed block is kept for the next request of similar size
  * (a decoder filling one batch per BAM file gets its arrays back without re-pinning).  cov_host_alloc returns NULL
