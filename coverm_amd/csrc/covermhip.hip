@@ -10,6 +10,7 @@
 #include "group_kernels.hip.h"
 #include "sam_kernels.hip.h"
 #include "gene_kernels.hip.h"
+#include "depth_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -49,6 +50,7 @@ static_assert(sizeof(cov_contig_stats) == 128 && offsetof(cov_contig_stats, sum_
 static_assert(sizeof(cov_ingest_stats) == 56 && offsetof(cov_ingest_stats, max_hop_records) == 32 && offsetof(cov_ingest_stats, repaired_starts) == 48, "cov_ingest_stats layout");
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
+static_assert(sizeof(cov_depth_run) == 8 && offsetof(cov_depth_run, depth) == 4 && sizeof(cov_depth_runs_info) == 40 && offsetof(cov_depth_runs_info, tid_lo) == 32, "depth run struct layout");
 static_assert(sizeof(cov_interval_reads) == 32 && sizeof(cov_interval_reads) == sizeof(covgn::Out) && offsetof(cov_interval_reads, sum_identity) == offsetof(covgn::Out, sum_identity) &&
               offsetof(cov_interval_reads, contig_taken) == offsetof(covgn::Out, contig_taken) && sizeof(cov_interval) == sizeof(gnrc::Interval) &&
               offsetof(cov_interval, start) == offsetof(gnrc::Interval, start), "cov_interval_reads mirrors the device struct");
@@ -275,6 +277,19 @@ struct cov_session {
     DevBuf<uint8_t> gr_code; DevBuf<u32> gr_mism, gr_trec, gr_pprim, gr_tids; DevBuf<int32_t> gr_ttid, gr_tpos; DevBuf<double> gr_ident, gr_tident, gr_ck;
     DevBuf<u64> gr_bcnt, gr_bmism, gr_pmism, gr_glob; DevBuf<gnrc::Interval> gr_iv; DevBuf<covgn::Out> gr_out; DevBuf<covgn::Bounds> gr_bounds;
     float gene_ms = 0.f; uint32_t gene_launches = 0;      // the last cov_interval_reads_compute (COV_K_GENE_READS)
+    // depth runs (cov_depth_runs_compute / _fetch, depth_kernels.hip.h): ONE chunk of whole targets at a time — its arena, start mask and
+    // rank, the scan's block sums, the runs and the targets' run offsets; kept for the next chunk
+    struct DepthRuns {
+        DevBuf<int32_t> arena; DevBuf<u32> woff, mask, rank, sums, run_off; DevBuf<u64> doff, total; DevBuf<dprc::Run> runs;
+        std::vector<u32> h_woff, h_run_off;
+        u64 chunk_bases = dprc::DEFAULT_CHUNK_BASES;      // COVERM_KNOBS depth_chunk_bases (tests: many chunks)
+        bool valid = false;                               // a chunk's runs are on the device: [lo, next), n_runs of them
+        u32 lo = 0, next = 0, launches = 0;
+        u64 n_runs = 0, arena_bases = 0;
+        hipEvent_t ev_mid = nullptr;
+        float arena_ms = 0.f, runs_ms = 0.f;              // of the last chunk: the pileup into the arena; the run kernels (COV_K_DEPTH_RUNS)
+        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
+    } dr;
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
     bool have_mask = false;
@@ -682,6 +697,7 @@ cov_status cov_create(const cov_config *cfg, cov_session **out) {
     { long long v; if (covknob::get("store_cap_records", v) && v >= 1) s->cap_records = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
     { long long v; if (covknob::get("store_cap_cigar", v) && v >= 1) s->cap_cigar = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
     { long long v; if (covknob::get("pileup_chunk_tiles", v) && v >= 1 && v <= 64) s->chunk_tiles = (int)v; }
+    { long long v; if (covknob::get("depth_chunk_bases", v) && v >= 4) s->dr.chunk_bases = (uint64_t)v; }
     // (every stream costs ~6 ms to create and as much again when the process ends, tools/ubench/exit_probe: the side stream of the
     // identity kernels is created by the first cov_finish that wants it, and borrows the ingest's second stream when there is one)
     e = hipEventCreateWithFlags(&s->ev_prep_done, hipEventDisableTiming);
@@ -713,7 +729,7 @@ void cov_destroy(cov_session *s) {
     s->d_stop_cnt.release(); s->d_stop_seg.release(); s->d_sent.release();
     s->d_gout.release(); if (s->h_gout) (void)hipHostFree(s->h_gout); s->h_gout = nullptr;
     s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
-    s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
+    s->dr.release(); s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
     s->gr_code.release(); s->gr_mism.release(); s->gr_trec.release(); s->gr_pprim.release(); s->gr_tids.release(); s->gr_ttid.release(); s->gr_tpos.release(); s->gr_ident.release();
     s->gr_tident.release(); s->gr_ck.release(); s->gr_bcnt.release(); s->gr_bmism.release(); s->gr_pmism.release(); s->gr_glob.release(); s->gr_iv.release(); s->gr_out.release(); s->gr_bounds.release();
     s->d_cx_list.release(); s->d_cx_cnt.release(); s->d_cx_cur.release(); s->d_cx_scan.release(); s->d_cx_top.release(); s->d_cx_runs.release();
@@ -973,7 +989,7 @@ cov_status cov_reset(cov_session *s) {
         if (a != COV_OK && !(spilled && a == COV_ERR_STATE)) return a;
         if (a != COV_OK) s->err.clear();
     }
-    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->store.mates_valid = 0; s->ing.was_span = false;
+    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->dr.valid = false; s->store.mates_valid = 0; s->ing.was_span = false;
     s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing.rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
@@ -1184,7 +1200,7 @@ static PrepArgs prep_args_of(const cov_session *s, const FinishPlan &p, const Pa
 
 // Stage 1: the session's state of a pass, the buffers sized by the records, the views, k_init.
 static cov_status stage_begin(cov_session *s, const FinishPlan &p, PassViews &v) {
-    s->depth_all_valid = false;
+    s->depth_all_valid = false; s->dr.valid = false;
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
@@ -1590,7 +1606,7 @@ static cov_status spill_store(cov_session *s, bool &progress) {
     }
     HIPCHK(hipStreamSynchronize(q));
     s->store.n_records = n_keep; s->store.n_cigar = cig_keep;
-    s->finished = false; s->depth_all_valid = false;
+    s->finished = false; s->depth_all_valid = false; s->dr.valid = false;
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] bounded store: spill %u, %llu records left the store (%llu stay: contig %lld in flight), %llu since the sample began\n", S.count,
                 (unsigned long long)keep_from, (unsigned long long)n_keep, (long long)cstar, (unsigned long long)S.records);
@@ -2473,7 +2489,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     const u32 R = (u32)s->store.n_records;
     if (n_selected) *n_selected = 0;
     if (n_primary) *n_primary = 0;
-    s->finished = false; s->depth_all_valid = false;
+    s->finished = false; s->depth_all_valid = false; s->dr.valid = false;
     if (R == 0) return COV_OK;
     covp::PairCols C{};
     s->store.view_unplaced(C); s->store.view_mates(C);
@@ -2691,7 +2707,7 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
         fprintf(stderr, "[covermhip] group: %u records, %u passes, %llu moved; order check %.3f ms, sort %.3f ms, gather %.3f ms\n", R, P, (unsigned long long)moved, s->grp_ms[1], s->grp_ms[2],
                 s->grp_ms[3]);
     if (n_moved) *n_moved = moved;
-    s->finished = false; s->depth_all_valid = false; s->ev_fresh = -1;
+    s->finished = false; s->depth_all_valid = false; s->dr.valid = false; s->ev_fresh = -1;
     return COV_OK;
 }
 
@@ -2963,6 +2979,115 @@ cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *iv, ui
     return COV_OK;
 }
 
+// ---------------------------------------------------------------------------------------------- depth runs (depth_kernels.hip.h)
+// One chunk of whole targets: the arena filled by the pileup against the scratch copy of the contig block, then marks, the rank scan over
+// the start mask, count / scan / emit over the arena's words.  The one host wait in the middle reads the run count the emit's buffer needs.
+cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_runs_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (!s->finished) { s->err = "cov_depth_runs_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_runs_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (!tid_next || !n_runs || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
+    covr::Range rr("depth runs of one chunk (cov_depth_runs_compute)");
+    cov_session::DepthRuns &D = s->dr;
+    D.valid = false;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    const u32 t1 = dprc::plan_chunk(s->h_tlen.data(), tid_lo, tid_hi, D.chunk_bases), nT = t1 - tid_lo;
+    D.h_woff.resize((size_t)nT + 1);
+    const u64 words64 = [&] { u64 w = 0; for (u32 k = 0; k < nT; k++) w += dprc::words_of(s->h_tlen[tid_lo + k]); return w; }();
+    // (the scan's item indices and block sums are u32: a chunk stays at or below 2^32 arena entries, which one target always does)
+    if (words64 > (1ull << 30)) { s->err = "cov_depth_runs_compute: a chunk of more than 2^32 arena entries (COVERM_KNOBS depth_chunk_bases)"; return COV_ERR_INVALID_ARG; }
+    const u32 words = dprc::layout(s->h_tlen.data() + tid_lo, nT, D.h_woff.data()), mw = (words + 31u) >> 5;
+    const u32 nb = (words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK, nbm = (mw + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    HIPCHK(D.arena.reserve(4ull * words, st)); HIPCHK(D.woff.reserve((size_t)nT + 1, st)); HIPCHK(D.mask.reserve(mw, st)); HIPCHK(D.rank.reserve(mw, st));
+    HIPCHK(D.sums.reserve((size_t)std::max(nb, nbm) + 1, st)); HIPCHK(D.run_off.reserve((size_t)nT + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
+    HIPCHK(D.total.reserve(2, st));
+    hipEvent_t *ev = s->ev[COV_K_DEPTH_RUNS];      // events of its own: the call is not part of a finish; ev_mid closes the run kernels in front of the host's wait
+    if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
+    // ---- the arena: zero, then the pileup of the chunk's tiles (a tile without a record is skipped by the kernel: its depth is the zero fill)
+    HIPCHK(hipMemcpyAsync(D.woff.p, D.h_woff.data(), ((size_t)nT + 1) * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemsetAsync(D.mask.p, 0, (size_t)mw * 4, st));
+    HIPCHK(hipEventRecord(ev[0], st));
+    HIPCHK(hipMemsetAsync(D.arena.p, 0, 16ull * words, st));
+    hipLaunchKernelGGL(covdr::k_depth_marks, dim3((nT + 255u) / 256u), dim3(256), 0, st, D.arena.p, (const u32 *)D.woff.p, (const u32 *)s->d_tlen.p + tid_lo, nT, D.mask.p,
+                       D.doff.p + tid_lo);
+    const u32 tile0 = s->h_tile_first[tid_lo], n_tiles = s->h_tile_first[t1] - tile0;
+    if (s->store.n_records && n_tiles) {
+        PileupArgs a = pileup_args(s);
+        HIPCHK(s->d_ctg_scratch.reserve(s->n_targets, st));   // the accumulated statistics must stay as they are
+        HIPCHK(hipMemcpyAsync(s->d_ctg_scratch.p, s->d_ctg.p, (size_t)s->n_targets * sizeof(DevContig), hipMemcpyDeviceToDevice, st));
+        a.ctg = s->d_ctg_scratch.p;
+        a.depth_out = D.arena.p; a.depth_off = D.doff.p; a.tile_base = tile0;
+        launch_any_pileup<false, true>(s, a, n_tiles);
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], st));
+    // ---- scan #1: rank of every mask word; scan #2, first half: the words' run starts counted, the block offsets and the total
+    const covdr::RankCount rc{D.mask.p};
+    const covdr::RankSink rs{D.rank.p};
+    hipLaunchKernelGGL((covp::k_scan_sums<covdr::RankCount>), dim3(nbm), dim3(256), 0, st, rc, mw, D.sums.p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nbm, D.total.p + 1);
+    hipLaunchKernelGGL((covp::k_scan_apply<covdr::RankCount, covdr::RankSink>), dim3(nbm), dim3(256), 0, st, rc, rs, mw, (const u32 *)D.sums.p);
+    const covdr::WordCount wc{D.arena.p, D.mask.p};
+    hipLaunchKernelGGL((covp::k_scan_sums<covdr::WordCount>), dim3(nb), dim3(256), 0, st, wc, words, D.sums.p);
+    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nb, D.total.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(D.ev_mid, st));
+    u64 total = 0;
+    HIPCHK(hipMemcpyAsync(&total, D.total.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (total > 0xffffffffull) { s->err = "cov_depth_runs_compute: more than 2^32 runs in one chunk"; return COV_ERR_STATE; }      // (at most one run per entry: only a chunk of exactly 2^32 entries, every one a run, gets here)
+    HIPCHK(D.runs.reserve(std::max<u64>(total, 1), st));
+    // ---- scan #2, second half: every word's runs written at its exclusive prefix, a target's first word leaves its run offset
+    const covdr::WordEmit we{D.arena.p, D.mask.p, D.rank.p, D.woff.p, D.runs.p, D.run_off.p};
+    float ms_arena = 0.f, ms_a = 0.f, ms_b = 0.f;
+    (void)hipEventElapsedTime(&ms_arena, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms_a, ev[1], D.ev_mid);
+    HIPCHK(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL((covp::k_scan_apply<covdr::WordCount, covdr::WordEmit>), dim3(nb), dim3(256), 0, st, wc, we, words, (const u32 *)D.sums.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev[1], st));
+    HIPCHK(hipStreamSynchronize(st));
+    (void)hipEventElapsedTime(&ms_b, ev[0], ev[1]);
+    s->ev_fresh = -1;
+    D.arena_ms = ms_arena; D.runs_ms = ms_a + ms_b; D.launches = 7;
+    D.lo = tid_lo; D.next = t1; D.n_runs = total; D.arena_bases = 4ull * words; D.valid = true;
+    *tid_next = t1; *n_runs = total;
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] depth runs: targets [%u, %u), %llu arena entries, %llu runs; arena %.3f ms, run kernels %.3f ms\n", tid_lo, t1,
+                (unsigned long long)D.arena_bases, (unsigned long long)total, D.arena_ms, D.runs_ms);
+    return COV_OK;
+}
+
+cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run *runs) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_runs_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_runs_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (!s->finished || !s->dr.valid) { s->err = "cov_depth_runs_fetch: no chunk computed since the last finish (cov_depth_runs_compute)"; return COV_ERR_STATE; }
+    if (!run_off || (s->dr.n_runs && !runs)) return COV_ERR_INVALID_ARG;
+    static_assert(sizeof(cov_depth_run) == 8 && sizeof(cov_depth_run) == sizeof(dprc::Run) && offsetof(cov_depth_run, depth) == 4 && offsetof(dprc::Run, depth) == 4,
+                  "cov_depth_run mirrors the device struct (numpy mirror in coverm_amd/native.py)");
+    cov_session::DepthRuns &D = s->dr;
+    const u32 nT = D.next - D.lo;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    D.h_run_off.resize((size_t)nT + 1);
+    HIPCHK(hipMemcpyAsync(D.h_run_off.data(), D.run_off.p, (size_t)nT * 4, hipMemcpyDeviceToHost, s->stream));
+    if (D.n_runs) HIPCHK(hipMemcpyAsync(runs, D.runs.p, (size_t)D.n_runs * sizeof(cov_depth_run), hipMemcpyDeviceToHost, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    for (u32 k = 0; k < nT; k++) run_off[k] = D.h_run_off[k];
+    run_off[nT] = D.n_runs;
+    return COV_OK;
+}
+
+cov_status cov_depth_runs_last(const cov_session *s, cov_depth_runs_info *out) {
+    if (!s || !out) return COV_ERR_INVALID_ARG;
+    const cov_session::DepthRuns &D = s->dr;
+    out->arena_bases = D.arena_bases; out->n_runs = D.n_runs; out->arena_ms = D.arena_ms; out->runs_ms = D.runs_ms; out->tid_lo = D.lo; out->tid_next = D.next;
+    return COV_OK;
+}
+
 cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist) {
     if (!s || !s->finished) return COV_ERR_STATE;
     if (s->ivhist_total == 0) return COV_OK;
@@ -2983,6 +3108,11 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
     if (k == COV_K_GENE_READS) {      // not part of a finish: the last cov_interval_reads_compute
         if (ms_total) *ms_total = s->gene_ms;
         if (launches) *launches = s->gene_launches;
+        return COV_OK;
+    }
+    if (k == COV_K_DEPTH_RUNS) {      // not part of a finish: the last cov_depth_runs_compute
+        if (ms_total) *ms_total = s->dr.runs_ms;
+        if (launches) *launches = s->dr.launches;
         return COV_OK;
     }
     if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records

@@ -1,0 +1,71 @@
+// cov_depth_runs_*: the per-base depth of a chunk of whole targets, run-length encoded on the device.  The arithmetic and the chunk's
+// layout are csrc/depth_runs_core.h (shared with the CPU emulation of tests/c/depth_runs_host.cpp); the pileup that fills the arena is the
+// one cov_copy_depth uses (k_pileup_stream<false, true> with depth_out / depth_off / tile_base).
+//
+//   k_depth_marks     a target per thread: its start bit in the mask (one bit per word of four bases), the PAD entries behind its last
+//                     base, and its arena offset for the pileup
+//   RankCount / RankSink      shared scan #1 over the mask's words: rank[i] = target starts in front of mask word i
+//   WordCount / WordEmit      shared scan #2 over the arena's words: a lane takes four bases with one 16-byte load and the entry in front
+//                     of them with one more (the scan hands a thread 16 consecutive items, so the neighbouring lane holds the word 64
+//                     bases on, not the one in front; the extra entry lies in the cache line the lane has just read); the functor counts
+//                     the word's run starts, the sink writes them at the word's exclusive prefix.  The output order is the scan's: target
+//                     order, then position order; no atomic takes part in it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "pair_kernels.hip.h"
+
+#define DPRC_FN __host__ __device__ __forceinline__
+#include "depth_runs_core.h"
+
+namespace covdr {
+
+using dprc::u32;
+using dprc::u64;
+
+__global__ __launch_bounds__(256) void k_depth_marks(int32_t *__restrict__ arena, const u32 *__restrict__ woff, const u32 *__restrict__ tlen, u32 n,
+                                                     u32 *__restrict__ mask, u64 *__restrict__ depth_off) {
+    const u32 k = blockIdx.x * 256u + threadIdx.x;
+    if (k >= n) return;
+    const u32 w = woff[k];
+    atomicOr(mask + (w >> 5), 1u << (w & 31u));
+    dprc::mark_pads(arena, woff, tlen, k);
+    depth_off[k] = 4ull * w;
+}
+
+struct RankCount { const u32 *mask; __device__ u32 operator()(u32 i) const { return dprc::popc32(mask[i]); } };
+struct RankSink { u32 *rank; __device__ void operator()(u32 i, u32 p) const { rank[i] = p; } };
+
+struct Word { int4 d; int32_t prev; bool ts; };
+__device__ __forceinline__ Word load_word(const int32_t *__restrict__ arena, const u32 *__restrict__ mask, u32 w) {
+    Word x;
+    x.d = *reinterpret_cast<const int4 *>(arena + 4ull * w);      // the arena and every word in it are 16-byte aligned
+    x.prev = w ? arena[4ull * w - 1ull] : dprc::PAD;
+    x.ts = dprc::word_starts_target(mask, w);
+    return x;
+}
+
+struct WordCount {
+    const int32_t *arena; const u32 *mask;
+    __device__ u32 operator()(u32 w) const {
+        const Word x = load_word(arena, mask, w);
+        return dprc::popc32(dprc::run_starts(x.d.x, x.d.y, x.d.z, x.d.w, x.prev, x.ts));
+    }
+};
+struct WordEmit {      // dprc::emit_word over registers
+    const int32_t *arena; const u32 *mask, *rank, *woff; dprc::Run *runs; u32 *run_off;
+    __device__ void operator()(u32 w, u32 p) const {
+        const Word x = load_word(arena, mask, w);
+        const u32 m = dprc::run_starts(x.d.x, x.d.y, x.d.z, x.d.w, x.prev, x.ts);
+        if (!x.ts && !m) return;
+        const u32 k = dprc::target_of(mask, rank, w);
+        if (x.ts) run_off[k] = p;
+        const u32 base = 4u * (w - woff[k]);
+        const int32_t d[4] = {x.d.x, x.d.y, x.d.z, x.d.w};
+#pragma unroll
+        for (u32 j = 0; j < 4u; j++)
+            if (m >> j & 1u) { dprc::Run r; r.start = base + j; r.depth = d[j]; runs[p++] = r; }
+    }
+};
+
+}  // namespace covdr

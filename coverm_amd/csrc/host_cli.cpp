@@ -867,11 +867,112 @@ int run_filter(int argc, char **argv) {
     return 0;
 }
 
+// coverm-amd depth: the per-base depth of every reference as a bedGraph, one track per sample.  The samples go through `contig`'s routes,
+// prepare_session, ingest and after_ingest (ingest() above) on one device, one after the other; behind a sample's cov_finish its depth runs
+// come from the device chunk by chunk (covh_depth_runs_write) and are written before the next sample's records replace the store.
+int run_depth(int argc, char **argv) {
+    const double t_main0 = now();
+    Run R;
+    Args &a = R.a;
+    a.mode = "contig";
+    auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && (argv[i + 1][0] != '-' || !argv[i + 1][1])) dst.push_back(argv[++i]); };
+    static const char *const REFUSED[] = {"-m", "--methods", "--gff", "--gff-feature-type", "--devices", "--contig-end-exclusion", "--min-covered-fraction", "--trim-min", "--trim-max",
+                                          "--output-format", "-s", "--separator", "--single-genome", "--genome-definition", "-f", "--genome-fasta-files", "-d",
+                                          "--genome-fasta-directory", "-x", "--genome-fasta-extension", "--genome-fasta-list", "--use-full-contig-names"};
+    for (int i = 2; i < argc; i++) {
+        const std::string k = argv[i];
+        auto val = [&]() -> const char * { if (i + 1 >= argc) die("missing value for " + k); return argv[++i]; };
+        for (const char *r : REFUSED)
+            if (k == r) {
+                if (k == "--devices") die("the argument '--devices' cannot be used with 'depth': a sample's depth runs come from one device (--device N)");
+                if (k == "--contig-end-exclusion") die("the argument '--contig-end-exclusion' cannot be used with 'depth': the track is the depth of every base, the exclusion belongs to the estimators");
+                if (k == "-m" || k == "--methods") die("the argument '" + k + "' cannot be used with 'depth': it writes the per-base depth itself, not a method's value (coverm-amd contig -m ...)");
+                if (k == "--gff" || k == "--gff-feature-type") die("the argument '" + k + "' cannot be used with 'depth' (per-gene coverage: coverm-amd contig --gff)");
+                die("the argument '" + k + "' cannot be used with 'depth': it belongs to coverm-amd contig / genome (the track has one line per depth run of a reference)");
+            }
+        if (k == "-b" || k == "--bam-files") collect(i, a.bams);
+        else if (k == "-o" || k == "--output-file") a.output_file = val();
+        else if (k == "--no-zeros") a.no_zeros = true;
+        else if (parse_filter_flag(k, val, a.filter)) {}
+        else if (k == "-t" || k == "--threads") a.threads = (int)parse_uint(k, val(), 65535);
+        else if (k == "--device") a.devices.assign(1, (int)parse_uint(k, val(), 1023));
+        else if (k == "--no-stream") a.no_stream = true;
+        else if (k == "--unsorted") a.unsorted = true;
+        else if (k == "-v" || k == "--verbose") a.verbose = true;
+        else if (k == "-q" || k == "--quiet") {}
+        else die("unknown argument " + k);
+    }
+    if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
+    if (a.devices.empty()) a.devices.push_back(0);
+    {
+        size_t n_stdin = 0, n_pipe = 0;
+        for (auto &b : a.bams) { n_stdin += b == "-"; n_pipe += input_is_pipe(b); }
+        if (n_stdin > 1) die("'-b -' (standard input) can be given once only");
+        if (n_pipe && a.no_stream) die("--no-stream reads the whole file on the host, which a pipe ('-b -', a FIFO) does not allow: write the stream to a file first");
+    }
+    R.contig = true;
+    Filter &f = R.f;
+    f = resolve_filter(a.filter);
+    if (f.doing_filtering()) f.mode(R.fs, R.fp);
+    cov_config &cfg = R.cfg; memset(&cfg, 0, sizeof cfg);
+    cfg.include_improper_pairs = f.improper; cfg.include_supplementary = f.supp;
+    cfg.include_secondary = f.sec; cfg.min_mapq = 255; cfg.contig_end_exclusion = 0; cfg.want = 0;
+    if (f.doing_filtering() && R.fs && !R.fp) {
+        cfg.filter_single = 1; cfg.min_mapq = (uint8_t)f.mapq; cfg.min_aligned_length = f.len_single;
+        cfg.min_percent_identity = f.pid_single; cfg.min_aligned_percent = f.pct_single;
+    }
+    for (auto &b : a.bams) {      // a pipe's format is told from its first bytes read, before any device work
+        if (!input_is_pipe(b) || R.sam_ahead.count(b)) continue;
+        char e[512] = {0};
+        covh_sam *h = covh_sam_open(b.c_str(), e, sizeof e);
+        if (!h) die(e);
+        R.sam_ahead.emplace(b, h);
+        if (covh_sam_kind(h) == 1) die("BAM from a pipe is not supported yet; SAM text is (e.g. `samtools view -h`), or pass the file's path");
+        if (covh_sam_kind(h) == 2) die(stoit_of(b) + ": the stream is neither SAM text nor BAM (NUL bytes in its first piece)");
+    }
+    struct SamDrain { Run &R; ~SamDrain() { for (auto &kv : R.sam_ahead) covh_sam_close(kv.second); R.sam_ahead.clear(); } } sam_drain{R};
+    FILE *out = a.output_file.empty() || a.output_file == "-" ? stdout : fopen(a.output_file.c_str(), "w");
+    if (!out) die("Failed to create output file: " + a.output_file);
+    struct OutClose { FILE *f; ~OutClose() { if (f != stdout) fclose(f); else fflush(stdout); } } out_close{out};
+    std::vector<cov_session *> sess(1, nullptr);
+    struct SessFree { std::vector<cov_session *> &v; ~SessFree() { if (!g_skip_teardown.load()) for (auto *s : v) if (s) cov_destroy(s); } } sess_free{sess};
+    {
+        cov_config c = cfg; c.device = a.devices[0];
+        long long prep = 1;
+        (void)covknob::get("ingest_prepare", prep);
+        if (!no_gpu_ingest() && prep) c.want |= COV_WANT_INGEST;
+        if (cov_create(&c, &sess[0]) != COV_OK) die(cov_last_error(nullptr));
+    }
+    cov_session *s = sess[0];
+    covh_bam_set_pinned(1);
+    covh_bam_set_release_staging(0);
+    if (a.bams.size() > 1) covh_bam_set_buffer_cache(1);
+    covh_bam_set_concurrent_feeders(1);
+    (void)cov_bind_thread_to_device_node(a.devices[0]);
+    const double t_sessions = now();
+    for (auto &b : a.bams) {
+        Sample S; S.path = b;
+        ingest(R, s, S, std::max(1, a.threads), 0, 1);
+        const double t_runs0 = now();
+        fprintf(out, "track type=bedGraph name=\"%s\"\n", S.stoit.c_str());
+        fflush(out);
+        const covh_header hdr = S.header();
+        uint64_t n_runs = 0;
+        if (covh_depth_runs_write(s, &hdr, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_runs) != COV_OK) die(covh_last_error());
+        if (timing_on())
+            fprintf(stderr, "[coverm-amd] sample %s: open %.3fs, ingest (decode+push) %.3fs, finish %.3fs, %llu records; depth runs: %llu runs computed, fetched and written in %.3fs\n",
+                    S.stoit.c_str(), S.t_open, S.t_ingest, S.t_finish, (unsigned long long)S.n_records, (unsigned long long)n_runs, now() - t_runs0);
+    }
+    if (timing_on()) fprintf(stderr, "[coverm-amd] main: arguments + device session %.3fs, samples %.3fs\n", t_sessions - t_main0, now() - t_sessions);
+    return 0;
+}
+
 int run_cli(int argc, char **argv) {
     const double t_main0 = now();
     Run R;
     Args &a = R.a;
     if (argc >= 2 && !strcmp(argv[1], "filter")) return run_filter(argc, argv);
+    if (argc >= 2 && !strcmp(argv[1], "depth")) return run_depth(argc, argv);
     if (argc < 2 || (strcmp(argv[1], "contig") && strcmp(argv[1], "genome"))) {
         fprintf(stderr, "usage: coverm-amd contig|genome -b <bam>... [-m <methods>...] [options]   (see src/cli.rs of CoverM for the flags; "
                         "engine flags: --device N | --devices a,b,..., --no-stream, --unsorted)\n"
@@ -887,7 +988,10 @@ int run_cli(int argc, char **argv) {
                         "       FILE whole on the host instead (the cross-check).  BAM from a pipe and gzip-compressed SAM are not supported.\n"
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
-                        "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n");
+                        "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n"
+                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
+                        "       the per-base depth of every reference, under contig's filters, as a bedGraph: one `track` line per sample, then\n"
+                        "       name<TAB>start<TAB>end<TAB>depth (0-based, half open) per stretch of equal depth; --no-zeros drops the stretches of depth 0\n");
         return 2;
     }
     a.mode = argv[1];

@@ -6,6 +6,8 @@
 #include "sep_entry_core.h"
 
 #include <algorithm>
+#include <cerrno>
+#include <unistd.h>
 #include <mutex>
 #include <functional>
 #include <condition_variable>
@@ -1597,3 +1599,86 @@ int covh_session_interval_reads(void *ctx, const cov_interval *iv, uint64_t n, i
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------- depth runs as a bedGraph (`coverm-amd depth`)
+namespace {
+
+bool write_all(int fd, const char *p, size_t n) {
+    while (n) {
+        const ssize_t w = ::write(fd, p, n);
+        if (w < 0) { if (errno == EINTR) continue; return false; }
+        p += w; n -= (size_t)w;
+    }
+    return true;
+}
+
+// runs [j0, j1) of the chunk as text; k = the target of run j0
+void format_piece(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, const uint64_t *run_off, const cov_depth_run *runs, bool no_zeros, uint64_t j0,
+                  uint64_t j1, std::string &out) {
+    out.clear();
+    uint32_t k = (uint32_t)(std::upper_bound(run_off, run_off + n_targets + 1, j0) - run_off) - 1u;      // last target whose offset is <= j0: an empty one in front shares it
+    char num[24];
+    auto put = [&](uint64_t v) { const auto r = std::to_chars(num, num + sizeof num, v); out.append(num, (size_t)(r.ptr - num)); };
+    for (uint64_t j = j0; j < j1; j++) {
+        while (j >= run_off[k + 1]) k++;
+        const cov_depth_run r = runs[j];
+        if (no_zeros && r.depth == 0) continue;
+        const uint32_t t = tid_lo + k;
+        const uint64_t end = j + 1 < run_off[k + 1] ? runs[j + 1].start : h->target_len[t];
+        out.append(h->names + h->name_off[t], h->name_off[t + 1] - h->name_off[t]);
+        out.push_back('\t'); put(r.start); out.push_back('\t'); put(end); out.push_back('\t');
+        if (r.depth < 0) { out.push_back('-'); put((uint64_t)(-(int64_t)r.depth)); } else put((uint64_t)r.depth);
+        out.push_back('\n');
+    }
+}
+
+}  // namespace
+
+int covh_depth_runs_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, const uint64_t *run_off, const cov_depth_run *runs, int no_zeros,
+                           int threads, int out_fd) {
+    if (!h || !run_off || (uint64_t)tid_lo + n_targets > h->n_targets) { g_err = "covh_depth_runs_format: targets outside the header"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = run_off[n_targets];
+    if (n && !runs) { g_err = "covh_depth_runs_format: no runs"; return COV_ERR_INVALID_ARG; }
+    constexpr uint64_t PIECE = 1ull << 17;      // runs per piece: a few MB of text
+    const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
+    std::vector<std::string> text(T);
+    for (uint64_t base = 0; base < n; base += PIECE * T) {      // T pieces side by side, written in their order
+        const unsigned np = (unsigned)std::min<uint64_t>(T, (n - base + PIECE - 1) / PIECE);
+        auto piece = [&](unsigned i) { format_piece(h, tid_lo, n_targets, run_off, runs, no_zeros != 0, base + i * PIECE, std::min(n, base + (i + 1) * PIECE), text[i]); };
+        std::vector<std::thread> th;
+        for (unsigned i = 1; i < np; i++) th.emplace_back(piece, i);
+        piece(0);
+        for (auto &t : th) t.join();
+        for (unsigned i = 0; i < np; i++)
+            if (!write_all(out_fd, text[i].data(), text[i].size())) { g_err = "covh_depth_runs_format: write failed"; return COV_ERR_INVALID_ARG; }
+    }
+    return COV_OK;
+}
+
+int covh_depth_runs_write(cov_session *s, const covh_header *h, int no_zeros, int threads, int out_fd, uint64_t *n_runs_out) {
+    if (!s || !h) { g_err = "covh_depth_runs_write: no session"; return COV_ERR_INVALID_ARG; }
+    uint64_t total = 0;
+    if (n_runs_out) *n_runs_out = 0;
+    cov_depth_run *runs = nullptr; size_t cap = 0;      // page-locked, grown to the largest chunk
+    struct Free { cov_depth_run *&p; ~Free() { if (p) cov_host_free(p); } } free_runs{runs};
+    std::vector<uint64_t> run_off;
+    for (uint32_t lo = 0; lo < h->n_targets;) {
+        uint32_t next = 0; uint64_t n = 0;
+        int rc = (int)cov_depth_runs_compute(s, lo, h->n_targets, &next, &n);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        if (n > cap) {
+            if (runs) { cov_host_free(runs); runs = nullptr; }
+            cap = (size_t)n;
+            runs = static_cast<cov_depth_run *>(cov_host_alloc(cap * sizeof(cov_depth_run)));
+            if (!runs) { g_err = "covh_depth_runs_write: no page-locked memory for a chunk's runs"; return COV_ERR_HIP; }
+        }
+        run_off.resize((size_t)(next - lo) + 1);
+        rc = (int)cov_depth_runs_fetch(s, run_off.data(), runs);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        rc = covh_depth_runs_format(h, lo, next - lo, run_off.data(), runs, no_zeros, threads, out_fd);
+        if (rc != COV_OK) return rc;
+        total += n; lo = next;
+    }
+    if (n_runs_out) *n_runs_out = total;
+    return COV_OK;
+}

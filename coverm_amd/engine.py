@@ -177,6 +177,39 @@ class Session:
         self._check(self._lib.cov_copy_depth(self._h, tid, d.ctypes.data if d.size else None))
         return d
 
+    def depth_runs(self, tid_lo: int = 0, tid_hi: Optional[int] = None, chunks=None):
+        """cov_depth_runs_compute / cov_depth_runs_fetch over targets [tid_lo, tid_hi) (default: all), chunk by chunk: the per-base depth
+        run-length encoded on the device.  Returns (run_off, start, depth): the runs of target tid_lo + k are entries
+        run_off[k] .. run_off[k + 1] (uint64, tid_hi - tid_lo + 1 entries), start[j] the run's first base (uint32, 0-based, inside its
+        target), depth[j] its depth (int32); a run ends where the next one of its target starts, or at the target's length.  `chunks`: a
+        list that receives one dict per chunk (cov_depth_runs_info: tid_lo, tid_next, arena_bases, n_runs, arena_ms, runs_ms)."""
+        hi = self.n_targets if tid_hi is None else int(tid_hi)
+        lo = int(tid_lo)
+        offs, parts, base = [np.zeros(1, dtype=np.uint64)], [], 0
+        while lo < hi:
+            nxt, n = C.c_uint32(0), C.c_uint64(0)
+            self._check(self._lib.cov_depth_runs_compute(self._h, C.c_uint32(lo), C.c_uint32(hi), C.byref(nxt), C.byref(n)))
+            ro = np.zeros(nxt.value - lo + 1, dtype=np.uint64)
+            runs = np.zeros(int(n.value), dtype=native.DEPTH_RUN_DTYPE)
+            self._check(self._lib.cov_depth_runs_fetch(self._h, ro.ctypes.data, runs.ctypes.data if runs.size else None))
+            if chunks is not None:
+                info = native.CovDepthRunsInfo()
+                self._check(self._lib.cov_depth_runs_last(self._h, C.byref(info)))
+                chunks.append({k: getattr(info, k) for k, _ in info._fields_})
+            offs.append(ro[1:] + np.uint64(base))
+            parts.append(runs)
+            base += int(n.value)
+            lo = nxt.value
+        runs = np.concatenate(parts) if parts else np.zeros(0, dtype=native.DEPTH_RUN_DTYPE)
+        return np.concatenate(offs), np.ascontiguousarray(runs["start"]), np.ascontiguousarray(runs["depth"])
+
+    def depth_runs_kernel_ms(self):
+        """(ms, launches) of the run kernels of the last chunk of depth_runs (COV_K_DEPTH_RUNS)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_RUNS, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def set_estimators(self, estimators):
         """cov_set_estimators: CoverageEstimator::calculate_coverage of every contig on the device at each finish (contig mode).
         `estimators`: coverm_amd.host.CoverageEstimator structures (same layout as cov_estimator); [] turns it off."""

@@ -349,6 +349,19 @@ int covh_gene_coverage_reads(const covh_header *h, const covh_genes *genes, cons
 int covh_session_interval_reads(void *ctx, const cov_interval *intervals, uint64_t n, int want_identity, cov_interval_reads *out,
                                 uint64_t *mapped_total, int *sorted_by_start);
 
+/* ---- depth runs as a bedGraph (`coverm-amd depth`): the runs cov_depth_runs_compute leaves on the device, as text lines
+ *   name \t start \t end \t depth \n        0-based, half open; end = the start of the target's next run, or the target's length
+ * in target order, then position order.  no_zeros drops the lines of depth 0 (the device always emits every run).
+ * covh_depth_runs_format needs no device: the runs of targets [tid_lo, tid_lo + n_targets) of `h` (run_off: n_targets + 1 entries, as
+ * cov_depth_runs_fetch returns them), formatted on up to `threads` threads in ordered pieces and written to the descriptor out_fd in order;
+ * the text is the same for every thread count.  covh_depth_runs_write does that for every target of a finished session, chunk by chunk
+ * (cov_depth_runs_compute / cov_depth_runs_fetch into page-locked memory): host memory is bounded by the chunk's runs.  *n_runs_out (may be
+ * NULL) = the runs the device emitted.  COV_OK, or the ABI's status with its text in covh_last_error (COV_ERR_STATE after a spill of the
+ * bounded record store); COV_ERR_INVALID_ARG "write failed" when the descriptor refuses the bytes. */
+int covh_depth_runs_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, const uint64_t *run_off, const cov_depth_run *runs,
+                           int no_zeros, int threads, int out_fd);
+int covh_depth_runs_write(cov_session *s, const covh_header *h, int no_zeros, int threads, int out_fd, uint64_t *n_runs_out);
+
 /* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
  * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.
  * covh_genome_fasta_paths resolves a directory (directory != NULL: regular files, symlinks followed, whose name ends in

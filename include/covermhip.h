@@ -154,7 +154,8 @@ typedef enum {
     COV_K_SAM = 9,      /* cov_sam_*: the decode kernels of the last SAM text ingest, summed over its windows (not part of a finish) */
     COV_K_SEP = 10,     /* cov_set_genome_runs: the table entry -> targets of the finish (scans, compaction, segments), in front of COV_K_GENOME */
     COV_K_GENE_READS = 11, /* cov_interval_reads_compute: the kernels of the last call, summed (not part of a finish) */
-    COV_K_COUNT = 12
+    COV_K_DEPTH_RUNS = 12, /* cov_depth_runs_compute: the run kernels of the last chunk (marks, the two scans, emit), summed (not part of a finish) */
+    COV_K_COUNT = 13
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -446,7 +447,7 @@ cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
  * the host, the records from the first considered record of the contig in flight onwards move to the front of the store and the call
  * goes on ("a spill"); cov_finish / cov_fetch_hist / cov_gather then return the whole sample (record indices count from the sample's first
  * record).  What remains: ONE reference's records must fit (2^32 - 16 records and CIGAR words); after a spill cov_copy_depth,
- * cov_interval_stats_compute, cov_interval_reads_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
+ * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
  * that has to hand its file to the CPU reader fails with COV_ERR_STATE instead of COV_ERR_INGEST_FALLBACK; a store that carries mate
  * columns (cov_ingest_want_mates) or an adopted device batch is never spilled.  cov_store_spills: spills since the last cov_reset. */
 uint32_t cov_store_spills(const cov_session *s);
@@ -484,6 +485,37 @@ cov_status cov_fetch_interval_hist(cov_session *s, uint64_t *hist);
 typedef struct { uint64_t n_reads, mismatches; double sum_identity; uint64_t contig_taken; } cov_interval_reads; /* 32 B */
 cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *intervals, uint64_t n, int want_identity,
                                       cov_interval_reads *out, uint64_t *mapped_total, int *sorted_by_start);
+
+/* ---- depth runs: the per-base depth the pileup computes (under cov_config's filters, the depth cov_copy_depth returns), run-length
+ * encoded on the device, for a coverage track that integrates to the table.  A depth run of target t is a maximal stretch [start, end) of
+ * equal depth inside t, stretches of depth 0 included: the runs of a target tile [0, L) exactly, never cross a target boundary (two
+ * adjacent targets whose last and first depths are equal still give two runs), and a target with L == 0 has none.  A run's end is the next
+ * run's start, or L for the target's last run.
+ * The work goes a CHUNK of whole targets at a time, so that device and host memory are bounded by the chunk and not by the sample:
+ *   cov_depth_runs_compute(s, tid_lo, tid_hi, &tid_next, &n_runs)
+ *         materialises the depth of targets [tid_lo, tid_next) — as many whole targets from tid_lo on as fit a budget of 2^28 bases (4 B per
+ *         base in HBM; COVERM_KNOBS depth_chunk_bases; every target takes a multiple of four bases and at least four; a single target above
+ *         the budget is a chunk of its own), tid_lo < tid_next <= tid_hi <= n_targets — and encodes it: marks, two scans, emit
+ *         (csrc/depth_kernels.hip.h).  The accumulated statistics stay as they are (the pileup runs against a scratch copy, as for
+ *         cov_copy_depth).  The chunk's n_runs runs stay on the device until the next compute / push / reset / finish.
+ *   cov_depth_runs_fetch(s, run_off, runs)
+ *         run_off: tid_next - tid_lo + 1 entries, the runs of target tid_lo + k are runs[run_off[k] .. run_off[k + 1]) (an empty target
+ *         repeats its neighbour's offset); runs: n_runs entries in target order, then position order (page-locked memory moves by DMA).
+ *   loop with tid_lo = tid_next until tid_next == tid_hi.
+ * Both are valid after cov_finish; COV_ERR_STATE before it, while an ingest is open, and after a spill of the bounded record store (the
+ * depth needs every record); cov_depth_runs_fetch also without a computed chunk.  cov_kernel_ms(COV_K_DEPTH_RUNS) and
+ * cov_depth_runs_last describe the last chunk. */
+typedef struct { uint32_t start; int32_t depth; } cov_depth_run; /* 8 B */
+typedef struct {
+    uint64_t arena_bases; /* entries of the chunk's arena (padding included) */
+    uint64_t n_runs;
+    double arena_ms;      /* the pileup into the arena (with its zero fill), HIP-event time */
+    double runs_ms;       /* the run kernels = cov_kernel_ms(COV_K_DEPTH_RUNS) */
+    uint32_t tid_lo, tid_next;
+} cov_depth_runs_info;
+cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs);
+cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run *runs);
+cov_status cov_depth_runs_last(const cov_session *s, cov_depth_runs_info *out);
 
 /* Page-locked host memory for record batches, pooled: a freed block is kept for the next request of similar size
  * (a decoder filling one batch per BAM file gets its arrays back without re-pinning).  cov_host_alloc returns NULL
