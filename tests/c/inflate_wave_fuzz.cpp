@@ -1,12 +1,18 @@
 // AddressSanitizer + UBSan run of csrc/inflate_wave_core.h over valid and damaged DEFLATE streams: the buffers are exactly as large as the
 // kernel's contract says (payload + 64 readable bytes, isize output bytes, TOK_CAP token positions), so any access outside them aborts.
-//   g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o fuzz tests/c/inflate_wave_fuzz.cpp -lz && ./fuzz [rounds] [seed]
+//   g++ -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -o fuzz tests/c/inflate_wave_fuzz.cpp -lz && ./fuzz [rounds] [seed] [directory]
+// directory: payload files, each the block's inflated size (4 bytes, little-endian) and the raw DEFLATE stream; valid_* must inflate to what
+// zlib makes of them, invalid_* must be refused, each at the four byte offsets of a word.
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <zlib.h>
 
+#include <dirent.h>
+
+#include <algorithm>
+#include <string>
 #include <vector>
 
 #define COVW_FN inline
@@ -71,16 +77,60 @@ static int run(const std::vector<uint8_t> &payload, uint32_t misalign, uint32_t 
             if (dist > p || p + len > isize) { rc = -2; break; }
             for (uint32_t k = 0; k < len; k++) out[p + k] = out[p + k - dist];
         }
-        if (rc == 0 && want && (want->size() != isize || memcmp(want->data(), out, isize) != 0)) rc = -3;
+        if (rc == 0 && want && (want->size() != isize || (isize && memcmp(want->data(), out, isize) != 0))) rc = -3;
     }
     for (uint32_t k = 0; k < off; k++) if (out_alloc[k] != 0x5A) rc = -4;    // wrote in front of the block
     free(words); free(out_alloc); free(tok_alloc);
     return rc;
 }
 
+// -> 0 when every file of the directory behaved
+static int run_directory(const char *dir) {
+    DIR *d = opendir(dir);
+    if (!d) { fprintf(stderr, "cannot open %s\n", dir); return 2; }
+    std::vector<std::string> names;
+    while (dirent *e = readdir(d)) if (e->d_name[0] != '.') names.push_back(e->d_name);
+    closedir(d);
+    std::sort(names.begin(), names.end());
+    long valid = 0, invalid = 0;
+    for (const std::string &n : names) {
+        const bool want_ok = n.compare(0, 6, "valid_") == 0;
+        FILE *f = fopen((std::string(dir) + "/" + n).c_str(), "rb");
+        if (!f) { fprintf(stderr, "cannot read %s\n", n.c_str()); return 2; }
+        std::vector<uint8_t> raw;
+        uint8_t buf[4096];
+        for (size_t got; (got = fread(buf, 1, sizeof buf, f)) > 0;) raw.insert(raw.end(), buf, buf + got);
+        fclose(f);
+        if (raw.size() < 4) { fprintf(stderr, "%s: too short\n", n.c_str()); return 2; }
+        const uint32_t isize = (uint32_t)raw[0] | ((uint32_t)raw[1] << 8) | ((uint32_t)raw[2] << 16) | ((uint32_t)raw[3] << 24);
+        const std::vector<uint8_t> payload(raw.begin() + 4, raw.end());
+        std::vector<uint8_t> want;
+        if (want_ok) {
+            want.resize(isize);
+            z_stream z; memset(&z, 0, sizeof z);
+            inflateInit2(&z, -15);
+            z.next_in = const_cast<uint8_t *>(payload.data()); z.avail_in = (uInt)payload.size();
+            uint8_t none = 0;
+            z.next_out = isize ? want.data() : &none; z.avail_out = isize;
+            const int rc = inflate(&z, Z_FINISH);
+            const bool ok = rc == Z_STREAM_END && z.total_out == isize;
+            inflateEnd(&z);
+            if (!ok) { fprintf(stderr, "%s: zlib does not inflate it to %u bytes (%d)\n", n.c_str(), isize, rc); return 1; }
+        }
+        for (uint32_t mis = 0; mis < 4; mis++) {
+            const int rc = run(payload, mis, isize, want_ok ? &want : nullptr);
+            if (want_ok ? rc != 0 : rc <= 0) { fprintf(stderr, "%s at offset %u: %d\n", n.c_str(), mis, rc); return 1; }
+        }
+        (want_ok ? valid : invalid)++;
+    }
+    printf("%ld valid payload files exact, %ld invalid refused\n", valid, invalid);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     const int rounds = argc > 1 ? atoi(argv[1]) : 200;
     if (argc > 2) rng_state ^= strtoull(argv[2], nullptr, 10) * 0x9e3779b97f4a7c15ull;
+    if (argc > 3) { const int rc = run_directory(argv[3]); if (rc) return rc; }
     long ok = 0, rejected = 0, differ = 0;
     for (int r = 0; r < rounds; r++) {
         const uint32_t size = 1 + rnd() % 65280u;

@@ -12,7 +12,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from coverm_amd import bam as cbam, synth  # noqa: E402
 from coverm_amd.engine import FilterConfig, Session  # noqa: E402
 from tests import namehash  # noqa: E402
-from tests.test_gpu_ingest_long_records import FIELDS, rec, text, write  # noqa: E402
+from tests.bamraw import FIELDS, rec  # noqa: E402
+from tests.test_gpu_ingest_long_records import text, write  # noqa: E402
 
 tmp = sys.argv[1]
 ref = synth.make_reference(40, 6_000_000, seed=18, min_len=5000, max_len=800_000)

@@ -228,6 +228,74 @@ def test_blocks_written_by_the_product_writer(host, tmp_path):
     assert np.mean(rounds_seen) < 1.5, np.bincount(rounds_seen)     # pass 2 runs once on nearly every block
 
 
+# ------------------------------------------------------------------------------------------------ the crafted catalogue (tests/lz_cases.py)
+def catalogue_blocks():
+    """(label, payload, bytes) of every block the GPU tests feed the device (tests/test_gpu_inflate_edges.py), the match cases at one start
+    alignment: their payloads are the same at the other three but for a token's length in one case"""
+    from tests import lz_cases as lc
+    cases = lc.lz_cases(0) + lc.lz_cases(3)[3:4] + lc.decoder_cases() + [lc.mixed_cases(64, 765)]
+    return [("%s [block %d]" % (c.id, k), b.payload, b.data) for c in cases for k, b in enumerate(c.blocks)]
+
+
+def test_every_catalogue_block_matches_zlib(host):
+    """every valid crafted stream through this build of the core, its payload at every byte offset of a word: status 0 and zlib's bytes.
+    The pass-2 case must take the rounds it was chosen for — it is what puts the device's repeat loop under test."""
+    from tests import lz_cases as lc
+    n = 0
+    for label, payload, data in catalogue_blocks():
+        assert zlib.decompress(payload, -15) == data
+        for misalign in range(4):
+            st, got, nt, rounds = inflate(host, payload, len(data), misalign)
+            assert st == 0 and got == data, (label, misalign, st)
+        n += 1
+    assert n > 150
+    p2 = lc.pass2_case()
+    b = p2.blocks[0]
+    st, got, nt, rounds = inflate(host, b.payload, len(b.data), 0)
+    print("pass-2 rounds", rounds)
+    assert st == 0 and got == b.data and rounds >= 2 and rounds >= p2.meta["rounds"], rounds
+
+
+def test_crafted_invalid_streams_are_refused(host):
+    """Streams that are wrong in exactly one way (zlib names the way): a non-zero status, never a byte outside the block (inflate()'s
+    canaries: -1).  These run here and under the sanitizer only, never on the device."""
+    from tests import lz_cases as lc
+    bad = lc.invalid_streams()
+    assert len(bad) == 15
+    for label, payload, isize in bad:
+        if not label.startswith(("isize", "match past")):
+            with pytest.raises(zlib.error):
+                zlib.decompress(payload, -15)
+        else:
+            assert len(zlib.decompress(payload, -15)) != isize
+        for misalign in range(4):
+            for fill in (0x00, 0xff):
+                st = inflate(host, payload, isize, misalign, fill)[0]
+                assert st > 0, (label, misalign, st)
+
+
+def test_sanitizer_run_over_the_catalogue(tmp_path):
+    """tests/c/inflate_wave_fuzz.cpp over a directory of payload files: every valid catalogue block must come out exact, every crafted
+    invalid stream must be refused, and no access may leave the exact-size buffers (AddressSanitizer + UBSan)."""
+    from tests import lz_cases as lc
+    exe = str(tmp_path / "covw_fuzz")
+    r = subprocess.run(["g++", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-o", exe, os.path.join(HERE, "c", "inflate_wave_fuzz.cpp"), "-lz"],
+                       capture_output=True, text=True)
+    if r.returncode != 0:
+        pytest.skip("no sanitizer runtime / zlib headers here: " + r.stderr[-200:])
+    d = tmp_path / "payloads"
+    d.mkdir()
+    blocks = catalogue_blocks()
+    for k, (label, payload, data) in enumerate(blocks):
+        (d / ("valid_%04d.bin" % k)).write_bytes(struct.pack("<I", len(data)) + payload)
+    bad = lc.invalid_streams()
+    for k, (label, payload, isize) in enumerate(bad):
+        (d / ("invalid_%04d.bin" % k)).write_bytes(struct.pack("<I", isize) + payload)
+    r = subprocess.run([exe, "0", "1", str(d)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-2000:]
+    assert "%d valid payload files exact, %d invalid refused" % (len(blocks), len(bad)) in r.stdout
+
+
 def test_sanitizer_run_over_valid_and_damaged_streams(tmp_path):
     """tests/c/inflate_wave_fuzz.cpp: exact-size buffers under AddressSanitizer + UBSan — the 64 readable bytes behind the payload, the isize
     output bytes and the TOK_CAP token positions are all the core may touch, whatever the stream holds."""
