@@ -11,6 +11,7 @@
 #include "sam_kernels.hip.h"
 #include "gene_kernels.hip.h"
 #include "depth_kernels.hip.h"
+#include "depth_bins_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -51,6 +52,10 @@ static_assert(sizeof(cov_ingest_stats) == 56 && offsetof(cov_ingest_stats, max_h
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
 static_assert(sizeof(cov_depth_run) == 8 && offsetof(cov_depth_run, depth) == 4 && sizeof(cov_depth_runs_info) == 40 && offsetof(cov_depth_runs_info, tid_lo) == 32, "depth run struct layout");
+static_assert(sizeof(cov_depth_bin) == 24 && sizeof(cov_depth_bin) == sizeof(dbnc::Bin) && offsetof(cov_depth_bin, min) == 8 && offsetof(dbnc::Bin, min) == 8 && offsetof(cov_depth_bin, max) == 12 &&
+              offsetof(dbnc::Bin, max) == 12 && offsetof(cov_depth_bin, covered) == 16 && offsetof(dbnc::Bin, covered) == 16 && offsetof(cov_depth_bin, reserved) == 20 &&
+              sizeof(cov_depth_bins_info) == 48 && offsetof(cov_depth_bins_info, tid_lo) == 32 && offsetof(cov_depth_bins_info, bin_size) == 40,
+              "cov_depth_bin mirrors the device struct (numpy mirror in coverm_amd/native.py)");
 static_assert(sizeof(cov_interval_reads) == 32 && sizeof(cov_interval_reads) == sizeof(covgn::Out) && offsetof(cov_interval_reads, sum_identity) == offsetof(covgn::Out, sum_identity) &&
               offsetof(cov_interval_reads, contig_taken) == offsetof(covgn::Out, contig_taken) && sizeof(cov_interval) == sizeof(gnrc::Interval) &&
               offsetof(cov_interval, start) == offsetof(gnrc::Interval, start), "cov_interval_reads mirrors the device struct");
@@ -288,7 +293,17 @@ struct cov_session {
         u64 n_runs = 0, arena_bases = 0;
         hipEvent_t ev_mid = nullptr;
         float arena_ms = 0.f, runs_ms = 0.f;              // of the last chunk: the pileup into the arena; the run kernels (COV_K_DEPTH_RUNS)
-        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
+        // depth bins (cov_depth_bins_compute / _fetch, depth_bins_kernels.hip.h): the same arena, mask and rank; the chunk's bins and the
+        // targets' bin offsets.  The arena holds ONE chunk: a compute of the runs drops the bins and the reverse (bins_took_arena /
+        // runs_took_arena: what the refused fetch says).
+        DevBuf<dbnc::Bin> bins; DevBuf<u32> bin_off;
+        std::vector<u64> h_bin_off; std::vector<u32> h_bin_off32;
+        bool bins_valid = false, bins_took_arena = false, runs_took_arena = false;
+        u32 b_lo = 0, b_next = 0, b_launches = 0, bin_size = 0;
+        u64 n_bins = 0, b_arena_bases = 0;
+        float b_arena_ms = 0.f, bins_ms = 0.f;            // of the last chunk of bins (COV_K_DEPTH_BINS)
+        void drop() { valid = false; bins_valid = false; bins_took_arena = false; runs_took_arena = false; }      // push / reset / finish: neither is there
+        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); bins.release(); bin_off.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
     } dr;
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
@@ -989,7 +1004,7 @@ cov_status cov_reset(cov_session *s) {
         if (a != COV_OK && !(spilled && a == COV_ERR_STATE)) return a;
         if (a != COV_OK) s->err.clear();
     }
-    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->dr.valid = false; s->store.mates_valid = 0; s->ing.was_span = false;
+    s->adopted = false; s->store.n_records = 0; s->store.n_cigar = 0; s->finished = false; s->depth_all_valid = false; s->dr.drop(); s->store.mates_valid = 0; s->ing.was_span = false;
     s->spill.clear(); s->merged_valid = false; s->merged_hist.clear(); s->ing.rec_spilled = 0; s->spill_retry_at = 0; s->spill_est.clear(); s->est_valid = false; s->gen_valid = false;
     return COV_OK;
 }
@@ -1200,7 +1215,7 @@ static PrepArgs prep_args_of(const cov_session *s, const FinishPlan &p, const Pa
 
 // Stage 1: the session's state of a pass, the buffers sized by the records, the views, k_init.
 static cov_status stage_begin(cov_session *s, const FinishPlan &p, PassViews &v) {
-    s->depth_all_valid = false; s->dr.valid = false;
+    s->depth_all_valid = false; s->dr.drop();
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
     for (int k = 0; k < COV_K_COUNT; k++) { s->k_launches[k] = 0; s->k_ms[k] = 0.f; }
@@ -1606,7 +1621,7 @@ static cov_status spill_store(cov_session *s, bool &progress) {
     }
     HIPCHK(hipStreamSynchronize(q));
     s->store.n_records = n_keep; s->store.n_cigar = cig_keep;
-    s->finished = false; s->depth_all_valid = false; s->dr.valid = false;
+    s->finished = false; s->depth_all_valid = false; s->dr.drop();
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] bounded store: spill %u, %llu records left the store (%llu stay: contig %lld in flight), %llu since the sample began\n", S.count,
                 (unsigned long long)keep_from, (unsigned long long)n_keep, (long long)cstar, (unsigned long long)S.records);
@@ -2489,7 +2504,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     const u32 R = (u32)s->store.n_records;
     if (n_selected) *n_selected = 0;
     if (n_primary) *n_primary = 0;
-    s->finished = false; s->depth_all_valid = false; s->dr.valid = false;
+    s->finished = false; s->depth_all_valid = false; s->dr.drop();
     if (R == 0) return COV_OK;
     covp::PairCols C{};
     s->store.view_unplaced(C); s->store.view_mates(C);
@@ -2707,7 +2722,7 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
         fprintf(stderr, "[covermhip] group: %u records, %u passes, %llu moved; order check %.3f ms, sort %.3f ms, gather %.3f ms\n", R, P, (unsigned long long)moved, s->grp_ms[1], s->grp_ms[2],
                 s->grp_ms[3]);
     if (n_moved) *n_moved = moved;
-    s->finished = false; s->depth_all_valid = false; s->dr.valid = false; s->ev_fresh = -1;
+    s->finished = false; s->depth_all_valid = false; s->dr.drop(); s->ev_fresh = -1;
     return COV_OK;
 }
 
@@ -2982,30 +2997,31 @@ cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *iv, ui
 // ---------------------------------------------------------------------------------------------- depth runs (depth_kernels.hip.h)
 // One chunk of whole targets: the arena filled by the pileup against the scratch copy of the contig block, then marks, the rank scan over
 // the start mask, count / scan / emit over the arena's words.  The one host wait in the middle reads the run count the emit's buffer needs.
-cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
-    if (!s) return COV_ERR_INVALID_ARG;
-    if (s->ing.active) { s->err = "cov_depth_runs_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
-    if (!s->finished) { s->err = "cov_depth_runs_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
-    if (s->spill.active) { s->err = "cov_depth_runs_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
-    if (!tid_next || !n_runs || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
-    covr::Range rr("depth runs of one chunk (cov_depth_runs_compute)");
+//
+// depth_arena_stage is what cov_depth_runs_compute and cov_depth_bins_compute share: the chunk's plan and layout, the buffers, the woff
+// upload, the zero fill, k_depth_marks, the pileup against the scratch copy of the contig block (ev[0] .. ev[1]) and the rank scan.
+struct DepthChunk { u32 t1, nT, words, mw; };
+// Behind its refusal, which touches nothing, the arena is the caller's: what the other call left in it is dropped there, not earlier.
+static cov_status depth_arena_stage(cov_session *s, const char *who, bool for_bins, uint32_t tid_lo, uint32_t tid_hi, hipEvent_t *ev, DepthChunk &c) {
     cov_session::DepthRuns &D = s->dr;
-    D.valid = false;
-    HIPCHK(hipSetDevice(s->cfg.device));
-    timing_events(s);
     hipStream_t st = s->stream;
     const u32 t1 = dprc::plan_chunk(s->h_tlen.data(), tid_lo, tid_hi, D.chunk_bases), nT = t1 - tid_lo;
     D.h_woff.resize((size_t)nT + 1);
     const u64 words64 = [&] { u64 w = 0; for (u32 k = 0; k < nT; k++) w += dprc::words_of(s->h_tlen[tid_lo + k]); return w; }();
     // (the scan's item indices and block sums are u32: a chunk stays at or below 2^32 arena entries, which one target always does)
-    if (words64 > (1ull << 30)) { s->err = "cov_depth_runs_compute: a chunk of more than 2^32 arena entries (COVERM_KNOBS depth_chunk_bases)"; return COV_ERR_INVALID_ARG; }
+    if (words64 > (1ull << 30)) { s->err = std::string(who) + ": a chunk of more than 2^32 arena entries (COVERM_KNOBS depth_chunk_bases)"; return COV_ERR_INVALID_ARG; }
+    if (for_bins) {      // the arena holds one chunk
+        D.bins_valid = false; D.runs_took_arena = false;
+        if (D.valid) { D.valid = false; D.bins_took_arena = true; }
+    } else {
+        D.valid = false; D.bins_took_arena = false;
+        if (D.bins_valid) { D.bins_valid = false; D.runs_took_arena = true; }
+    }
     const u32 words = dprc::layout(s->h_tlen.data() + tid_lo, nT, D.h_woff.data()), mw = (words + 31u) >> 5;
     const u32 nb = (words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK, nbm = (mw + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
     HIPCHK(D.arena.reserve(4ull * words, st)); HIPCHK(D.woff.reserve((size_t)nT + 1, st)); HIPCHK(D.mask.reserve(mw, st)); HIPCHK(D.rank.reserve(mw, st));
-    HIPCHK(D.sums.reserve((size_t)std::max(nb, nbm) + 1, st)); HIPCHK(D.run_off.reserve((size_t)nT + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
+    HIPCHK(D.sums.reserve((size_t)std::max(nb, nbm) + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
     HIPCHK(D.total.reserve(2, st));
-    hipEvent_t *ev = s->ev[COV_K_DEPTH_RUNS];      // events of its own: the call is not part of a finish; ev_mid closes the run kernels in front of the host's wait
-    if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
     // ---- the arena: zero, then the pileup of the chunk's tiles (a tile without a record is skipped by the kernel: its depth is the zero fill)
     HIPCHK(hipMemcpyAsync(D.woff.p, D.h_woff.data(), ((size_t)nT + 1) * 4, hipMemcpyHostToDevice, st));
     HIPCHK(hipMemsetAsync(D.mask.p, 0, (size_t)mw * 4, st));
@@ -3024,12 +3040,36 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev[1], st));
-    // ---- scan #1: rank of every mask word; scan #2, first half: the words' run starts counted, the block offsets and the total
+    // ---- the rank of every mask word: the shared scan over the start mask
     const covdr::RankCount rc{D.mask.p};
     const covdr::RankSink rs{D.rank.p};
     hipLaunchKernelGGL((covp::k_scan_sums<covdr::RankCount>), dim3(nbm), dim3(256), 0, st, rc, mw, D.sums.p);
     hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nbm, D.total.p + 1);
     hipLaunchKernelGGL((covp::k_scan_apply<covdr::RankCount, covdr::RankSink>), dim3(nbm), dim3(256), 0, st, rc, rs, mw, (const u32 *)D.sums.p);
+    c.t1 = t1; c.nT = nT; c.words = words; c.mw = mw;
+    return COV_OK;
+}
+
+cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_runs_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (!s->finished) { s->err = "cov_depth_runs_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_runs_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (!tid_next || !n_runs || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
+    covr::Range rr("depth runs of one chunk (cov_depth_runs_compute)");
+    cov_session::DepthRuns &D = s->dr;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    hipEvent_t *ev = s->ev[COV_K_DEPTH_RUNS];      // events of its own: the call is not part of a finish; ev_mid closes the run kernels in front of the host's wait
+    if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
+    // ---- the arena and scan #1 (the rank of every mask word)
+    DepthChunk ck;
+    if (const cov_status rc = depth_arena_stage(s, "cov_depth_runs_compute", false, tid_lo, tid_hi, ev, ck)) return rc;
+    const u32 t1 = ck.t1, nT = ck.nT, words = ck.words;
+    const u32 nb = (words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    HIPCHK(D.run_off.reserve((size_t)nT + 1, st));
+    // ---- scan #2, first half: the words' run starts counted, the block offsets and the total
     const covdr::WordCount wc{D.arena.p, D.mask.p};
     hipLaunchKernelGGL((covp::k_scan_sums<covdr::WordCount>), dim3(nb), dim3(256), 0, st, wc, words, D.sums.p);
     hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nb, D.total.p);
@@ -3065,6 +3105,7 @@ cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run
     if (!s) return COV_ERR_INVALID_ARG;
     if (s->ing.active) { s->err = "cov_depth_runs_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_depth_runs_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.valid && s->dr.bins_took_arena) { s->err = "cov_depth_runs_fetch: the chunk's arena was taken by a cov_depth_bins_compute since (cov_depth_runs_compute again)"; return COV_ERR_STATE; }
     if (!s->finished || !s->dr.valid) { s->err = "cov_depth_runs_fetch: no chunk computed since the last finish (cov_depth_runs_compute)"; return COV_ERR_STATE; }
     if (!run_off || (s->dr.n_runs && !runs)) return COV_ERR_INVALID_ARG;
     static_assert(sizeof(cov_depth_run) == 8 && sizeof(cov_depth_run) == sizeof(dprc::Run) && offsetof(cov_depth_run, depth) == 4 && offsetof(dprc::Run, depth) == 4,
@@ -3085,6 +3126,85 @@ cov_status cov_depth_runs_last(const cov_session *s, cov_depth_runs_info *out) {
     if (!s || !out) return COV_ERR_INVALID_ARG;
     const cov_session::DepthRuns &D = s->dr;
     out->arena_bases = D.arena_bases; out->n_runs = D.n_runs; out->arena_ms = D.arena_ms; out->runs_ms = D.runs_ms; out->tid_lo = D.lo; out->tid_next = D.next;
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- depth bins (depth_bins_kernels.hip.h)
+// One chunk of whole targets: the arena stage of the depth runs, then every bin initialised and the arena reduced in one pass.  The bin
+// offsets come from the lengths, which the host has: no count, no scan and no host wait in front of the reduction.
+cov_status cov_depth_bins_compute(cov_session *s, uint32_t bin_size, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_bins) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_bins_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (!s->finished) { s->err = "cov_depth_bins_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_bins_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (bin_size == 0 || bin_size > dbnc::MAX_BIN_SIZE) { s->err = "cov_depth_bins_compute: the bin size is 1 .. 2^31 - 1 bases"; return COV_ERR_INVALID_ARG; }
+    if (!tid_next || !n_bins || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
+    covr::Range rr("depth bins of one chunk (cov_depth_bins_compute)");
+    cov_session::DepthRuns &D = s->dr;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    // the chunk is the planner's whatever the bin size; its bins are known from the lengths alone
+    const u32 t1 = dprc::plan_chunk(s->h_tlen.data(), tid_lo, tid_hi, D.chunk_bases), nT = t1 - tid_lo;
+    const u64 total = [&] { u64 b = 0; for (u32 k = 0; k < nT; k++) b += dbnc::bins_of(s->h_tlen[tid_lo + k], bin_size); return b; }();
+    // (a refusal leaves the chunk computed before, its offsets included, as it was)
+    if (total > 0xffffffffull) { s->err = "cov_depth_bins_compute: more than 2^32 bins in one chunk"; return COV_ERR_STATE; }      // (at most one bin per entry, as for the runs)
+    hipEvent_t *ev = s->ev[COV_K_DEPTH_BINS];      // events of its own: the call is not part of a finish; ev_mid closes the bin kernels
+    if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
+    DepthChunk ck;
+    if (const cov_status rc = depth_arena_stage(s, "cov_depth_bins_compute", true, tid_lo, tid_hi, ev, ck)) return rc;
+    D.h_bin_off.resize((size_t)nT + 1); D.h_bin_off32.resize((size_t)nT + 1);
+    (void)dbnc::bin_layout(s->h_tlen.data() + tid_lo, nT, bin_size, D.h_bin_off.data());
+    for (u32 k = 0; k <= nT; k++) D.h_bin_off32[k] = (u32)D.h_bin_off[k];
+    HIPCHK(D.bin_off.reserve((size_t)nT + 1, st)); HIPCHK(D.bins.reserve(std::max<u64>(total, 1), st));
+    HIPCHK(hipMemcpyAsync(D.bin_off.p, D.h_bin_off32.data(), ((size_t)nT + 1) * 4, hipMemcpyHostToDevice, st));
+    u32 launches = 4;      // k_depth_marks and the rank scan's three
+    if (total) {
+        hipLaunchKernelGGL(covdb::k_bins_init, dim3((u32)((total + 255ull) / 256ull)), dim3(256), 0, st, D.bins.p, total);
+        const u32 waves = (ck.words + dbnc::STRETCH_WORDS - 1u) / dbnc::STRETCH_WORDS;
+        hipLaunchKernelGGL(covdb::k_depth_bins, dim3((waves + 3u) / 4u), dim3(256), 0, st, (const int32_t *)D.arena.p, (const u32 *)D.mask.p, (const u32 *)D.rank.p,
+                           (const u32 *)D.woff.p, (const u32 *)D.bin_off.p, ck.words, bin_size, D.bins.p, (u32)total);
+        launches += 2;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(D.ev_mid, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms_arena = 0.f, ms_bins = 0.f;
+    (void)hipEventElapsedTime(&ms_arena, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms_bins, ev[1], D.ev_mid);
+    s->ev_fresh = -1;
+    D.b_arena_ms = ms_arena; D.bins_ms = ms_bins; D.b_launches = launches;
+    D.b_lo = tid_lo; D.b_next = t1; D.n_bins = total; D.b_arena_bases = 4ull * ck.words; D.bin_size = bin_size; D.bins_valid = true;
+    *tid_next = t1; *n_bins = total;
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] depth bins of %u: targets [%u, %u), %llu arena entries, %llu bins; arena %.3f ms, bin kernels %.3f ms\n", bin_size, tid_lo, t1,
+                (unsigned long long)D.b_arena_bases, (unsigned long long)total, D.b_arena_ms, D.bins_ms);
+    return COV_OK;
+}
+
+cov_status cov_depth_bins_fetch(cov_session *s, uint64_t *bin_off, cov_depth_bin *bins) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_bins_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_bins_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.bins_valid && s->dr.runs_took_arena) { s->err = "cov_depth_bins_fetch: the chunk's arena was taken by a cov_depth_runs_compute since (cov_depth_bins_compute again)"; return COV_ERR_STATE; }
+    if (!s->finished || !s->dr.bins_valid) { s->err = "cov_depth_bins_fetch: no chunk computed since the last finish (cov_depth_bins_compute)"; return COV_ERR_STATE; }
+    if (!bin_off || (s->dr.n_bins && !bins)) return COV_ERR_INVALID_ARG;
+    cov_session::DepthRuns &D = s->dr;
+    const u32 nT = D.b_next - D.b_lo;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    if (D.n_bins) {
+        HIPCHK(hipMemcpyAsync(bins, D.bins.p, (size_t)D.n_bins * sizeof(cov_depth_bin), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    for (u32 k = 0; k <= nT; k++) bin_off[k] = D.h_bin_off[k];
+    return COV_OK;
+}
+
+cov_status cov_depth_bins_last(const cov_session *s, cov_depth_bins_info *out) {
+    if (!s || !out) return COV_ERR_INVALID_ARG;
+    const cov_session::DepthRuns &D = s->dr;
+    out->arena_bases = D.b_arena_bases; out->n_bins = D.n_bins; out->arena_ms = D.b_arena_ms; out->bins_ms = D.bins_ms; out->tid_lo = D.b_lo; out->tid_next = D.b_next;
+    out->bin_size = D.bin_size; out->reserved = 0;
     return COV_OK;
 }
 
@@ -3113,6 +3233,11 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
     if (k == COV_K_DEPTH_RUNS) {      // not part of a finish: the last cov_depth_runs_compute
         if (ms_total) *ms_total = s->dr.runs_ms;
         if (launches) *launches = s->dr.launches;
+        return COV_OK;
+    }
+    if (k == COV_K_DEPTH_BINS) {      // not part of a finish: the last cov_depth_bins_compute
+        if (ms_total) *ms_total = s->dr.bins_ms;
+        if (launches) *launches = s->dr.b_launches;
         return COV_OK;
     }
     if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records

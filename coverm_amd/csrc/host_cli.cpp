@@ -875,6 +875,9 @@ int run_depth(int argc, char **argv) {
     Run R;
     Args &a = R.a;
     a.mode = "contig";
+    uint32_t bin_size = 0;      // --bin-size: one line per fixed window (covh_depth_bins_write) instead of one per depth run
+    int bin_value = COVH_BIN_MEAN;
+    bool have_bin_value = false;
     auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && (argv[i + 1][0] != '-' || !argv[i + 1][1])) dst.push_back(argv[++i]); };
     static const char *const REFUSED[] = {"-m", "--methods", "--gff", "--gff-feature-type", "--devices", "--contig-end-exclusion", "--min-covered-fraction", "--trim-min", "--trim-max",
                                           "--output-format", "-s", "--separator", "--single-genome", "--genome-definition", "-f", "--genome-fasta-files", "-d",
@@ -893,6 +896,17 @@ int run_depth(int argc, char **argv) {
         if (k == "-b" || k == "--bam-files") collect(i, a.bams);
         else if (k == "-o" || k == "--output-file") a.output_file = val();
         else if (k == "--no-zeros") a.no_zeros = true;
+        else if (k == "--bin-size") {
+            bin_size = (uint32_t)parse_uint(k, val(), 0x7fffffffull);
+            if (bin_size == 0) die("invalid value '0' for '" + k + "'");
+        } else if (k == "--bin-value") {
+            const std::string v = val();
+            static const char *const KINDS[] = {"mean", "sum", "min", "max", "covered"};      // covh_bin_value
+            bin_value = -1;
+            for (int j = 0; j < 5; j++) if (v == KINDS[j]) bin_value = j;
+            if (bin_value < 0) die("invalid value '" + v + "' for '" + k + "' (mean, sum, min, max or covered)");
+            have_bin_value = true;
+        }
         else if (parse_filter_flag(k, val, a.filter)) {}
         else if (k == "-t" || k == "--threads") a.threads = (int)parse_uint(k, val(), 65535);
         else if (k == "--device") a.devices.assign(1, (int)parse_uint(k, val(), 1023));
@@ -902,6 +916,7 @@ int run_depth(int argc, char **argv) {
         else if (k == "-q" || k == "--quiet") {}
         else die("unknown argument " + k);
     }
+    if (have_bin_value && !bin_size) die("the argument '--bin-value' needs '--bin-size': it picks what is printed per bin (coverm-amd depth --bin-size N --bin-value ...)");
     if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
     if (a.devices.empty()) a.devices.push_back(0);
     {
@@ -957,6 +972,14 @@ int run_depth(int argc, char **argv) {
         fprintf(out, "track type=bedGraph name=\"%s\"\n", S.stoit.c_str());
         fflush(out);
         const covh_header hdr = S.header();
+        if (bin_size) {
+            uint64_t n_bins = 0;
+            if (covh_depth_bins_write(s, &hdr, bin_size, bin_value, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_bins) != COV_OK) die(covh_last_error());
+            if (timing_on())
+                fprintf(stderr, "[coverm-amd] sample %s: open %.3fs, ingest (decode+push) %.3fs, finish %.3fs, %llu records; depth bins of %u: %llu bins computed, fetched and written in %.3fs\n",
+                        S.stoit.c_str(), S.t_open, S.t_ingest, S.t_finish, (unsigned long long)S.n_records, bin_size, (unsigned long long)n_bins, now() - t_runs0);
+            continue;
+        }
         uint64_t n_runs = 0;
         if (covh_depth_runs_write(s, &hdr, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_runs) != COV_OK) die(covh_last_error());
         if (timing_on())
@@ -989,9 +1012,12 @@ int run_cli(int argc, char **argv) {
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n"
-                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
+                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--bin-size N [--bin-value V]] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
                         "       the per-base depth of every reference, under contig's filters, as a bedGraph: one `track` line per sample, then\n"
-                        "       name<TAB>start<TAB>end<TAB>depth (0-based, half open) per stretch of equal depth; --no-zeros drops the stretches of depth 0\n");
+                        "       name<TAB>start<TAB>end<TAB>depth (0-based, half open) per stretch of equal depth; --no-zeros drops the stretches of depth 0\n"
+                        "       --bin-size N [--bin-value mean|sum|min|max|covered]: one line per window of N bases instead (the last window of a reference\n"
+                        "       is short; windows never cross references), reduced on the device; mean (the default) is printed with three decimals, the\n"
+                        "       others as integers; --no-zeros then drops the windows without a covered base\n");
         return 2;
     }
     a.mode = argv[1];

@@ -1682,3 +1682,87 @@ int covh_depth_runs_write(cov_session *s, const covh_header *h, int no_zeros, in
     if (n_runs_out) *n_runs_out = total;
     return COV_OK;
 }
+
+// ---------------------------------------------------------------------------------------------- depth bins as a bedGraph (`coverm-amd depth --bin-size`)
+namespace {
+
+// bins [j0, j1) of the chunk as text
+void format_bins_piece(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, uint32_t bin_size, const uint64_t *bin_off, const cov_depth_bin *bins, int value,
+                       bool no_zeros, uint64_t j0, uint64_t j1, std::string &out) {
+    out.clear();
+    uint32_t k = (uint32_t)(std::upper_bound(bin_off, bin_off + n_targets + 1, j0) - bin_off) - 1u;      // last target whose offset is <= j0: an empty one in front shares it
+    char num[40];
+    auto put = [&](uint64_t v) { const auto r = std::to_chars(num, num + sizeof num, v); out.append(num, (size_t)(r.ptr - num)); };
+    auto put_i = [&](int64_t v) { if (v < 0) { out.push_back('-'); put((uint64_t)(-v)); } else put((uint64_t)v); };
+    for (uint64_t j = j0; j < j1; j++) {
+        while (j >= bin_off[k + 1]) k++;
+        const cov_depth_bin b = bins[j];
+        if (no_zeros && b.max == 0) continue;
+        const uint32_t t = tid_lo + k;
+        const uint64_t start = (j - bin_off[k]) * bin_size, end = std::min<uint64_t>(start + bin_size, h->target_len[t]);
+        out.append(h->names + h->name_off[t], h->name_off[t + 1] - h->name_off[t]);
+        out.push_back('\t'); put(start); out.push_back('\t'); put(end); out.push_back('\t');
+        switch (value) {
+        case COVH_BIN_SUM: put(b.sum); break;
+        case COVH_BIN_MIN: put_i(b.min); break;
+        case COVH_BIN_MAX: put_i(b.max); break;
+        case COVH_BIN_COVERED: put(b.covered); break;
+        default: out.append(num, (size_t)snprintf(num, sizeof num, "%.3f", (double)b.sum / (double)(end - start))); break;
+        }
+        out.push_back('\n');
+    }
+}
+
+}  // namespace
+
+int covh_depth_bins_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, uint32_t bin_size, const uint64_t *bin_off, const cov_depth_bin *bins, int value,
+                           int no_zeros, int threads, int out_fd) {
+    if (!h || !bin_off || (uint64_t)tid_lo + n_targets > h->n_targets) { g_err = "covh_depth_bins_format: targets outside the header"; return COV_ERR_INVALID_ARG; }
+    if (bin_size == 0 || value < COVH_BIN_MEAN || value > COVH_BIN_COVERED) { g_err = "covh_depth_bins_format: bin size 0 or an unknown value kind"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = bin_off[n_targets];
+    if (n && !bins) { g_err = "covh_depth_bins_format: no bins"; return COV_ERR_INVALID_ARG; }
+    constexpr uint64_t PIECE = 1ull << 17;      // bins per piece: a few MB of text
+    const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
+    std::vector<std::string> text(T);
+    for (uint64_t base = 0; base < n; base += PIECE * T) {      // T pieces side by side, written in their order
+        const unsigned np = (unsigned)std::min<uint64_t>(T, (n - base + PIECE - 1) / PIECE);
+        auto piece = [&](unsigned i) {
+            format_bins_piece(h, tid_lo, n_targets, bin_size, bin_off, bins, value, no_zeros != 0, base + i * PIECE, std::min(n, base + (i + 1) * PIECE), text[i]);
+        };
+        std::vector<std::thread> th;
+        for (unsigned i = 1; i < np; i++) th.emplace_back(piece, i);
+        piece(0);
+        for (auto &t : th) t.join();
+        for (unsigned i = 0; i < np; i++)
+            if (!write_all(out_fd, text[i].data(), text[i].size())) { g_err = "covh_depth_bins_format: write failed"; return COV_ERR_INVALID_ARG; }
+    }
+    return COV_OK;
+}
+
+int covh_depth_bins_write(cov_session *s, const covh_header *h, uint32_t bin_size, int value, int no_zeros, int threads, int out_fd, uint64_t *n_bins_out) {
+    if (!s || !h) { g_err = "covh_depth_bins_write: no session"; return COV_ERR_INVALID_ARG; }
+    uint64_t total = 0;
+    if (n_bins_out) *n_bins_out = 0;
+    cov_depth_bin *bins = nullptr; size_t cap = 0;      // page-locked, grown to the largest chunk
+    struct Free { cov_depth_bin *&p; ~Free() { if (p) cov_host_free(p); } } free_bins{bins};
+    std::vector<uint64_t> bin_off;
+    for (uint32_t lo = 0; lo < h->n_targets;) {
+        uint32_t next = 0; uint64_t n = 0;
+        int rc = (int)cov_depth_bins_compute(s, bin_size, lo, h->n_targets, &next, &n);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        if (n > cap) {
+            if (bins) { cov_host_free(bins); bins = nullptr; }
+            cap = (size_t)n;
+            bins = static_cast<cov_depth_bin *>(cov_host_alloc(cap * sizeof(cov_depth_bin)));
+            if (!bins) { g_err = "covh_depth_bins_write: no page-locked memory for a chunk's bins"; return COV_ERR_HIP; }
+        }
+        bin_off.resize((size_t)(next - lo) + 1);
+        rc = (int)cov_depth_bins_fetch(s, bin_off.data(), bins);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        rc = covh_depth_bins_format(h, lo, next - lo, bin_size, bin_off.data(), bins, value, no_zeros, threads, out_fd);
+        if (rc != COV_OK) return rc;
+        total += n; lo = next;
+    }
+    if (n_bins_out) *n_bins_out = total;
+    return COV_OK;
+}

@@ -210,6 +210,41 @@ class Session:
         self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_RUNS, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def depth_bins(self, bin_size: int, tid_lo: int = 0, tid_hi: Optional[int] = None, chunks=None):
+        """cov_depth_bins_compute / cov_depth_bins_fetch over targets [tid_lo, tid_hi) (default: all), chunk by chunk: the per-base depth
+        reduced over windows of `bin_size` bases on the device.  Returns (bin_off, bins): the bins of target tid_lo + k are entries
+        bin_off[k] .. bin_off[k + 1] (uint64, tid_hi - tid_lo + 1 entries) of `bins`, a structured array (native.DEPTH_BIN_DTYPE: sum, min,
+        max, covered); bin b of a target covers bases [b * bin_size, min((b + 1) * bin_size, length)).  `chunks`: a list that receives one
+        dict per chunk (cov_depth_bins_info: tid_lo, tid_next, arena_bases, n_bins, arena_ms, bins_ms, bin_size)."""
+        if not 0 <= int(bin_size) <= 0xffffffff:
+            raise ValueError("bin_size out of range")
+        hi = self.n_targets if tid_hi is None else int(tid_hi)
+        lo = int(tid_lo)
+        offs, parts, base = [np.zeros(1, dtype=np.uint64)], [], 0
+        while lo < hi:
+            nxt, n = C.c_uint32(0), C.c_uint64(0)
+            self._check(self._lib.cov_depth_bins_compute(self._h, C.c_uint32(int(bin_size)), C.c_uint32(lo), C.c_uint32(hi), C.byref(nxt), C.byref(n)))
+            bo = np.zeros(nxt.value - lo + 1, dtype=np.uint64)
+            bins = np.zeros(int(n.value), dtype=native.DEPTH_BIN_DTYPE)
+            self._check(self._lib.cov_depth_bins_fetch(self._h, bo.ctypes.data, bins.ctypes.data if bins.size else None))
+            if chunks is not None:
+                info = native.CovDepthBinsInfo()
+                self._check(self._lib.cov_depth_bins_last(self._h, C.byref(info)))
+                chunks.append({k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"})
+            offs.append(bo[1:] + np.uint64(base))
+            parts.append(bins)
+            base += int(n.value)
+            lo = nxt.value
+        return np.concatenate(offs), (np.concatenate(parts) if parts else np.zeros(0, dtype=native.DEPTH_BIN_DTYPE))
+
+    def depth_bins_kernel_ms(self):
+        """(ms, launches) of the bin kernels of the last chunk of depth_bins (COV_K_DEPTH_BINS): six launches, k_depth_marks, the rank
+        scan's three, k_bins_init and k_depth_bins (four for a chunk without a bin)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_BINS, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
     def set_estimators(self, estimators):
         """cov_set_estimators: CoverageEstimator::calculate_coverage of every contig on the device at each finish (contig mode).
         `estimators`: coverm_amd.host.CoverageEstimator structures (same layout as cov_estimator); [] turns it off."""

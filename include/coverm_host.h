@@ -362,6 +362,21 @@ int covh_depth_runs_format(const covh_header *h, uint32_t tid_lo, uint32_t n_tar
                            int no_zeros, int threads, int out_fd);
 int covh_depth_runs_write(cov_session *s, const covh_header *h, int no_zeros, int threads, int out_fd, uint64_t *n_runs_out);
 
+/* ---- depth bins as a bedGraph (`coverm-amd depth --bin-size N`): the bins cov_depth_bins_compute leaves on the device, as text lines
+ *   name \t start \t end \t value \n        0-based, half open; start = b * bin_size, end = min(start + bin_size, the target's length)
+ * in target order, then position order.  `value` picks what is printed: sum, min, max and covered as integers, mean as
+ * (double)sum / (double)(end - start) with "%.3f" (sum < 2^53: the text is an exact function of the two integers).  no_zeros drops the bins
+ * whose max is 0, for every value.
+ * covh_depth_bins_format needs no device: the bins of targets [tid_lo, tid_lo + n_targets) of `h` (bin_off: n_targets + 1 entries, as
+ * cov_depth_bins_fetch returns them), formatted on up to `threads` threads in ordered pieces and written to out_fd in order; the text is the
+ * same for every thread count.  covh_depth_bins_write does that for every target of a finished session, chunk by chunk, through page-locked
+ * memory.  *n_bins_out (may be NULL) = the bins the device computed.  Status and errors as for the runs. */
+typedef enum { COVH_BIN_MEAN = 0, COVH_BIN_SUM = 1, COVH_BIN_MIN = 2, COVH_BIN_MAX = 3, COVH_BIN_COVERED = 4 } covh_bin_value;
+int covh_depth_bins_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, uint32_t bin_size, const uint64_t *bin_off,
+                           const cov_depth_bin *bins, int value, int no_zeros, int threads, int out_fd);
+int covh_depth_bins_write(cov_session *s, const covh_header *h, uint32_t bin_size, int value, int no_zeros, int threads, int out_fd,
+                          uint64_t *n_bins_out);
+
 /* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
  * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.
  * covh_genome_fasta_paths resolves a directory (directory != NULL: regular files, symlinks followed, whose name ends in

@@ -155,7 +155,8 @@ typedef enum {
     COV_K_SEP = 10,     /* cov_set_genome_runs: the table entry -> targets of the finish (scans, compaction, segments), in front of COV_K_GENOME */
     COV_K_GENE_READS = 11, /* cov_interval_reads_compute: the kernels of the last call, summed (not part of a finish) */
     COV_K_DEPTH_RUNS = 12, /* cov_depth_runs_compute: the run kernels of the last chunk (marks, the two scans, emit), summed (not part of a finish) */
-    COV_K_COUNT = 13
+    COV_K_DEPTH_BINS = 13, /* cov_depth_bins_compute: the bin kernels of the last chunk (marks, the rank scan, init, reduce), summed (not part of a finish) */
+    COV_K_COUNT = 14
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -447,7 +448,7 @@ cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
  * the host, the records from the first considered record of the contig in flight onwards move to the front of the store and the call
  * goes on ("a spill"); cov_finish / cov_fetch_hist / cov_gather then return the whole sample (record indices count from the sample's first
  * record).  What remains: ONE reference's records must fit (2^32 - 16 records and CIGAR words); after a spill cov_copy_depth,
- * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
+ * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_depth_bins_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
  * that has to hand its file to the CPU reader fails with COV_ERR_STATE instead of COV_ERR_INGEST_FALLBACK; a store that carries mate
  * columns (cov_ingest_want_mates) or an adopted device batch is never spilled.  cov_store_spills: spills since the last cov_reset. */
 uint32_t cov_store_spills(const cov_session *s);
@@ -516,6 +517,35 @@ typedef struct {
 cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs);
 cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run *runs);
 cov_status cov_depth_runs_last(const cov_session *s, cov_depth_runs_info *out);
+
+/* ---- depth bins: the same per-base depth reduced over fixed windows on the device, for coverage plots, copy-number windows and binning
+ * input (one value per window, not one line per depth change).  For a bin size B, 1 <= B <= 2^31 - 1, target t of length L has
+ * ceil(L / B) bins; bin b covers bases [b * B, min((b + 1) * B, L)): bins never cross a target boundary, the last bin of a target is short
+ * when B does not divide L, and a target with L == 0 has none.  Per bin: the sum, the smallest and the largest depth of its bases and the
+ * number of bases with depth > 0; all integers, no float is computed on the device.
+ * The chunking is that of the depth runs (the same planner and budget, the same arena):
+ *   cov_depth_bins_compute(s, bin_size, tid_lo, tid_hi, &tid_next, &n_bins)
+ *         materialises the depth of targets [tid_lo, tid_next) as cov_depth_runs_compute does and reduces it: every arena word is read
+ *         once (csrc/depth_bins_kernels.hip.h).  The chunk's n_bins bins stay on the device until the next compute / push / reset / finish.
+ *         bin_size 0 or above 2^31 - 1 is COV_ERR_INVALID_ARG; a chunk of 2^32 bins is refused.
+ *   cov_depth_bins_fetch(s, bin_off, bins)
+ *         bin_off: tid_next - tid_lo + 1 entries relative to the chunk, the bins of target tid_lo + k are bins[bin_off[k] .. bin_off[k + 1])
+ *         (an empty target repeats its neighbour's offset); bins: n_bins entries in target order, then position order.
+ * The states are those of the depth runs.  The runs and the bins of a session share the chunk's arena: a cov_depth_runs_compute makes
+ * cov_depth_bins_fetch return COV_ERR_STATE until the next cov_depth_bins_compute, and the reverse.  cov_kernel_ms(COV_K_DEPTH_BINS) and
+ * cov_depth_bins_last describe the last chunk. */
+typedef struct { uint64_t sum; int32_t min; int32_t max; uint32_t covered; uint32_t reserved; } cov_depth_bin; /* 24 B */
+typedef struct {
+    uint64_t arena_bases; /* entries of the chunk's arena (padding included) */
+    uint64_t n_bins;
+    double arena_ms;      /* the pileup into the arena (with its zero fill), HIP-event time */
+    double bins_ms;       /* the bin kernels = cov_kernel_ms(COV_K_DEPTH_BINS) */
+    uint32_t tid_lo, tid_next;
+    uint32_t bin_size, reserved;
+} cov_depth_bins_info;
+cov_status cov_depth_bins_compute(cov_session *s, uint32_t bin_size, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_bins);
+cov_status cov_depth_bins_fetch(cov_session *s, uint64_t *bin_off, cov_depth_bin *bins);
+cov_status cov_depth_bins_last(const cov_session *s, cov_depth_bins_info *out);
 
 /* Page-locked host memory for record batches, pooled: a freed block is kept for the next request of similar size
  * (a decoder filling one batch per BAM file gets its arrays back without re-pinning).  cov_host_alloc returns NULL
