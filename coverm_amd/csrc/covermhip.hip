@@ -664,6 +664,21 @@ void launch_prep_key(int key, cov_session *s, const FinishPlan &p, const PassVie
     else launch_prep_key<KEY, BIT / 2>(key, s, p, v);
 }
 
+// The device-wide exclusive scan of scan_ops.hip.h over items [0, n) of f, in two halves, since some callers read the total on the host between
+// them.  scan_offsets: bsum (scan_blocks(n) + 1 words, the caller's) receives the blocks' exclusive prefixes and *total64 the grand total.
+// scan_apply: out(i, exclusive prefix of item i) for every item.  Two launches and one; neither allocates.
+constexpr u32 scan_blocks(u32 n) { return (n + covsc::SCAN_BLOCK - 1) / covsc::SCAN_BLOCK; }
+template <typename F>
+void scan_offsets(hipStream_t st, F f, u32 n, u32 *bsum, u64 *total64) {
+    const u32 nb = scan_blocks(n);
+    hipLaunchKernelGGL((covsc::k_scan_sums<F>), dim3(nb), dim3(256), 0, st, f, n, bsum);
+    hipLaunchKernelGGL(covsc::k_scan_offsets, dim3(1), dim3(1024), 0, st, bsum, nb, total64);
+}
+template <typename F, typename O>
+void scan_apply(hipStream_t st, F f, O out, u32 n, const u32 *bsum) {
+    hipLaunchKernelGGL((covsc::k_scan_apply<F, O>), dim3(scan_blocks(n)), dim3(256), 0, st, f, out, n, bsum);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2316,7 +2331,7 @@ cov_status cov_sam_begin(cov_session *s, const char *names_blob, const uint64_t 
     }
     for (hipEvent_t &e : s->sam_ev) if (!e) HIPCHK(hipEventCreate(&e));
     HIPCHK(s->m_nl.reserve(n_words, st)); HIPCHK(s->m_tab.reserve(n_words, st)); HIPCHK(s->m_res.reserve(covs::RES_WORDS, st));
-    HIPCHK(s->m_bsum[0].reserve((n_words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK + 1, st));
+    HIPCHK(s->m_bsum[0].reserve((size_t)scan_blocks((u32)n_words) + 1, st));
     // the reference names: blob, offsets, and the open-addressing table over them (sam_parse_core.h)
     s->m_names = samc::Table{nullptr, 0u, nullptr, nullptr};
     if (n_names) {
@@ -2369,28 +2384,25 @@ cov_status cov_sam_feed(cov_session *s, int slot, const void *host_bytes, uint64
     HIPCHK(hipMemsetAsync(res, 0xff, covs::RES_WORDS * sizeof(u64), st));
     HIPCHK(hipMemsetAsync(res + covs::RES_LAST_AT, 0, sizeof(u64), st));
     HIPCHK(hipEventRecord(s->sam_ev[0], st));
-    const u32 n_words = (u32)((n + 63) / 64), nbw = (n_words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    const u32 n_words = (u32)((n + 63) / 64);
     hipLaunchKernelGGL(covs::k_sam_masks, dim3((u32)((n + samc::MASK_WG_BYTES - 1) / samc::MASK_WG_BYTES)), dim3(256), 0, st, (const uint8_t *)text, n, s->m_nl.p, s->m_tab.p);
     const covs::NlPop nlp{s->m_nl.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covs::NlPop>), dim3(nbw), dim3(256), 0, st, nlp, n_words, s->m_bsum[0].p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[0].p, nbw, res + covs::RES_LINES);
+    scan_offsets(st, nlp, n_words, s->m_bsum[0].p, res + covs::RES_LINES);
     HIPCHK(hipGetLastError());
     u64 *h = s->ing.h_winres;
     HIPCHK(hipMemcpyAsync(h, res, covs::RES_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    const u32 n_lines = (u32)h[covs::RES_LINES], nbl = (n_lines + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
+    const u32 n_lines = (u32)h[covs::RES_LINES], nbl = scan_blocks(n_lines);
     HIPCHK(s->m_line_end.reserve(n_lines, st)); HIPCHK(s->m_cnt.reserve(n_lines, st)); HIPCHK(s->m_rec_idx.reserve(n_lines, st)); HIPCHK(s->m_cig_idx.reserve(n_lines, st));
     HIPCHK(s->m_bsum[1].reserve((size_t)nbl + 1, st)); HIPCHK(s->m_bsum[2].reserve((size_t)nbl + 1, st));
     const covs::Lines L{text, s->m_tab.p, s->m_line_end.p, n_lines};
-    hipLaunchKernelGGL((covp::k_scan_apply<covs::NlPop, covs::LineEmit>), dim3(nbw), dim3(256), 0, st, nlp, covs::LineEmit{s->m_nl.p, s->m_line_end.p}, n_words, (const u32 *)s->m_bsum[0].p);
+    scan_apply(st, nlp, covs::LineEmit{s->m_nl.p, s->m_line_end.p}, n_words, s->m_bsum[0].p);
     hipLaunchKernelGGL(covs::k_sam_count, dim3((n_lines + 255u) / 256u), dim3(256), 0, st, L, s->m_cnt.p, res);
     const covs::IsRec isr{s->m_cnt.p}; const covs::NCig ncg{s->m_cnt.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covs::IsRec>), dim3(nbl), dim3(256), 0, st, isr, n_lines, s->m_bsum[1].p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[1].p, nbl, res + covs::RES_RECORDS);
-    hipLaunchKernelGGL((covp::k_scan_apply<covs::IsRec, covs::Put>), dim3(nbl), dim3(256), 0, st, isr, covs::Put{s->m_rec_idx.p}, n_lines, (const u32 *)s->m_bsum[1].p);
-    hipLaunchKernelGGL((covp::k_scan_sums<covs::NCig>), dim3(nbl), dim3(256), 0, st, ncg, n_lines, s->m_bsum[2].p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, s->m_bsum[2].p, nbl, res + covs::RES_CIGAR);
-    hipLaunchKernelGGL((covp::k_scan_apply<covs::NCig, covs::Put>), dim3(nbl), dim3(256), 0, st, ncg, covs::Put{s->m_cig_idx.p}, n_lines, (const u32 *)s->m_bsum[2].p);
+    scan_offsets(st, isr, n_lines, s->m_bsum[1].p, res + covs::RES_RECORDS);
+    scan_apply(st, isr, covs::Put{s->m_rec_idx.p}, n_lines, s->m_bsum[1].p);
+    scan_offsets(st, ncg, n_lines, s->m_bsum[2].p, res + covs::RES_CIGAR);
+    scan_apply(st, ncg, covs::Put{s->m_cig_idx.p}, n_lines, s->m_bsum[2].p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(s->sam_ev[1], st));
     HIPCHK(hipMemcpyAsync(h, res, covs::RES_WORDS * sizeof(u64), hipMemcpyDeviceToHost, st));
@@ -2470,18 +2482,16 @@ static cov_status gather_store(cov_session *s, const u32 *order, u32 S, bool wit
     DevBuf<u32> d_bsum; DevBuf<u64> d_tot;
     struct Rel { DevBuf<u32> &a; DevBuf<u64> &b; ~Rel() { a.release(); b.release(); } } rel{d_bsum, d_tot};
     RecordStore sel;      // (after the swap below: the old store, which goes with it)
-    const u32 nb = (S + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
-    HIPCHK(d_bsum.reserve((size_t)nb + 1, st)); HIPCHK(d_tot.reserve(1, st));
+    HIPCHK(d_bsum.reserve((size_t)scan_blocks(S) + 1, st)); HIPCHK(d_tot.reserve(1, st));
     const covp::SelCigarLen clen{order, s->store.cigar_off.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covp::SelCigarLen>), dim3(nb), dim3(256), 0, st, clen, S, d_bsum.p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_tot.p);
+    scan_offsets(st, clen, S, d_bsum.p, d_tot.p);
     HIPCHK(hipGetLastError());
     u64 n_cig_sel = 0;
     HIPCHK(hipMemcpyAsync(&n_cig_sel, d_tot.p, sizeof n_cig_sel, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(sel.reserve(S, (size_t)n_cig_sel + 1, st, 0, 0, with_mates));
     covp::SelGather G{}; G.order = order; s->store.view(G.src); sel.view(G.dst);
-    hipLaunchKernelGGL((covp::k_scan_apply<covp::SelCigarLen, covp::SelGather>), dim3(nb), dim3(256), 0, st, clen, G, S, (const u32 *)d_bsum.p);
+    scan_apply(st, clen, G, S, d_bsum.p);
     HIPCHK(hipGetLastError());
     if (with_mates) {
         hipLaunchKernelGGL(covg::k_group_gather_mates, dim3((S + 255u) / 256u), dim3(256), 0, st, order, S, (const int32_t *)s->store.mtid.p, (const u64 *)s->store.qh1.p, (const u32 *)s->store.qh2.p,
@@ -2607,11 +2617,9 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
         }
     }
     // ---- the reference's output order: pairs by their second record, first record then second
-    const u32 nb = (R + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
-    HIPCHK(d_bsum.reserve((size_t)nb + 1, st));
+    HIPCHK(d_bsum.reserve((size_t)scan_blocks(R) + 1, st));
     const covp::PairSlots slots{d_partner.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covp::PairSlots>), dim3(nb), dim3(256), 0, st, slots, R, d_bsum.p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_w.p + 2);
+    scan_offsets(st, slots, R, d_bsum.p, d_w.p + 2);
     HIPCHK(hipGetLastError());
     u64 hw[4];
     HIPCHK(hipMemcpyAsync(hw, d_w.p, sizeof hw, hipMemcpyDeviceToHost, st));
@@ -2628,7 +2636,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     const u32 S = (u32)n_sel;
     HIPCHK(d_order.reserve(S, st));
     const covp::PairEmit emit{d_partner.p, d_order.p};
-    hipLaunchKernelGGL((covp::k_scan_apply<covp::PairSlots, covp::PairEmit>), dim3(nb), dim3(256), 0, st, slots, emit, R, (const u32 *)d_bsum.p);
+    scan_apply(st, slots, emit, R, d_bsum.p);
     // ---- the selected store: CIGAR offsets by a second scan, whose consumer moves the records
     HIPCHK(hipGetLastError());
     { const cov_status g = gather_store(s, d_order.p, S, false); if (g != COV_OK) return g; }
@@ -2678,10 +2686,9 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
 
     // ---- stable LSD radix sort of the record indices
     const u32 P = grpk::n_passes(nT), n_wg = grpk::n_tiles(R), n_hist = n_wg * grpk::RADIX;
-    const u32 nb = (n_hist + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
     DevBuf<u32> d_bsum;
     struct Rel1 { DevBuf<u32> &a; ~Rel1() { a.release(); } } rel1{d_bsum};
-    HIPCHK(d_hist.reserve(n_hist, st)); HIPCHK(d_bsum.reserve((size_t)nb + 1, st)); HIPCHK(d_cnt.reserve(2, st));
+    HIPCHK(d_hist.reserve(n_hist, st)); HIPCHK(d_bsum.reserve((size_t)scan_blocks(n_hist) + 1, st)); HIPCHK(d_cnt.reserve(2, st));
     HIPCHK(d_idx[0].reserve(R, st));
     if (P > 1) { HIPCHK(d_key[0].reserve(R, st)); HIPCHK(d_idx[1].reserve(R, st)); }
     if (P > 2) HIPCHK(d_key[1].reserve(R, st));
@@ -2694,9 +2701,8 @@ cov_status cov_group_records(cov_session *s, uint64_t *n_moved) {
         if (first) hipLaunchKernelGGL(covg::k_group_hist<true>, dim3(n_wg), dim3(256), 0, st, tid, key_in, R, nT, p, d_hist.p, n_wg);
         else hipLaunchKernelGGL(covg::k_group_hist<false>, dim3(n_wg), dim3(256), 0, st, tid, key_in, R, nT, p, d_hist.p, n_wg);
         const covg::HistVal hv{d_hist.p}; const covg::HistPut hp{d_hist.p};      // in place: a thread of the scan writes the items it read itself
-        hipLaunchKernelGGL((covp::k_scan_sums<covg::HistVal>), dim3(nb), dim3(256), 0, st, hv, n_hist, d_bsum.p);
-        hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, d_bsum.p, nb, d_cnt.p + 1);
-        hipLaunchKernelGGL((covp::k_scan_apply<covg::HistVal, covg::HistPut>), dim3(nb), dim3(256), 0, st, hv, hp, n_hist, (const u32 *)d_bsum.p);
+        scan_offsets(st, hv, n_hist, d_bsum.p, d_cnt.p + 1);
+        scan_apply(st, hv, hp, n_hist, d_bsum.p);
         const dim3 g(n_wg), b(256);
         if (first && last) hipLaunchKernelGGL((covg::k_group_scatter<true, true>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
         else if (first) hipLaunchKernelGGL((covg::k_group_scatter<true, false>), g, b, 0, st, tid, key_in, idx_in, key_out, idx_out, R, nT, p, (const u32 *)d_hist.p, n_wg);
@@ -3018,9 +3024,8 @@ static cov_status depth_arena_stage(cov_session *s, const char *who, bool for_bi
         if (D.bins_valid) { D.bins_valid = false; D.runs_took_arena = true; }
     }
     const u32 words = dprc::layout(s->h_tlen.data() + tid_lo, nT, D.h_woff.data()), mw = (words + 31u) >> 5;
-    const u32 nb = (words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK, nbm = (mw + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
     HIPCHK(D.arena.reserve(4ull * words, st)); HIPCHK(D.woff.reserve((size_t)nT + 1, st)); HIPCHK(D.mask.reserve(mw, st)); HIPCHK(D.rank.reserve(mw, st));
-    HIPCHK(D.sums.reserve((size_t)std::max(nb, nbm) + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
+    HIPCHK(D.sums.reserve((size_t)scan_blocks(std::max(words, mw)) + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
     HIPCHK(D.total.reserve(2, st));
     // ---- the arena: zero, then the pileup of the chunk's tiles (a tile without a record is skipped by the kernel: its depth is the zero fill)
     HIPCHK(hipMemcpyAsync(D.woff.p, D.h_woff.data(), ((size_t)nT + 1) * 4, hipMemcpyHostToDevice, st));
@@ -3043,9 +3048,8 @@ static cov_status depth_arena_stage(cov_session *s, const char *who, bool for_bi
     // ---- the rank of every mask word: the shared scan over the start mask
     const covdr::RankCount rc{D.mask.p};
     const covdr::RankSink rs{D.rank.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covdr::RankCount>), dim3(nbm), dim3(256), 0, st, rc, mw, D.sums.p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nbm, D.total.p + 1);
-    hipLaunchKernelGGL((covp::k_scan_apply<covdr::RankCount, covdr::RankSink>), dim3(nbm), dim3(256), 0, st, rc, rs, mw, (const u32 *)D.sums.p);
+    scan_offsets(st, rc, mw, D.sums.p, D.total.p + 1);
+    scan_apply(st, rc, rs, mw, D.sums.p);
     c.t1 = t1; c.nT = nT; c.words = words; c.mw = mw;
     return COV_OK;
 }
@@ -3067,12 +3071,10 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     DepthChunk ck;
     if (const cov_status rc = depth_arena_stage(s, "cov_depth_runs_compute", false, tid_lo, tid_hi, ev, ck)) return rc;
     const u32 t1 = ck.t1, nT = ck.nT, words = ck.words;
-    const u32 nb = (words + covp::SCAN_BLOCK - 1) / covp::SCAN_BLOCK;
     HIPCHK(D.run_off.reserve((size_t)nT + 1, st));
     // ---- scan #2, first half: the words' run starts counted, the block offsets and the total
     const covdr::WordCount wc{D.arena.p, D.mask.p};
-    hipLaunchKernelGGL((covp::k_scan_sums<covdr::WordCount>), dim3(nb), dim3(256), 0, st, wc, words, D.sums.p);
-    hipLaunchKernelGGL(covp::k_scan_offsets, dim3(1), dim3(1024), 0, st, D.sums.p, nb, D.total.p);
+    scan_offsets(st, wc, words, D.sums.p, D.total.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(D.ev_mid, st));
     u64 total = 0;
@@ -3086,7 +3088,7 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     (void)hipEventElapsedTime(&ms_arena, ev[0], ev[1]);
     (void)hipEventElapsedTime(&ms_a, ev[1], D.ev_mid);
     HIPCHK(hipEventRecord(ev[0], st));
-    hipLaunchKernelGGL((covp::k_scan_apply<covdr::WordCount, covdr::WordEmit>), dim3(nb), dim3(256), 0, st, wc, we, words, (const u32 *)D.sums.p);
+    scan_apply(st, wc, we, words, D.sums.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev[1], st));
     HIPCHK(hipStreamSynchronize(st));

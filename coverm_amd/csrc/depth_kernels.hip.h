@@ -13,7 +13,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "pair_kernels.hip.h"
+#include "scan_ops.hip.h"
 
 #define DPRC_FN __host__ __device__ __forceinline__
 #include "depth_runs_core.h"

@@ -55,25 +55,7 @@ __device__ __forceinline__ void post_verdict(u64 *glob, u64 key) {      // the w
     const u64 m = wave_min_u64(key);
     if (covk::lane_id() == 0) atomicMin((unsigned long long *)&glob[G_VERDICT], (unsigned long long)m);
 }
-__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v, int lane) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const u64 t = __shfl_up(v, o); if (lane >= o) v += t; }
-    return v;
-}
-// Exclusive scan over the workgroup's threads (NW waves), wrapping; `total` = the sum over all of them.  lds: NW words.
-template <int NW>
-__device__ __forceinline__ u64 block_excl_scan(u64 v, u64 *lds, u64 &total) {
-    const int lane = covk::lane_id(), w = (int)(threadIdx.x >> 6);
-    const u64 incl = wave_incl_scan_u64(v, lane);
-    __syncthreads();      // (the previous use of lds is over)
-    if (lane == 63) lds[w] = incl;
-    __syncthreads();
-    u64 off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NW; i++) { const u64 x = lds[i]; if (i < w) off += x; tot += x; }
-    total = tot;
-    return off + incl - v;
-}
+using covsc::block_incl_scan;      // (the sums below wrap; an exclusive prefix is the inclusive one less the thread's own value)
 
 __global__ __launch_bounds__(256) void k_gene_classify(const covk::Records r, const gnrc::Filter f, Work w) {
     __shared__ u64 s_cnt[4], s_mism[4];
@@ -108,10 +90,11 @@ __global__ __launch_bounds__(1024) void k_gene_offsets(Work w, u32 nb) {
     for (u32 b0 = 0; b0 < nb; b0 += 1024u) {
         const u32 b = b0 + threadIdx.x;
         const u64 cnt = b < nb ? w.b_cnt[b] : 0ull, ms = b < nb ? w.b_mism[b] : 0ull;
+        const u64 taken = cnt & 0xffffffffull, prim = cnt >> 32;
         u64 t_tot, p_tot, m_tot;
-        const u64 t_ex = block_excl_scan<16>(cnt & 0xffffffffull, lds, t_tot);
-        const u64 p_ex = block_excl_scan<16>(cnt >> 32, lds, p_tot);
-        const u64 m_ex = block_excl_scan<16>(ms, lds, m_tot);
+        const u64 t_ex = block_incl_scan<16>(taken, lds, t_tot) - taken;
+        const u64 p_ex = block_incl_scan<16>(prim, lds, p_tot) - prim;
+        const u64 m_ex = block_incl_scan<16>(ms, lds, m_tot) - ms;
         if (b < nb) { w.b_cnt[b] = ((c_taken + t_ex) & 0xffffffffull) | ((c_prim + p_ex) << 32); w.b_mism[b] = c_mism + m_ex; }
         c_taken += t_tot; c_prim += p_tot; c_mism += m_tot;
     }
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(256) void k_gene_scatter(const covk::Records r, Wor
         if (take) { cnt += 1ull + ((u64)(code[k] >> 2) << 32); msum += ms[k]; }
     }
     u64 tot;
-    const u64 c_ex = block_excl_scan<4>(cnt, lds, tot), m_ex = block_excl_scan<4>(msum, lds, tot);      // (a tile's counts stay below 2^32: no carry between the halves)
+    const u64 c_ex = block_incl_scan<4>(cnt, lds, tot) - cnt, m_ex = block_incl_scan<4>(msum, lds, tot) - msum;      // (a tile's counts stay below 2^32: no carry between the halves)
     const u64 b_cnt = w.b_cnt[blockIdx.x];
     u32 j = (u32)b_cnt + (u32)c_ex, p = (u32)(b_cnt >> 32) + (u32)(c_ex >> 32);
     u64 m = w.b_mism[blockIdx.x] + m_ex;

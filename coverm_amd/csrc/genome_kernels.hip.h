@@ -118,19 +118,17 @@ __global__ __launch_bounds__(1024) void k_genome_hist_sum(const DevGenome *__res
     __shared__ u64 wtot[16];
     const u32 g = blockIdx.x * 1024u + threadIdx.x;
     u64 total;
-    (void)block_incl_scan_u64(g < n_genomes ? (u64)G[g].nh : 0, wtot, total);
+    (void)block_incl_scan<16>(g < n_genomes ? (u64)G[g].nh : 0ull, wtot, total);
     if (threadIdx.x == 0) top[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(1024) void k_genome_hist_off(DevGenome *__restrict__ G, u32 n_genomes, const u64 *__restrict__ top, u64 *__restrict__ total_out,
                                                           u64 cap, DevGlobal *__restrict__ glob) {
     __shared__ u64 wtot[16];
-    u64 mine = 0, base;
-    for (u32 b = threadIdx.x; b < blockIdx.x; b += 1024u) mine += top[b];
-    (void)block_incl_scan_u64(mine, wtot, base);
+    const u64 base = blocks_in_front<16>(top, wtot);
     const u32 g = blockIdx.x * 1024u + threadIdx.x;
     const u64 v = g < n_genomes ? (u64)G[g].nh : 0;
     u64 total;
-    const u64 inc = block_incl_scan_u64(v, wtot, total);
+    const u64 inc = block_incl_scan<16>(v, wtot, total);
     if (g < n_genomes) G[g].hist_off = base + inc - v;
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
         *total_out = base + total;
@@ -171,46 +169,24 @@ __global__ __launch_bounds__(256) void k_genome_hist_merge(const DevContig *__re
 // The order rule without the per-contig block on the host (cov_finish_genomes): over the contigs with a considered record, in tid order,
 // first_rec must not lie before the largest last_rec in front (convert_results; contig.rs:129-132).  k_order_max leaves every block's
 // largest last_rec + 1 (0: no seen contig) in ord[1 + block]; k_order_check scans and leaves the smallest offending first_rec in ord[0].
-__device__ __forceinline__ u32 block_incl_max_u32(u32 v, u32 *wmax, u32 &total) {
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    u32 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u32 t = __shfl_up(inc, o);
-        if (lane >= o) inc = max(inc, t);
-    }
-    if (lane == 63) wmax[w] = inc;
-    __syncthreads();
-    u32 wbase = 0; total = 0;
-    for (int k = 0; k < 16; k++) { const u32 x = wmax[k]; if (k < w) wbase = max(wbase, x); total = max(total, x); }
-    __syncthreads();
-    return max(wbase, inc);
-}
 // (last_rec + 1 as a u64 would be needed at 2^32 - 1 records; the store holds at most 2^32 - 16)
 __global__ __launch_bounds__(1024) void k_order_max(const DevContig *__restrict__ ctg, u32 n_targets, u64 *__restrict__ ord) {
     __shared__ u32 wmax[16];
     const u32 c = blockIdx.x * 1024u + threadIdx.x;
     u32 total;
-    (void)block_incl_max_u32((c < n_targets && ctg[c].n_pass != 0) ? ctg[c].last_rec + 1u : 0u, wmax, total);
+    (void)block_incl_scan<16>((c < n_targets && ctg[c].n_pass != 0) ? ctg[c].last_rec + 1u : 0u, wmax, total, Max{});
     if (threadIdx.x == 0) ord[1 + blockIdx.x] = total;
     if (blockIdx.x == 0 && threadIdx.x == 0) ord[0] = ~0ull;
 }
 __global__ __launch_bounds__(1024) void k_order_check(const DevContig *__restrict__ ctg, u32 n_targets, u64 *__restrict__ ord) {
     __shared__ u32 wmax[16];
-    u32 mine = 0, base;
-    for (u32 b = threadIdx.x; b < blockIdx.x; b += 1024u) mine = max(mine, (u32)ord[1 + b]);
-    (void)block_incl_max_u32(mine, wmax, base);              // base = largest last_rec + 1 of the blocks in front
+    const u32 base = blocks_in_front<16>(ord + 1, wmax, Max{});      // largest last_rec + 1 of the blocks in front
     const u32 c = blockIdx.x * 1024u + threadIdx.x;
     const bool seen = c < n_targets && ctg[c].n_pass != 0;
     const u32 v = seen ? ctg[c].last_rec + 1u : 0u;
     u32 total;
-    const u32 inc = block_incl_max_u32(v, wmax, total);
-    const u32 up = __shfl_up(inc, 1);                        // exclusive prefix: the lane in front, or the waves in front
-    __shared__ u32 wlast[16];
-    if (lane_id() == 63) wlast[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    u32 prev = lane_id() ? up : ((threadIdx.x >> 6) ? wlast[(threadIdx.x >> 6) - 1] : 0u);
-    prev = max(prev, base);
+    const u32 inc = block_incl_scan<16>(v, wmax, total, Max{});
+    const u32 prev = max(block_prev<16>(inc, wmax, 0u), base);      // exclusive prefix: the thread in front
     if (seen && prev != 0u && ctg[c].first_rec < prev - 1u) atomicMin(&ord[0], (u64)ctg[c].first_rec);
 }
 

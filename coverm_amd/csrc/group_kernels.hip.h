@@ -6,7 +6,7 @@
 //   k_group_check     does a key ever decrease?  When not, nothing else runs: a grouped file pays one read of the tid column.
 //   per pass (digit of 8 bits, grpk::n_passes(n_targets) of them):
 //     k_group_hist    digit histogram of every workgroup's tile of 4096 items, stored digit-major
-//     covp::k_scan_*  ONE exclusive scan over [digit][workgroup] (the device-wide scan of pair_kernels.hip.h): base[d][wg]
+//     covsc::k_scan_* ONE exclusive scan over [digit][workgroup] (the device-wide scan of scan_ops.hip.h): base[d][wg]
 //     k_group_scatter item -> base + rank inside the tile.  The rank is counted, never raced for: per round of 256 items the lanes of a wave
 //                     find their peers (same digit) with eight ballots, the lowest peer posts the wave's count in LDS, the digit's thread turns
 //                     the four counts into four bases (group_rank_core.h, shared with the CPU emulation of tests/c/group_rank_host.cpp).

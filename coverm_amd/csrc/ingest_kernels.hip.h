@@ -32,6 +32,7 @@
 #include <stdint.h>
 
 #include "pair_kernels.hip.h"
+#include "scan_ops.hip.h"
 #include "ingest_plan_core.h"
 
 namespace covi {
@@ -482,18 +483,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4))) void k_
 // arguments and tests/test_inflate_wave_core.py runs them on the CPU.)
 // (Held to 96 registers = five waves per SIMD, one spilled register: 24.5 ms per round against 22.3 on the same box, profiles/r04_waves5_lzscope.log.)
 
-// Inclusive wave64 prefix sum (DPP row shifts + row broadcasts; VALU latency only).
-__device__ __forceinline__ u32 wave_incl_scan_u32(u32 x) {
-    int v = (int)x;
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return (u32)v;
-}
-
 // One wave per BGZF block executes the block's match tokens.  64 tokens are taken at a time, one per lane; a token may only
 // run once every byte it reads is final: everything below the output position of the lowest unfinished token is (literals were
 // written by k_inflate, earlier matches are done), so in each round the lanes whose source range ends at or below that
@@ -540,7 +529,7 @@ __global__ __launch_bounds__(256) void k_lz_resolve(const BgzfBlock *__restrict_
             // 200 bytes costs four wave steps, not 200 dependent round trips of its one lane.  Owner of byte x = the lane whose
             // running length first exceeds x (binary search over the lanes' inclusive prefix sums, 6 shuffles).
             const u32 glen = go ? len : 0u;
-            const u32 incl = wave_incl_scan_u32(glen), excl = incl - glen;
+            const u32 incl = covsc::wave_incl_scan(glen), excl = incl - glen;
             const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
             for (u32 base = 0; base < total; base += 64u) {
                 const u32 x = base + (u32)lane;
@@ -630,7 +619,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k
         const bool far = mine && src + (int)len <= P0a;
         {
             const u32 glen = far ? len : 0u;
-            const u32 incl = wave_incl_scan_u32(glen), excl = incl - glen;
+            const u32 incl = covsc::wave_incl_scan(glen), excl = incl - glen;
             const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
             for (u32 base = 0; base < total; base += 64u) {
                 const u32 x = base + (u32)lane;

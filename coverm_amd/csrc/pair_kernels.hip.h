@@ -202,61 +202,7 @@ __global__ __launch_bounds__(256) void k_pair_judge_list(PairCols C, const uint2
     judge_pair(C, f, pairs[g].x, pairs[g].y, partner, first_err, err_missing, err_badtype);
 }
 
-// ---------------------------------------------------------------------------------------------- device-wide exclusive scan
-// Three launches: per-block sums (4096 items per block), one workgroup scans the block sums, every block re-reads its items and
-// hands (item, exclusive prefix) to the consumer.  F: value of item i; O: consumer.
-constexpr u32 SCAN_ITEMS = 16, SCAN_BLOCK = 256 * SCAN_ITEMS;
-
-__device__ __forceinline__ u32 wave_incl_scan(u32 x) {
-    for (int o = 1; o < 64; o <<= 1) { const u32 y = __shfl_up(x, o); if ((int)(threadIdx.x & 63) >= o) x += y; }
-    return x;
-}
-// exclusive prefix of x over the 256 threads of the workgroup; *total receives the workgroup's sum
-__device__ __forceinline__ u32 block_excl_scan(u32 x, u32 *total) {
-    __shared__ u32 wsum[4];
-    const u32 incl = wave_incl_scan(x);
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
-    __syncthreads();
-    u32 base = 0;
-    for (u32 w = 0; w < (threadIdx.x >> 6); w++) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + incl - x;
-}
-
-template <typename F>
-__global__ __launch_bounds__(256) void k_scan_sums(F f, u32 n, u32 *__restrict__ block_sums) {
-    const u32 i0 = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
-    u32 s = 0;
-    for (u32 k = 0; k < SCAN_ITEMS; k++) if (i0 + k < n) s += f(i0 + k);
-    u32 total;
-    (void)block_excl_scan(s, &total);
-    if (threadIdx.x == 0) block_sums[blockIdx.x] = total;
-}
-// block_sums[0 .. nb) -> exclusive prefixes in place, grand total at block_sums[nb]  (64-bit total at total64)
-__global__ __launch_bounds__(1024) void k_scan_offsets(u32 *__restrict__ block_sums, u32 nb, u64 *__restrict__ total64) {
-    __shared__ u64 part[1024];
-    const u32 t = threadIdx.x, per = (nb + 1023u) / 1024u, k0 = t * per, k1 = min(nb, k0 + per);
-    u64 s = 0;
-    for (u32 k = k0; k < k1; k++) s += block_sums[k];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) { u64 a = 0; for (u32 i = 0; i < 1024; i++) { const u64 x = part[i]; part[i] = a; a += x; } *total64 = a; }
-    __syncthreads();
-    u64 a = part[t];
-    for (u32 k = k0; k < k1; k++) { const u32 x = block_sums[k]; block_sums[k] = (u32)a; a += x; }
-    if (t == 0) block_sums[nb] = (u32)*total64;
-}
-template <typename F, typename O>
-__global__ __launch_bounds__(256) void k_scan_apply(F f, O out, u32 n, const u32 *__restrict__ block_offs) {
-    const u32 i0 = blockIdx.x * SCAN_BLOCK + threadIdx.x * SCAN_ITEMS;
-    u32 v[SCAN_ITEMS], s = 0;
-    for (u32 k = 0; k < SCAN_ITEMS; k++) { v[k] = i0 + k < n ? f(i0 + k) : 0u; s += v[k]; }
-    u32 total;
-    u32 p = block_offs[blockIdx.x] + block_excl_scan(s, &total);
-    for (u32 k = 0; k < SCAN_ITEMS; k++) { if (i0 + k < n) out(i0 + k, p); p += v[k]; }
-}
-
+// ---------------------------------------------------------------------------------------------- items and consumers of the device-wide scan (scan_ops.hip.h)
 struct PairSlots { const u32 *partner; __device__ u32 operator()(u32 i) const { return partner[i] != NONE ? 2u : 0u; } };
 struct PairEmit {      // order[p] = first, order[p + 1] = second
     const u32 *partner; u32 *order;

@@ -22,6 +22,7 @@
 
 #define HSTC_FN __host__ __device__ __forceinline__
 #include "hist_stats_core.h"
+#include "scan_ops.hip.h"
 
 namespace covk {
 
@@ -91,62 +92,7 @@ struct Records {
     u32 cigar_end;   // one past the largest index cigar_off can address (for clamped speculative loads)
 };
 
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
-
-// Inclusive wave64 prefix sum with DPP lane moves (VALU latency, no LDS crossbar round trips):
-// row_shr 1/2/4/8 inside each row of 16 lanes, then row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2-3.
-__device__ __forceinline__ int wave_incl_scan(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
-    return v;
-}
-// Inclusive wave64 running maximum (same DPP schedule as wave_incl_scan; lanes without a source keep INT_MIN).
-__device__ __forceinline__ int wave_incl_max(int v) {
-    const int NEG = (int)0x80000000;
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x111, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x112, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x114, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x118, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x142, 0xa, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(NEG, v, 0x143, 0xc, 0xf, false));
-    return v;
-}
-__device__ __forceinline__ u64 wave_sum_u64(u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ u32 wave_sum_u32(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ u32 wave_min_u32(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, (u32)__shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ u32 wave_max_u32(u32 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, (u32)__shfl_xor(v, o));
-    return v;
-}
-
-// Wave totals by DPP prefix sums (VALU only; the __shfl_xor versions above go through the LDS crossbar, twelve round trips for a u64).  Every lane
-// returns the total.  wave_sum_u56: two 24-bit-apart halves, each summed in 32 bits — exact while the 64 values are below 2^50 (callers test that).
-__device__ __forceinline__ u32 wave_sum_u32_dpp(u32 v) { return (u32)__builtin_amdgcn_readlane(wave_incl_scan((int)v), 63); }
-__device__ __forceinline__ u64 wave_sum_u56(u64 v) {
-    const u32 lo = (u32)v & 0xffffffu, hi = (u32)(v >> 24);
-    return (u64)wave_sum_u32_dpp(lo) + ((u64)wave_sum_u32_dpp(hi) << 24);
-}
-__device__ __forceinline__ u32 wave_max_u32_dpp(u32 v) {      // (wave_incl_max compares as signed: flip the top bit)
-    return (u32)__builtin_amdgcn_readlane(wave_incl_max((int)(v ^ 0x80000000u)), 63) ^ 0x80000000u;
-}
-__device__ __forceinline__ u32 wave_min_u32_dpp(u32 v) { return ~wave_max_u32_dpp(~v); }
+using namespace covsc;      // lane_id, the wave scans and totals, block_incl_scan, blocks_in_front: scan_ops.hip.h
 
 // broadcast of lane q's value through the scalar unit (v_readlane), far cheaper than a ds_bpermute shuffle
 __device__ __forceinline__ double bcast_f64(double v, int q) {
@@ -822,40 +768,27 @@ __global__ __launch_bounds__(1024) void k_tile_scan1(ScanPair sp, u32 n_tiles, u
     const u32 which = blockIdx.x >= n_blocks ? 1u : 0u, blk = blockIdx.x - which * n_blocks;
     const u32 *__restrict__ tcnt = sp.cnt[which];
     const u32 t = blk * 1024u + threadIdx.x;
-    const int lane = lane_id(), w = threadIdx.x >> 6;
     const u32 v = t < n_tiles ? tcnt[t] : 0u;
-    const u32 inc = (u32)wave_incl_scan((int)v);
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    u32 wbase = 0, tot = 0;
-    for (int k = 0; k < 16; k++) { const u32 x = wtot[k]; if (k < w) wbase += x; tot += x; }
-    if (t < n_tiles) sp.scan[which][t] = wbase + inc - v;
+    u32 tot;
+    const u32 inc = block_incl_scan<16>(v, wtot, tot);
+    if (t < n_tiles) sp.scan[which][t] = inc - v;
     if (threadIdx.x == 0) sp.top[which][blk] = tot;
 }
 
 __global__ __launch_bounds__(1024) void k_tile_scan2(ScanPair sp, u32 n_blocks) {
     __shared__ u32 wtot[16];
-    __shared__ u32 carry_s;
     u32 *ttop = sp.top[blockIdx.x];
     u64 *total = sp.total[blockIdx.x];
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    const int lane = lane_id(), w = threadIdx.x >> 6;
+    u32 carry = 0;      // the sum of the batches in front: every thread holds it
     for (u32 base = 0; base < n_blocks; base += 1024u) {
         const u32 b = base + threadIdx.x;
         const u32 v = b < n_blocks ? ttop[b] : 0u;
-        const u32 inc = (u32)wave_incl_scan((int)v);
-        if (lane == 63) wtot[w] = inc;
-        __syncthreads();
-        u32 wbase = 0, tot = 0;
-        for (int k = 0; k < 16; k++) { const u32 x = wtot[k]; if (k < w) wbase += x; tot += x; }
-        const u32 carry = carry_s;
-        if (b < n_blocks) ttop[b] = carry + wbase + inc - v;
-        __syncthreads();
-        if (threadIdx.x == 0) carry_s = carry + tot;
-        __syncthreads();
+        u32 tot;
+        const u32 inc = block_incl_scan<16>(v, wtot, tot);
+        if (b < n_blocks) ttop[b] = carry + inc - v;
+        carry += tot;
     }
-    if (total != nullptr && threadIdx.x == 0) *total = carry_s;
+    if (total != nullptr && threadIdx.x == 0) *total = carry;
 }
 
 // Expansion of RW_BUCKET records (long CIGARs): one wave per record walks the CIGAR 64 operations per step (as
@@ -985,42 +918,24 @@ __device__ __forceinline__ u64 hist_bins_of(const DevContig *C, u32 c, const u32
     if (MODE == 0) return live ? (u64)C->hist_cap + 1 : 0;
     return (live && 2 * excl < (u64)tlen[c]) ? (u64)C->max_d + 1 : 0;
 }
-// inclusive scan over the 1024 threads of a block (16 waves); returns this thread's inclusive prefix, `total` = the block's sum
-__device__ __forceinline__ u64 block_incl_scan_u64(u64 v, u64 *wtot, u64 &total) {
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    u64 inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) wtot[w] = inc;
-    __syncthreads();
-    u64 wbase = 0; total = 0;
-    for (int k = 0; k < 16; k++) { const u64 x = wtot[k]; if (k < w) wbase += x; total += x; }
-    __syncthreads();
-    return wbase + inc;
-}
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_hist_sum(const DevContig *__restrict__ ctg, u32 n_targets, const u32 *__restrict__ tlen,
                                                    const uint8_t *__restrict__ mask, u64 excl, u64 *__restrict__ top) {
     __shared__ u64 wtot[16];
     const u32 c = blockIdx.x * 1024u + threadIdx.x;
     u64 total;
-    (void)block_incl_scan_u64(c < n_targets ? hist_bins_of<MODE>(&ctg[c], c, tlen, mask, excl) : 0, wtot, total);
+    (void)block_incl_scan<16>(c < n_targets ? hist_bins_of<MODE>(&ctg[c], c, tlen, mask, excl) : 0ull, wtot, total);
     if (threadIdx.x == 0) top[blockIdx.x] = total;
 }
 template <int MODE>
 __global__ __launch_bounds__(1024) void k_hist_off(DevContig *ctg, u32 n_targets, const u32 *__restrict__ tlen, const uint8_t *__restrict__ mask,
                                                    u64 excl, const u64 *__restrict__ top, DevGlobal *g) {
     __shared__ u64 wtot[16];
-    u64 mine = 0, base;
-    for (u32 b = threadIdx.x; b < blockIdx.x; b += 1024u) mine += top[b];
-    (void)block_incl_scan_u64(mine, wtot, base);          // base = bins of all contigs in front of this block
+    const u64 base = blocks_in_front<16>(top, wtot);      // bins of all contigs in front of this block
     const u32 c = blockIdx.x * 1024u + threadIdx.x;
     const u64 v = c < n_targets ? hist_bins_of<MODE>(&ctg[c], c, tlen, mask, excl) : 0;
     u64 total;
-    const u64 inc = block_incl_scan_u64(v, wtot, total);
+    const u64 inc = block_incl_scan<16>(v, wtot, total);
     if (c < n_targets) {
         if (MODE == 0) ctg[c].hist_off = base + inc - v;
         else { ctg[c].chist_off = base + inc - v; ctg[c].hist_len = (u32)v; }
@@ -1255,9 +1170,7 @@ __device__ __forceinline__ void id_block_add(double &S, const double xv, const i
         bool tie = false;
         const u64 t = irregular ? 0ull : id_units(xv, e_cur, tie);        // <= 2^52 for x <= 1, e >= 1
         const bool in_range = (u32)lane >= q;
-        u64 P = in_range ? t : 0ull;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const u64 u = __shfl_up(P, o); if (lane >= o) P += u; }
+        const u64 P = wave_incl_scan_u64(in_range ? t : 0ull);
         const bool fits = in_range && !tie && !irregular && m + P < (1ull << 53);
         const u64 failm = __ballot(in_range && !fits);
         const u32 jstar = failm ? (u32)(__ffsll((long long)failm) - 1) : 64u;
@@ -1322,9 +1235,7 @@ __global__ __launch_bounds__(64) void k_id_combine(DevContig *ctg, u32 n_targets
                     const int e_cur = (int)((bits >> 52) & 0x7ff) - 1023;
                     const u64 m = (bits & 0xfffffffffffffull) | (1ull << 52);
                     const bool in_range = (u32)lane >= q && (u32)lane < nb;
-                    u64 P = in_range ? t_l : 0ull;
-#pragma unroll
-                    for (int o = 1; o < 64; o <<= 1) { const u64 t = __shfl_up(P, o); if (lane >= o) P += t; }
+                    const u64 P = wave_incl_scan_u64(in_range ? t_l : 0ull);
                     const bool fits = in_range && !bad_l && !(bits >> 63) && e_l == e_cur && t_l < (1ull << 53) &&
                                       P < (1ull << 53) && m + P < (1ull << 53);
                     const u64 failm = __ballot(in_range && !fits);
@@ -2016,14 +1927,6 @@ __device__ __forceinline__ u64 est_f32_to_usize(float x) {                      
     if (!(x == x) || x <= 0.0f) return 0ull;
     if (x >= 18446744073709551616.0f) return ~0ull;
     return (u64)x;
-}
-__device__ __forceinline__ u64 wave_incl_scan_u64(u64 v) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const u64 t = __shfl_up(v, o);
-        if (lane_id() >= o) v += t;
-    }
-    return v;
 }
 
 // The trimmed mean's total (estimators.rs:596-640, restated over prefix sums as described above) by the WHOLE wave for one entry: 64 bins per

@@ -2,11 +2,11 @@
 //
 //   k_sam_masks      structure in one coalesced pass: every lane loads 16 bytes (one dwordx4), compares them with '\n' and '\t', four lanes
 //                    fold their 16-bit masks into one 64-bit word with three shuffles; per 64 input bytes one word of each mask is written
-//   covp::k_scan_*   lines: popcount of the newline words, the device-wide exclusive scan of pair_kernels.hip.h (the one the pair filter, the
+//   covsc::k_scan_*  lines: popcount of the newline words, the device-wide exclusive scan of scan_ops.hip.h (the one the pair filter, the
 //                    store gather and the grouping use), whose consumer (LineEmit) writes every line's end offset at the line's index
 //   k_sam_count      a lane per line: record or not (empty, header), well formed or not, number of CIGAR words.  Tabs come from the tab
 //                    masks, so SEQ and QUAL are jumped over, not walked.  Errors: min over (line index, code), never a race between lanes
-//   covp::k_scan_*   twice: records before each line, CIGAR words before each line
+//   covsc::k_scan_*  twice: records before each line, CIGAR words before each line
 //   k_sam_decode     a lane per line: every field into the store's columns, CIGAR words at their scanned offset; with mates the
 //                    next_refID and covn::name_hash of QNAME (name_hash_core.h) — the very function k_bam_extract calls
 // The arithmetic is sam_parse_core.h's (shared with the CPU emulation, tests/c/sam_parse_host.cpp).
@@ -16,7 +16,7 @@
 
 #define SAMC_FN __host__ __device__ __forceinline__
 #include "sam_parse_core.h"
-#include "pair_kernels.hip.h"
+#include "scan_ops.hip.h"
 
 namespace covs {
 

@@ -23,7 +23,6 @@
 namespace covk {
 
 constexpr u32 SEP_TILE = sepc::SCAN_TILE;
-static_assert(SEP_TILE == 1024u, "block_incl_scan_u64 / block_incl_max_u32 scan 16 waves");
 
 struct SepEntry { u32 first_tid; int32_t gid; };      // of the entry's starting target q: blk[q], gid[q]
 
@@ -35,8 +34,8 @@ __global__ __launch_bounds__(1024) void k_sep_obs_top(const DevContig *__restric
     const u32 t = blockIdx.x * SEP_TILE + threadIdx.x;
     const bool obs = t < n_targets && ctg[t].n_pass != 0;
     u32 last1, first_inv;
-    (void)block_incl_max_u32(obs ? t + 1u : 0u, wmax, last1);
-    (void)block_incl_max_u32(obs ? ~t : 0u, wmax, first_inv);      // (~t > 0 for every tid; 0 = none -> NONE)
+    (void)block_incl_scan<16>(obs ? t + 1u : 0u, wmax, last1, Max{});
+    (void)block_incl_scan<16>(obs ? ~t : 0u, wmax, first_inv, Max{});      // (~t > 0 for every tid; 0 = none -> NONE)
     if (threadIdx.x == 0) { top_last1[blockIdx.x] = last1; top_first[blockIdx.x] = ~first_inv; }
 }
 
@@ -47,19 +46,17 @@ __global__ __launch_bounds__(1024) void k_sep_flags(const DevContig *__restrict_
     __shared__ u64 wtot[16];
     __shared__ u32 s_prev1[SEP_TILE], s_next[SEP_TILE];
     const u32 b = blockIdx.x, nb = gridDim.x;
-    u32 mine = 0, base_prev1, base_next_inv, tot;
-    for (u32 k = threadIdx.x; k < b; k += SEP_TILE) mine = max(mine, top_last1[k]);
-    (void)block_incl_max_u32(mine, wmax, base_prev1);          // 1 + the nearest observed tid in front of this workgroup
-    mine = 0;
+    const u32 base_prev1 = blocks_in_front<16>(top_last1, wmax, Max{});      // 1 + the nearest observed tid in front of this workgroup
+    u32 mine = 0, base_next_inv, tot;
     for (u32 k = b + 1u + threadIdx.x; k < nb; k += SEP_TILE) mine = max(mine, ~top_first[k]);
-    (void)block_incl_max_u32(mine, wmax, base_next_inv);       // ~ the nearest observed tid behind it
+    (void)block_incl_scan<16>(mine, wmax, base_next_inv, Max{});       // ~ the nearest observed tid behind it
     const u32 t = b * SEP_TILE + threadIdx.x;
     const bool obs = t < n_targets && ctg[t].n_pass != 0;
-    const u32 prev1 = max(base_prev1, block_incl_max_u32(obs ? t + 1u : 0u, wmax, tot));
+    const u32 prev1 = max(base_prev1, block_incl_scan<16>(obs ? t + 1u : 0u, wmax, tot, Max{}));
     // from the right: thread j scans target SEP_TILE - 1 - j of the workgroup
     const u32 jr = SEP_TILE - 1u - threadIdx.x, tr = b * SEP_TILE + jr;
     const bool obs_r = tr < n_targets && ctg[tr].n_pass != 0;
-    const u32 next_inv = max(base_next_inv, block_incl_max_u32(obs_r ? ~tr : 0u, wmax, tot));
+    const u32 next_inv = max(base_next_inv, block_incl_scan<16>(obs_r ? ~tr : 0u, wmax, tot, Max{}));
     s_prev1[threadIdx.x] = prev1; s_next[jr] = ~next_inv;
     __syncthreads();
     const u32 next = s_next[threadIdx.x];
@@ -71,7 +68,7 @@ __global__ __launch_bounds__(1024) void k_sep_flags(const DevContig *__restrict_
         code[t] = (uint8_t)(start | (m << 1));
     }
     u64 total;
-    (void)block_incl_scan_u64(((u64)start << 32) | (m != sepc::NOT_MEMBER ? 1ull : 0ull), wtot, total);
+    (void)block_incl_scan<16>(((u64)start << 32) | (m != sepc::NOT_MEMBER ? 1ull : 0ull), wtot, total);
     if (threadIdx.x == 0) top_cnt[b] = total;
 }
 
@@ -79,12 +76,11 @@ __global__ __launch_bounds__(1024) void k_sep_compact(u32 n_targets, const int32
                                                       const u64 *__restrict__ top_cnt, u32 *__restrict__ tids, u32 *__restrict__ ent_of_pos,
                                                       SepEntry *__restrict__ ent, u32 ent_cap, u32 *__restrict__ counts, DevGlobal *__restrict__ glob) {
     __shared__ u64 wtot[16];
-    u64 mine = 0, base, total;
-    for (u32 k = threadIdx.x; k < blockIdx.x; k += SEP_TILE) mine += top_cnt[k];
-    (void)block_incl_scan_u64(mine, wtot, base);
+    const u64 base = blocks_in_front<16>(top_cnt, wtot);
+    u64 total;
     const u32 t = blockIdx.x * SEP_TILE + threadIdx.x;
     const u32 c = t < n_targets ? code[t] : 0u, start = c & 1u, m = c >> 1;
-    const u64 inc = base + block_incl_scan_u64(((u64)start << 32) | (m != sepc::NOT_MEMBER ? 1ull : 0ull), wtot, total);
+    const u64 inc = base + block_incl_scan<16>(((u64)start << 32) | (m != sepc::NOT_MEMBER ? 1ull : 0ull), wtot, total);
     const u32 starts_incl = (u32)(inc >> 32);
     if (start && starts_incl - 1u < ent_cap) { SepEntry e; e.first_tid = blk[t]; e.gid = gid[t]; ent[starts_incl - 1u] = e; }
     if (m != sepc::NOT_MEMBER) {
@@ -114,18 +110,17 @@ __global__ __launch_bounds__(1024) void k_sep_seg_sum(const u32 *__restrict__ co
     __shared__ u64 wtot[16];
     const u32 e = blockIdx.x * SEP_TILE + threadIdx.x;
     u64 total;
-    (void)block_incl_scan_u64(e < counts[SEP_N_ENTRIES] ? (u64)sep_segments_of(row, e) : 0ull, wtot, total);
+    (void)block_incl_scan<16>(e < counts[SEP_N_ENTRIES] ? (u64)sep_segments_of(row, e) : 0ull, wtot, total);
     if (threadIdx.x == 0) top[blockIdx.x] = total;
 }
 __global__ __launch_bounds__(1024) void k_sep_seg_write(u32 *__restrict__ counts, const u32 *__restrict__ row, const u64 *__restrict__ top, u32 *__restrict__ seg_genome,
                                                         u32 *__restrict__ seg_start, u32 seg_cap) {
     __shared__ u64 wtot[16];
-    u64 mine = 0, base, total;
-    for (u32 k = threadIdx.x; k < blockIdx.x; k += SEP_TILE) mine += top[k];
-    (void)block_incl_scan_u64(mine, wtot, base);
+    const u64 base = blocks_in_front<16>(top, wtot);
+    u64 total;
     const u32 e = blockIdx.x * SEP_TILE + threadIdx.x;
     const u32 ns = e < counts[SEP_N_ENTRIES] ? sep_segments_of(row, e) : 0u;
-    const u64 inc = base + block_incl_scan_u64((u64)ns, wtot, total);
+    const u64 inc = base + block_incl_scan<16>((u64)ns, wtot, total);
     u32 sg = (u32)(inc - ns);
     for (u32 k = 0, i = ns ? row[e] : 0u; k < ns && sg < seg_cap; k++, sg++, i += GENOME_SEG) { seg_genome[sg] = e; seg_start[sg] = i; }
     if (blockIdx.x == gridDim.x - 1u && threadIdx.x == 0) counts[SEP_N_SEG] = (u32)min(base + total, (u64)seg_cap);

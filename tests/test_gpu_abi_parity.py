@@ -463,6 +463,38 @@ def test_assemblies_of_many_short_contigs():
     compare(b, ff=(True, True, False), excl=75, mask=mask)
 
 
+def _records_on_the_last_contigs(ref_lens, first, n_reads, seed):
+    """synth reads over the contigs [first, end) of ref_lens alone: the oracle walks only contigs with records, whatever lies in front."""
+    sub = synth.SynthReference([], np.asarray(ref_lens[first:], np.int64), np.zeros(len(ref_lens) - first, np.int32), [])
+    batch = synth.make_reads(sub, n_reads, seed=seed)
+    batch.tid = (batch.tid + first).astype(np.int32)
+    return batch
+
+
+@pytest.mark.parametrize("n_contigs", [1025, 2049])
+def test_one_and_two_blocks_of_tiles_and_contigs_in_front(n_contigs):
+    """Contigs of one tile each: the scans over tiles (candidate ranges) and over contigs (both histogram layouts) have exactly one and two
+    workgroups of 1 024 in front of their last one, with records on both sides of every border and of the wave border 63 | 64."""
+    ref = synth.make_reference(n_contigs, n_contigs * 650, seed=71, min_len=400, max_len=1000)
+    assert ref.lengths.max() <= 1024
+    b = to_bamdata(synth.make_reads(ref, 8 * n_contigs, seed=74), ref.lengths, ref.names)
+    considered = np.bincount(b.tid[(b.flag & 0x904) == 0], minlength=n_contigs)
+    borders = [63, 64] + [k for k in (1023, 1024, 2047, 2048) if k < n_contigs]
+    assert (considered[borders] > 0).all() and (considered > 1).sum() > n_contigs // 2
+    compare(b, ff=(True, True, False), excl=75, check_depth=[1023, 1024, n_contigs - 1])
+
+
+def test_block_totals_of_the_tile_scan_in_two_batches():
+    """More than 1 024 x 1 024 tiles: k_tile_scan2 takes the block totals in two batches of 1 024 and carries the first batch's sum into
+    the second.  The first contig is half a block of tiles long, so every later contig's tiles lie in two blocks; contig 1 024 has its
+    first tile in block 1 023 and its last ones in block 1 024, on the two sides of the batch border.  Records on the last five contigs only."""
+    ref_lens = np.full(1026, 1 << 20, np.int64)
+    ref_lens[0] = 1 << 19
+    batch = _records_on_the_last_contigs(ref_lens, 1021, 40_000, seed=73)
+    assert set(np.unique(batch.tid)) == set(range(1021, 1026))
+    compare(to_bamdata(batch, ref_lens), ff=(True, True, False), excl=75)
+
+
 def _piles_between_the_bin_counts():
     """Contigs whose depth climbs through 384 and 512: interior tiles leave the stripped loop (candidates >= bins) at different depths in
     the two variants, and the general loop's segments cross from the LDS bins into the arena."""

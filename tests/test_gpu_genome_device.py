@@ -199,6 +199,19 @@ def test_every_genome_its_own_contig_lane_per_genome():
     check_sample(ref.lengths, batch, g_of, 70_000, 75)
 
 
+@pytest.mark.parametrize("n_contigs", [1025, 2049])
+def test_one_and_two_blocks_of_genomes_and_contigs_in_front(n_contigs):
+    """Every contig its own genome, one tile each: the layout of the merged histograms (a scan over genomes) and the order rule of
+    cov_finish_genomes (a running maximum over contigs) have exactly one and two workgroups of 1 024 in front of their last one, with
+    reads in the genomes and contigs on both sides of every border."""
+    ref = synth.make_reference(n_contigs, n_contigs * 650, seed=71, min_len=400, max_len=1000)
+    batch = synth.make_reads(ref, 8 * n_contigs, seed=74)
+    considered = np.bincount(batch.tid[(batch.flag & 0x904) == 0], minlength=n_contigs)
+    borders = [63, 64] + [k for k in (1023, 1024, 2047, 2048) if k < n_contigs]
+    assert (considered[borders] > 0).all()
+    check_sample(ref.lengths, batch, np.arange(n_contigs, dtype=np.int32), n_contigs, 75, sets=estimator_sets(75)[:1])
+
+
 def test_after_a_spill_the_genome_fetches_say_so(monkeypatch):
     set_knobs(monkeypatch, store_cap_records=40000)
     ref = synth.make_reference(150, 12_000_000, seed=11, min_len=1500, max_len=300_000)

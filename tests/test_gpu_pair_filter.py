@@ -90,6 +90,46 @@ def test_synthetic_pairs_with_repeated_names(tmp_path, monkeypatch, params, chun
     assert nprim == prim
 
 
+def _adjacent_pairs(n):
+    """n records on one contig: record 0 alone (its mate is not in the file), then the pairs (1, 2), (3, 4), ...; an even n leaves the last
+    record alone as well.  Every third pair misses the identity bound and every fifth record has a CIGAR of three words, so neither scan's
+    items (two slots at a kept pair's second record; a selected record's CIGAR words) are all equal."""
+    i = np.arange(n)
+    pair = (i + 1) // 2                                        # 0: record 0; k >= 1: records 2 k - 1 and 2 k
+    alone = (i == 0) | ((i == n - 1) & (n % 2 == 0))
+    second = ~alone & (i % 2 == 0)
+    flag = np.where(second, 147, 99).astype(np.uint16)
+    nm = np.where(pair % 3 == 0, 40, i % 4).astype(np.uint32)
+    three = i % 5 == 0
+    n_ops = np.where(three, 3, 1)
+    coff = np.zeros(n + 1, np.uint32)
+    np.cumsum(n_ops, out=coff[1:])
+    cigar = np.zeros(int(coff[-1]), np.uint32)
+    cigar[coff[:-1]] = np.where(three, 50 << 4, 100 << 4)
+    cigar[coff[:-1][three] + 1] = (2 << 4) | 1                 # 50M 2I 50M
+    cigar[coff[:-1][three] + 2] = 50 << 4
+    z = np.zeros(n, np.int32)
+    return bamio.BamData(["c0"], np.asarray([10 * n + 1000], np.int64), z, (10 * i).astype(np.int32), flag, np.full(n, 30, np.uint8),
+                         np.where(three, 102, 100).astype(np.int32), nm, np.ones(n, np.uint8), coff, cigar, z, z, z,
+                         [b"q%d" % (n + k if a else p) for k, (p, a) in enumerate(zip(pair, alone))], "")
+
+
+@pytest.mark.parametrize("n", [4095, 4096, 4097, 8193])
+def test_the_scan_blocks_of_4096_records(tmp_path, n):
+    """The device-wide scan takes 4 096 items per workgroup, and the pair filter's items are the records: one item short of a block, a whole
+    block, one item into the second block (the kept pair 4 095 | 4 096 lies on both sides of the border), one item into the third."""
+    b = _adjacent_pairs(n)
+    p = str(tmp_path / "edge.bam")
+    bamio.write_bam(p, b, level=1)
+    ofp = O.FilterParameters(O.FlagFilter(True, True, False), min_percent_identity_pair=0.95)
+    got, nprim = _device_selection(p, ofp, threads=2)
+    order, prim = _expect(b, ofp)
+    kept = (n - 1) // 2 - (n - 1) // 6                            # the pairs 1 .. (n - 1) / 2 but for every third
+    assert len(order) == 2 * kept and (n < 4097 or {4095, 4096} <= set(order.tolist())) and (n < 8193 or {8191, 8192} <= set(order.tolist()))
+    _compare(got, b, order)
+    assert nprim == prim
+
+
 def test_missing_nm_in_a_judged_pair_is_the_references_panic(tmp_path):
     b = _paired_sample(3_000, seed=5)
     ofp = O.FilterParameters(O.FlagFilter(True, True, False), min_percent_identity_pair=0.9)
