@@ -12,6 +12,7 @@
 #include "gene_kernels.hip.h"
 #include "depth_kernels.hip.h"
 #include "depth_bins_kernels.hip.h"
+#include "depth_regions_kernels.hip.h"
 
 #include <algorithm>
 #include <atomic>
@@ -56,6 +57,10 @@ static_assert(sizeof(cov_depth_bin) == 24 && sizeof(cov_depth_bin) == sizeof(dbn
               offsetof(dbnc::Bin, max) == 12 && offsetof(cov_depth_bin, covered) == 16 && offsetof(dbnc::Bin, covered) == 16 && offsetof(cov_depth_bin, reserved) == 20 &&
               sizeof(cov_depth_bins_info) == 48 && offsetof(cov_depth_bins_info, tid_lo) == 32 && offsetof(cov_depth_bins_info, bin_size) == 40,
               "cov_depth_bin mirrors the device struct (numpy mirror in coverm_amd/native.py)");
+static_assert(sizeof(cov_depth_region) == 16 && sizeof(cov_depth_region) == sizeof(drgc::Region) && offsetof(cov_depth_region, start) == 4 && offsetof(drgc::Region, start) == 4 &&
+              offsetof(cov_depth_region, end) == 8 && offsetof(drgc::Region, end) == 8 && offsetof(cov_depth_region, reserved) == 12 && sizeof(drgc::Desc) == 16 &&
+              sizeof(cov_depth_regions_info) == 48 && offsetof(cov_depth_regions_info, n_pieces) == 16 && offsetof(cov_depth_regions_info, tid_lo) == 40,
+              "cov_depth_region mirrors the core's struct (numpy mirror in coverm_amd/native.py)");
 static_assert(sizeof(cov_interval_reads) == 32 && sizeof(cov_interval_reads) == sizeof(covgn::Out) && offsetof(cov_interval_reads, sum_identity) == offsetof(covgn::Out, sum_identity) &&
               offsetof(cov_interval_reads, contig_taken) == offsetof(covgn::Out, contig_taken) && sizeof(cov_interval) == sizeof(gnrc::Interval) &&
               offsetof(cov_interval, start) == offsetof(gnrc::Interval, start), "cov_interval_reads mirrors the device struct");
@@ -294,16 +299,42 @@ struct cov_session {
         hipEvent_t ev_mid = nullptr;
         float arena_ms = 0.f, runs_ms = 0.f;              // of the last chunk: the pileup into the arena; the run kernels (COV_K_DEPTH_RUNS)
         // depth bins (cov_depth_bins_compute / _fetch, depth_bins_kernels.hip.h): the same arena, mask and rank; the chunk's bins and the
-        // targets' bin offsets.  The arena holds ONE chunk: a compute of the runs drops the bins and the reverse (bins_took_arena /
-        // runs_took_arena: what the refused fetch says).
+        // targets' bin offsets.  The arena holds ONE chunk: a compute of the runs drops the bins and the reverse (take_arena below).
         DevBuf<dbnc::Bin> bins; DevBuf<u32> bin_off;
         std::vector<u64> h_bin_off; std::vector<u32> h_bin_off32;
-        bool bins_valid = false, bins_took_arena = false, runs_took_arena = false;
+        bool bins_valid = false;
+        // The arena holds ONE chunk of ONE of the three parties (runs, bins, regions): taker[x] = the party whose compute took the arena
+        // from under x's chunk (0: nobody), which is what x's refused fetch names.
+        enum Party : int { RUNS = 0, BINS = 1, REGIONS = 2 };
+        uint8_t taker[3] = {0, 0, 0};
+        bool &valid_of(int party) { return party == RUNS ? valid : party == BINS ? bins_valid : regs_valid; }
+        void take_arena(int party) {
+            for (int o = 0; o < 3; o++)
+                if (o != party && valid_of(o)) { valid_of(o) = false; taker[o] = (uint8_t)(party + 1); }
+            valid_of(party) = false; taker[party] = 0;
+        }
+        static const char *party_name(int party) { return party == RUNS ? "cov_depth_runs" : party == BINS ? "cov_depth_bins" : "cov_depth_regions"; }
+        // the fetch of `party` that lost its chunk: empty when it did not
+        std::string lost(int party) const {
+            if (!taker[party]) return std::string();
+            return std::string(party_name(party)) + "_fetch: the chunk's arena was taken by a " + party_name(taker[party] - 1) + "_compute since (" + party_name(party) + "_compute again)";
+        }
         u32 b_lo = 0, b_next = 0, b_launches = 0, bin_size = 0;
         u64 n_bins = 0, b_arena_bases = 0;
         float b_arena_ms = 0.f, bins_ms = 0.f;            // of the last chunk of bins (COV_K_DEPTH_BINS)
-        void drop() { valid = false; bins_valid = false; bins_took_arena = false; runs_took_arena = false; }      // push / reset / finish: neither is there
-        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); bins.release(); bin_off.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
+        // depth regions (cov_depth_regions_set / _compute / _fetch, depth_regions_kernels.hip.h): the session's regions in a stable order by
+        // tid (h_reg; h_reg_input: their positions in the caller's array; h_reg_first: CSR over the targets), and of the last chunk the
+        // descriptors, the piece offsets and the results.  cov_set_targets drops the regions; reset and finish keep them.
+        std::vector<drgc::Region> h_reg; std::vector<u32> h_reg_input, h_reg_first;
+        bool have_regions = false;
+        DevBuf<drgc::Desc> reg_desc; DevBuf<u32> reg_piece_off; DevBuf<dbnc::Bin> regs;
+        std::vector<drgc::Desc> h_reg_desc; std::vector<u32> h_reg_piece_off;
+        bool regs_valid = false;
+        u32 g_lo = 0, g_next = 0, g_launches = 0, g_first = 0;      // g_first: the chunk's first region in h_reg
+        u64 n_regs = 0, n_pieces = 0, g_arena_bases = 0;
+        float g_arena_ms = 0.f, regs_ms = 0.f;            // of the last chunk of regions (COV_K_DEPTH_REGIONS)
+        void drop() { valid = false; bins_valid = false; regs_valid = false; taker[0] = taker[1] = taker[2] = 0; }      // push / reset / finish: none is there
+        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); bins.release(); bin_off.release(); reg_desc.release(); reg_piece_off.release(); regs.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
     } dr;
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
@@ -844,6 +875,7 @@ cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *t
     s->have_mask = false;
     genomes_off(s);
     s->finished = false;
+    s->dr.h_reg.clear(); s->dr.h_reg_input.clear(); s->dr.h_reg_first.clear(); s->dr.have_regions = false; s->dr.regs_valid = false;      // the regions were validated against the targets before
     if (n_targets >= 65536u && !s->h_res_prep.valid() && result_host_bytes(s, n_targets) > s->h_res_cap) {
         const size_t need = result_host_bytes(s, n_targets);
         const int dev = s->cfg.device;
@@ -3004,11 +3036,11 @@ cov_status cov_interval_reads_compute(cov_session *s, const cov_interval *iv, ui
 // One chunk of whole targets: the arena filled by the pileup against the scratch copy of the contig block, then marks, the rank scan over
 // the start mask, count / scan / emit over the arena's words.  The one host wait in the middle reads the run count the emit's buffer needs.
 //
-// depth_arena_stage is what cov_depth_runs_compute and cov_depth_bins_compute share: the chunk's plan and layout, the buffers, the woff
+// depth_arena_stage is what cov_depth_runs_compute, cov_depth_bins_compute and cov_depth_regions_compute share: the chunk's plan and layout, the buffers, the woff
 // upload, the zero fill, k_depth_marks, the pileup against the scratch copy of the contig block (ev[0] .. ev[1]) and the rank scan.
 struct DepthChunk { u32 t1, nT, words, mw; };
 // Behind its refusal, which touches nothing, the arena is the caller's: what the other call left in it is dropped there, not earlier.
-static cov_status depth_arena_stage(cov_session *s, const char *who, bool for_bins, uint32_t tid_lo, uint32_t tid_hi, hipEvent_t *ev, DepthChunk &c) {
+static cov_status depth_arena_stage(cov_session *s, const char *who, int party, uint32_t tid_lo, uint32_t tid_hi, hipEvent_t *ev, DepthChunk &c) {
     cov_session::DepthRuns &D = s->dr;
     hipStream_t st = s->stream;
     const u32 t1 = dprc::plan_chunk(s->h_tlen.data(), tid_lo, tid_hi, D.chunk_bases), nT = t1 - tid_lo;
@@ -3016,13 +3048,7 @@ static cov_status depth_arena_stage(cov_session *s, const char *who, bool for_bi
     const u64 words64 = [&] { u64 w = 0; for (u32 k = 0; k < nT; k++) w += dprc::words_of(s->h_tlen[tid_lo + k]); return w; }();
     // (the scan's item indices and block sums are u32: a chunk stays at or below 2^32 arena entries, which one target always does)
     if (words64 > (1ull << 30)) { s->err = std::string(who) + ": a chunk of more than 2^32 arena entries (COVERM_KNOBS depth_chunk_bases)"; return COV_ERR_INVALID_ARG; }
-    if (for_bins) {      // the arena holds one chunk
-        D.bins_valid = false; D.runs_took_arena = false;
-        if (D.valid) { D.valid = false; D.bins_took_arena = true; }
-    } else {
-        D.valid = false; D.bins_took_arena = false;
-        if (D.bins_valid) { D.bins_valid = false; D.runs_took_arena = true; }
-    }
+    D.take_arena(party);      // the arena holds one chunk
     const u32 words = dprc::layout(s->h_tlen.data() + tid_lo, nT, D.h_woff.data()), mw = (words + 31u) >> 5;
     HIPCHK(D.arena.reserve(4ull * words, st)); HIPCHK(D.woff.reserve((size_t)nT + 1, st)); HIPCHK(D.mask.reserve(mw, st)); HIPCHK(D.rank.reserve(mw, st));
     HIPCHK(D.sums.reserve((size_t)scan_blocks(std::max(words, mw)) + 1, st)); HIPCHK(D.doff.reserve((size_t)s->n_targets + 1, st));
@@ -3069,7 +3095,7 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
     // ---- the arena and scan #1 (the rank of every mask word)
     DepthChunk ck;
-    if (const cov_status rc = depth_arena_stage(s, "cov_depth_runs_compute", false, tid_lo, tid_hi, ev, ck)) return rc;
+    if (const cov_status rc = depth_arena_stage(s, "cov_depth_runs_compute", cov_session::DepthRuns::RUNS, tid_lo, tid_hi, ev, ck)) return rc;
     const u32 t1 = ck.t1, nT = ck.nT, words = ck.words;
     HIPCHK(D.run_off.reserve((size_t)nT + 1, st));
     // ---- scan #2, first half: the words' run starts counted, the block offsets and the total
@@ -3107,7 +3133,7 @@ cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run
     if (!s) return COV_ERR_INVALID_ARG;
     if (s->ing.active) { s->err = "cov_depth_runs_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_depth_runs_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
-    if (s->finished && !s->dr.valid && s->dr.bins_took_arena) { s->err = "cov_depth_runs_fetch: the chunk's arena was taken by a cov_depth_bins_compute since (cov_depth_runs_compute again)"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.valid && s->dr.taker[cov_session::DepthRuns::RUNS]) { s->err = s->dr.lost(cov_session::DepthRuns::RUNS); return COV_ERR_STATE; }
     if (!s->finished || !s->dr.valid) { s->err = "cov_depth_runs_fetch: no chunk computed since the last finish (cov_depth_runs_compute)"; return COV_ERR_STATE; }
     if (!run_off || (s->dr.n_runs && !runs)) return COV_ERR_INVALID_ARG;
     static_assert(sizeof(cov_depth_run) == 8 && sizeof(cov_depth_run) == sizeof(dprc::Run) && offsetof(cov_depth_run, depth) == 4 && offsetof(dprc::Run, depth) == 4,
@@ -3154,7 +3180,7 @@ cov_status cov_depth_bins_compute(cov_session *s, uint32_t bin_size, uint32_t ti
     hipEvent_t *ev = s->ev[COV_K_DEPTH_BINS];      // events of its own: the call is not part of a finish; ev_mid closes the bin kernels
     if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
     DepthChunk ck;
-    if (const cov_status rc = depth_arena_stage(s, "cov_depth_bins_compute", true, tid_lo, tid_hi, ev, ck)) return rc;
+    if (const cov_status rc = depth_arena_stage(s, "cov_depth_bins_compute", cov_session::DepthRuns::BINS, tid_lo, tid_hi, ev, ck)) return rc;
     D.h_bin_off.resize((size_t)nT + 1); D.h_bin_off32.resize((size_t)nT + 1);
     (void)dbnc::bin_layout(s->h_tlen.data() + tid_lo, nT, bin_size, D.h_bin_off.data());
     for (u32 k = 0; k <= nT; k++) D.h_bin_off32[k] = (u32)D.h_bin_off[k];
@@ -3188,7 +3214,7 @@ cov_status cov_depth_bins_fetch(cov_session *s, uint64_t *bin_off, cov_depth_bin
     if (!s) return COV_ERR_INVALID_ARG;
     if (s->ing.active) { s->err = "cov_depth_bins_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
     if (s->spill.active) { s->err = "cov_depth_bins_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
-    if (s->finished && !s->dr.bins_valid && s->dr.runs_took_arena) { s->err = "cov_depth_bins_fetch: the chunk's arena was taken by a cov_depth_runs_compute since (cov_depth_bins_compute again)"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.bins_valid && s->dr.taker[cov_session::DepthRuns::BINS]) { s->err = s->dr.lost(cov_session::DepthRuns::BINS); return COV_ERR_STATE; }
     if (!s->finished || !s->dr.bins_valid) { s->err = "cov_depth_bins_fetch: no chunk computed since the last finish (cov_depth_bins_compute)"; return COV_ERR_STATE; }
     if (!bin_off || (s->dr.n_bins && !bins)) return COV_ERR_INVALID_ARG;
     cov_session::DepthRuns &D = s->dr;
@@ -3207,6 +3233,119 @@ cov_status cov_depth_bins_last(const cov_session *s, cov_depth_bins_info *out) {
     const cov_session::DepthRuns &D = s->dr;
     out->arena_bases = D.b_arena_bases; out->n_bins = D.n_bins; out->arena_ms = D.b_arena_ms; out->bins_ms = D.bins_ms; out->tid_lo = D.b_lo; out->tid_next = D.b_next;
     out->bin_size = D.bin_size; out->reserved = 0;
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- depth regions (depth_regions_kernels.hip.h)
+// The session's regions: validated, then kept in a stable order by tid with their positions in the caller's array.
+cov_status cov_depth_regions_set(cov_session *s, const cov_depth_region *regions, uint64_t n) {
+    if (!s || (n && !regions)) return COV_ERR_INVALID_ARG;
+    if (s->h_tile_first.empty()) /* (cov_set_targets leaves n_targets + 1 entries) */ { s->err = "cov_depth_regions_set: needs cov_set_targets (the regions are validated against the targets)"; return COV_ERR_STATE; }
+    if (n >= (1ull << 32)) { s->err = "cov_depth_regions_set: 2^32 regions or more (index 4294967296 is the first that does not fit)"; return COV_ERR_INVALID_ARG; }
+    cov_session::DepthRuns &D = s->dr;
+    for (uint64_t i = 0; i < n; i++) {
+        const cov_depth_region &r = regions[i];
+        const char *what = r.tid >= s->n_targets ? "its tid is not a target" : r.reserved != 0 ? "its reserved field is not 0" : r.start >= r.end ? "start >= end" :
+                           r.end > s->h_tlen[r.tid] ? "its end lies behind the target's length" : nullptr;
+        if (what) { s->err = "cov_depth_regions_set: region " + std::to_string(i) + ": " + what; return COV_ERR_INVALID_ARG; }
+    }
+    // counting sort by tid: stable, so the input order inside a target is kept
+    std::vector<u32> first((size_t)s->n_targets + 1, 0u);
+    for (uint64_t i = 0; i < n; i++) first[regions[i].tid + 1]++;
+    for (u32 t = 0; t < s->n_targets; t++) first[t + 1] += first[t];
+    std::vector<drgc::Region> reg((size_t)n);
+    std::vector<u32> input((size_t)n), at(first.begin(), first.end() - 1);
+    for (uint64_t i = 0; i < n; i++) {
+        const u32 j = at[regions[i].tid]++;
+        reg[j].tid = regions[i].tid; reg[j].start = regions[i].start; reg[j].end = regions[i].end; reg[j].reserved = 0u;
+        input[j] = (u32)i;
+    }
+    D.h_reg.swap(reg); D.h_reg_input.swap(input); D.h_reg_first.swap(first);
+    D.have_regions = n != 0;
+    if (D.regs_valid) { D.regs_valid = false; D.taker[cov_session::DepthRuns::REGIONS] = 0; }      // the chunk computed for the regions before is not theirs
+    return COV_OK;
+}
+
+// One chunk of whole targets: the arena stage of the depth runs, then the chunk's regions described from its woff[] on the host, every
+// result initialised and one wave per piece of a region.  The piece offsets come from the regions alone: no count, no scan and no host wait
+// in front of the reduction.
+cov_status cov_depth_regions_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_regions) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_regions_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (!s->finished) { s->err = "cov_depth_regions_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_regions_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (!s->dr.have_regions) { s->err = "cov_depth_regions_compute: no regions set (cov_depth_regions_set)"; return COV_ERR_STATE; }
+    if (!tid_next || !n_regions || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
+    covr::Range rr("depth regions of one chunk (cov_depth_regions_compute)");
+    cov_session::DepthRuns &D = s->dr;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    timing_events(s);
+    hipStream_t st = s->stream;
+    const u32 t1 = dprc::plan_chunk(s->h_tlen.data(), tid_lo, tid_hi, D.chunk_bases);
+    const u32 r0 = D.h_reg_first[tid_lo], n = D.h_reg_first[t1] - r0;
+    const u64 pieces = [&] { u64 p = 0; for (u32 r = 0; r < n; r++) p += drgc::pieces_of_region(D.h_reg[r0 + r].start, D.h_reg[r0 + r].end); return p; }();
+    // (a refusal leaves the chunk computed before as it was)
+    if (pieces > 0xffffffffull) { s->err = "cov_depth_regions_compute: more than 2^32 pieces in one chunk"; return COV_ERR_STATE; }
+    hipEvent_t *ev = s->ev[COV_K_DEPTH_REGIONS];      // events of its own: the call is not part of a finish; ev_mid closes the region kernels
+    if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
+    DepthChunk ck;
+    if (const cov_status rc = depth_arena_stage(s, "cov_depth_regions_compute", cov_session::DepthRuns::REGIONS, tid_lo, tid_hi, ev, ck)) return rc;
+    u32 launches = 4;      // k_depth_marks and the rank scan's three
+    if (n) {
+        D.h_reg_desc.resize(n); D.h_reg_piece_off.resize((size_t)n + 1);
+        u32 p = 0;
+        for (u32 r = 0; r < n; r++) {
+            const drgc::Region &g = D.h_reg[r0 + r];
+            D.h_reg_desc[r] = drgc::describe(D.h_woff[g.tid - tid_lo], g.start, g.end);
+            D.h_reg_piece_off[r] = p; p += drgc::pieces_of(D.h_reg_desc[r]);
+        }
+        D.h_reg_piece_off[n] = p;
+        HIPCHK(D.reg_desc.reserve(n, st)); HIPCHK(D.reg_piece_off.reserve((size_t)n + 1, st)); HIPCHK(D.regs.reserve(n, st));
+        HIPCHK(hipMemcpyAsync(D.reg_desc.p, D.h_reg_desc.data(), (size_t)n * sizeof(drgc::Desc), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(D.reg_piece_off.p, D.h_reg_piece_off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(covdb::k_bins_init, dim3((n + 255u) / 256u), dim3(256), 0, st, D.regs.p, (u64)n);
+        hipLaunchKernelGGL(covrg::k_depth_regions, dim3((u32)((pieces + 3ull) / 4ull)), dim3(256), 0, st, (const int32_t *)D.arena.p, (const drgc::Desc *)D.reg_desc.p,
+                           (const u32 *)D.reg_piece_off.p, n, (u32)pieces, D.regs.p);
+        launches += 2;
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(D.ev_mid, st));
+    HIPCHK(hipStreamSynchronize(st));
+    float ms_arena = 0.f, ms_regs = 0.f;
+    (void)hipEventElapsedTime(&ms_arena, ev[0], ev[1]);
+    (void)hipEventElapsedTime(&ms_regs, ev[1], D.ev_mid);
+    s->ev_fresh = -1;
+    D.g_arena_ms = ms_arena; D.regs_ms = ms_regs; D.g_launches = launches;
+    D.g_lo = tid_lo; D.g_next = t1; D.g_first = r0; D.n_regs = n; D.n_pieces = pieces; D.g_arena_bases = 4ull * ck.words; D.regs_valid = true;
+    *tid_next = t1; *n_regions = n;
+    if (cov_timing_on())
+        fprintf(stderr, "[covermhip] depth regions: targets [%u, %u), %llu arena entries, %u regions in %llu pieces; arena %.3f ms, region kernels %.3f ms\n", tid_lo, t1,
+                (unsigned long long)D.g_arena_bases, n, (unsigned long long)pieces, D.g_arena_ms, D.regs_ms);
+    return COV_OK;
+}
+
+cov_status cov_depth_regions_fetch(cov_session *s, uint64_t *input_index, cov_depth_bin *out) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_regions_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_regions_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.regs_valid && s->dr.taker[cov_session::DepthRuns::REGIONS]) { s->err = s->dr.lost(cov_session::DepthRuns::REGIONS); return COV_ERR_STATE; }
+    if (!s->finished || !s->dr.regs_valid) { s->err = "cov_depth_regions_fetch: no chunk computed since the last finish (cov_depth_regions_compute)"; return COV_ERR_STATE; }
+    if (s->dr.n_regs && (!input_index || !out)) return COV_ERR_INVALID_ARG;
+    cov_session::DepthRuns &D = s->dr;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    if (D.n_regs) {
+        HIPCHK(hipMemcpyAsync(out, D.regs.p, (size_t)D.n_regs * sizeof(cov_depth_bin), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    for (u64 i = 0; i < D.n_regs; i++) input_index[i] = D.h_reg_input[D.g_first + i];
+    return COV_OK;
+}
+
+cov_status cov_depth_regions_last(const cov_session *s, cov_depth_regions_info *out) {
+    if (!s || !out) return COV_ERR_INVALID_ARG;
+    const cov_session::DepthRuns &D = s->dr;
+    out->arena_bases = D.g_arena_bases; out->n_regions = D.n_regs; out->n_pieces = D.n_pieces; out->arena_ms = D.g_arena_ms; out->regions_ms = D.regs_ms;
+    out->tid_lo = D.g_lo; out->tid_next = D.g_next;
     return COV_OK;
 }
 
@@ -3240,6 +3379,11 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
     if (k == COV_K_DEPTH_BINS) {      // not part of a finish: the last cov_depth_bins_compute
         if (ms_total) *ms_total = s->dr.bins_ms;
         if (launches) *launches = s->dr.b_launches;
+        return COV_OK;
+    }
+    if (k == COV_K_DEPTH_REGIONS) {      // not part of a finish: the last cov_depth_regions_compute
+        if (ms_total) *ms_total = s->dr.regs_ms;
+        if (launches) *launches = s->dr.g_launches;
         return COV_OK;
     }
     if (k == COV_K_GROUP) {      // not part of a finish: the last cov_group_records

@@ -878,6 +878,7 @@ int run_depth(int argc, char **argv) {
     uint32_t bin_size = 0;      // --bin-size: one line per fixed window (covh_depth_bins_write) instead of one per depth run
     int bin_value = COVH_BIN_MEAN;
     bool have_bin_value = false;
+    std::string regions_path;      // --regions: one line per region of a BED file (covh_depth_regions_write)
     auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && (argv[i + 1][0] != '-' || !argv[i + 1][1])) dst.push_back(argv[++i]); };
     static const char *const REFUSED[] = {"-m", "--methods", "--gff", "--gff-feature-type", "--devices", "--contig-end-exclusion", "--min-covered-fraction", "--trim-min", "--trim-max",
                                           "--output-format", "-s", "--separator", "--single-genome", "--genome-definition", "-f", "--genome-fasta-files", "-d",
@@ -899,7 +900,8 @@ int run_depth(int argc, char **argv) {
         else if (k == "--bin-size") {
             bin_size = (uint32_t)parse_uint(k, val(), 0x7fffffffull);
             if (bin_size == 0) die("invalid value '0' for '" + k + "'");
-        } else if (k == "--bin-value") {
+        } else if (k == "--regions") regions_path = val();
+        else if (k == "--bin-value") {
             const std::string v = val();
             static const char *const KINDS[] = {"mean", "sum", "min", "max", "covered"};      // covh_bin_value
             bin_value = -1;
@@ -916,7 +918,9 @@ int run_depth(int argc, char **argv) {
         else if (k == "-q" || k == "--quiet") {}
         else die("unknown argument " + k);
     }
-    if (have_bin_value && !bin_size) die("the argument '--bin-value' needs '--bin-size': it picks what is printed per bin (coverm-amd depth --bin-size N --bin-value ...)");
+    if (!regions_path.empty() && bin_size) die("the argument '--regions' cannot be used with '--bin-size': a line per region of the BED file, or a line per fixed window");
+    if (have_bin_value && !bin_size && regions_path.empty())
+        die("the argument '--bin-value' needs '--bin-size' or '--regions': it picks what is printed per bin or region (coverm-amd depth --bin-size N --bin-value ...)");
     if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
     if (a.devices.empty()) a.devices.push_back(0);
     {
@@ -945,6 +949,9 @@ int run_depth(int argc, char **argv) {
         if (covh_sam_kind(h) == 1) die("BAM from a pipe is not supported yet; SAM text is (e.g. `samtools view -h`), or pass the file's path");
         if (covh_sam_kind(h) == 2) die(stoit_of(b) + ": the stream is neither SAM text nor BAM (NUL bytes in its first piece)");
     }
+    covh_bed *bed = nullptr;      // read and syntax-checked before any device work; resolved per sample, against its header
+    struct BedFree { covh_bed *&b; ~BedFree() { covh_bed_free(b); } } bed_free{bed};
+    if (!regions_path.empty() && !(bed = covh_bed_read(regions_path.c_str()))) die(covh_last_error());
     struct SamDrain { Run &R; ~SamDrain() { for (auto &kv : R.sam_ahead) covh_sam_close(kv.second); R.sam_ahead.clear(); } } sam_drain{R};
     FILE *out = a.output_file.empty() || a.output_file == "-" ? stdout : fopen(a.output_file.c_str(), "w");
     if (!out) die("Failed to create output file: " + a.output_file);
@@ -972,6 +979,14 @@ int run_depth(int argc, char **argv) {
         fprintf(out, "track type=bedGraph name=\"%s\"\n", S.stoit.c_str());
         fflush(out);
         const covh_header hdr = S.header();
+        if (bed) {
+            uint64_t n_regions = 0;
+            if (covh_depth_regions_write(s, &hdr, bed, bin_value, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_regions) != COV_OK) die(covh_last_error());
+            if (timing_on())
+                fprintf(stderr, "[coverm-amd] sample %s: open %.3fs, ingest (decode+push) %.3fs, finish %.3fs, %llu records; depth regions: %llu regions computed, fetched and written in %.3fs\n",
+                        S.stoit.c_str(), S.t_open, S.t_ingest, S.t_finish, (unsigned long long)S.n_records, (unsigned long long)n_regions, now() - t_runs0);
+            continue;
+        }
         if (bin_size) {
             uint64_t n_bins = 0;
             if (covh_depth_bins_write(s, &hdr, bin_size, bin_value, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_bins) != COV_OK) die(covh_last_error());
@@ -1012,12 +1027,15 @@ int run_cli(int argc, char **argv) {
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n"
-                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--bin-size N [--bin-value V]] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
+                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--bin-size N | --regions BED [--bin-value V]] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
                         "       the per-base depth of every reference, under contig's filters, as a bedGraph: one `track` line per sample, then\n"
                         "       name<TAB>start<TAB>end<TAB>depth (0-based, half open) per stretch of equal depth; --no-zeros drops the stretches of depth 0\n"
                         "       --bin-size N [--bin-value mean|sum|min|max|covered]: one line per window of N bases instead (the last window of a reference\n"
                         "       is short; windows never cross references), reduced on the device; mean (the default) is printed with three decimals, the\n"
-                        "       others as integers; --no-zeros then drops the windows without a covered base\n");
+                        "       others as integers; --no-zeros then drops the windows without a covered base\n"
+                        "       --regions BED [--bin-value ...]: one line per region of a BED file instead (chrom<TAB>start<TAB>end[<TAB>name], 0-based, half\n"
+                        "       open; regions may overlap and come in any order), in the file's order, reduced on the device: chrom, start, end, the name when\n"
+                        "       the line had one, then the value; a reference the sample's header does not have, or an end behind its length, is an error\n");
         return 2;
     }
     a.mode = argv[1];

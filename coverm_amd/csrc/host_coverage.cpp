@@ -16,6 +16,7 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <optional>
 #include <string>
 #include <thread>
@@ -1764,5 +1765,197 @@ int covh_depth_bins_write(cov_session *s, const covh_header *h, uint32_t bin_siz
         total += n; lo = next;
     }
     if (n_bins_out) *n_bins_out = total;
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- depth regions of a BED file (`coverm-amd depth --regions`)
+struct covh_bed {
+    struct Line { uint32_t chrom_off, chrom_len, name_off, name_len, start, end; uint64_t line_no; bool has_name; };
+    std::string path, text;      // text: the chrom and name fields, back to back
+    std::vector<Line> lines;
+};
+
+namespace {
+
+// a decimal integer <= 2^31 - 1, digits only
+bool bed_number(std::string_view f, uint32_t &v) {
+    if (f.empty() || f.size() > 10) return false;
+    uint64_t x = 0;
+    for (char c : f) { if (c < '0' || c > '9') return false; x = x * 10 + (uint64_t)(c - '0'); }
+    if (x > 0x7fffffffull) return false;
+    v = (uint32_t)x;
+    return true;
+}
+
+std::string bed_at(const covh_bed *b, uint64_t line_no) { return b->path + ":" + std::to_string(line_no) + ": "; }
+
+// regions [j0, j1) of the file as text
+void format_regions_piece(const covh_bed *b, const cov_depth_bin *res, int value, bool no_zeros, uint64_t j0, uint64_t j1, std::string &out) {
+    out.clear();
+    char num[40];
+    auto put = [&](uint64_t v) { const auto r = std::to_chars(num, num + sizeof num, v); out.append(num, (size_t)(r.ptr - num)); };
+    auto put_i = [&](int64_t v) { if (v < 0) { out.push_back('-'); put((uint64_t)(-v)); } else put((uint64_t)v); };
+    for (uint64_t j = j0; j < j1; j++) {
+        const covh_bed::Line &l = b->lines[j];
+        const cov_depth_bin r = res[j];
+        if (no_zeros && r.max == 0) continue;
+        out.append(b->text, l.chrom_off, l.chrom_len);
+        out.push_back('\t'); put(l.start); out.push_back('\t'); put(l.end); out.push_back('\t');
+        if (l.has_name) { out.append(b->text, l.name_off, l.name_len); out.push_back('\t'); }
+        switch (value) {
+        case COVH_BIN_SUM: put(r.sum); break;
+        case COVH_BIN_MIN: put_i(r.min); break;
+        case COVH_BIN_MAX: put_i(r.max); break;
+        case COVH_BIN_COVERED: put(r.covered); break;
+        default: out.append(num, (size_t)snprintf(num, sizeof num, "%.3f", (double)r.sum / (double)(l.end - l.start))); break;
+        }
+        out.push_back('\n');
+    }
+}
+
+}  // namespace
+
+covh_bed *covh_bed_read(const char *path) {
+    if (!path) { g_err = "covh_bed_read: no path"; return nullptr; }
+    FILE *fh = fopen(path, "rb");
+    if (!fh) { g_err = std::string(path) + ": " + strerror(errno); return nullptr; }
+    std::string data;
+    char buf[1 << 16];
+    size_t got;
+    while ((got = fread(buf, 1, sizeof buf, fh)) > 0) data.append(buf, got);
+    const bool bad = ferror(fh) != 0;
+    fclose(fh);
+    if (bad) { g_err = std::string(path) + ": read failed"; return nullptr; }
+    std::unique_ptr<covh_bed> b(new covh_bed);
+    b->path = path;
+    uint64_t line_no = 0;
+    for (size_t at = 0; at < data.size();) {
+        size_t nl = data.find('\n', at);
+        if (nl == std::string::npos) nl = data.size();
+        std::string_view line(data.data() + at, nl - at);
+        at = nl + 1; line_no++;
+        if (!line.empty() && line.back() == '\r') line.remove_suffix(1);
+        if (line.empty() || line[0] == '#' || line.substr(0, 5) == "track" || line.substr(0, 7) == "browser") continue;
+        std::string_view f[4];
+        size_t nf = 0, p = 0;
+        while (nf < 4) {
+            const size_t t = line.find('\t', p);
+            f[nf++] = line.substr(p, t == std::string_view::npos ? std::string_view::npos : t - p);
+            if (t == std::string_view::npos) break;
+            p = t + 1;
+        }
+        if (nf < 3) { g_err = bed_at(b.get(), line_no) + "expected chrom<TAB>start<TAB>end, found " + std::to_string(nf) + (nf == 1 ? " field" : " fields"); return nullptr; }
+        if (f[0].empty()) { g_err = bed_at(b.get(), line_no) + "the reference name is empty"; return nullptr; }
+        covh_bed::Line l{};
+        if (!bed_number(f[1], l.start)) { g_err = bed_at(b.get(), line_no) + "start '" + std::string(f[1]) + "' is not a decimal integer of at most 2147483647"; return nullptr; }
+        if (!bed_number(f[2], l.end)) { g_err = bed_at(b.get(), line_no) + "end '" + std::string(f[2]) + "' is not a decimal integer of at most 2147483647"; return nullptr; }
+        if (l.start >= l.end) { g_err = bed_at(b.get(), line_no) + "start " + std::to_string(l.start) + " >= end " + std::to_string(l.end) + " (a region is [start, end), not empty)"; return nullptr; }
+        if (b->text.size() + f[0].size() + f[3].size() > 0xffffffffull || b->lines.size() >= 0xffffffffull) { g_err = bed_at(b.get(), line_no) + "more than 2^32 regions or bytes of names"; return nullptr; }
+        l.chrom_off = (uint32_t)b->text.size(); l.chrom_len = (uint32_t)f[0].size(); b->text.append(f[0]);
+        l.has_name = nf >= 4;
+        if (l.has_name) { l.name_off = (uint32_t)b->text.size(); l.name_len = (uint32_t)f[3].size(); b->text.append(f[3]); }
+        l.line_no = line_no;
+        b->lines.push_back(l);
+    }
+    return b.release();
+}
+
+void covh_bed_free(covh_bed *b) { delete b; }
+uint64_t covh_bed_count(const covh_bed *b) { return b ? b->lines.size() : 0; }
+
+int covh_bed_line(const covh_bed *b, uint64_t i, const char **chrom, uint32_t *chrom_len, uint32_t *start, uint32_t *end, const char **name, uint32_t *name_len, uint64_t *line_no) {
+    if (!b || i >= b->lines.size()) { g_err = "covh_bed_line: no such region"; return COV_ERR_INVALID_ARG; }
+    const covh_bed::Line &l = b->lines[i];
+    if (chrom) *chrom = b->text.data() + l.chrom_off;
+    if (chrom_len) *chrom_len = l.chrom_len;
+    if (start) *start = l.start;
+    if (end) *end = l.end;
+    if (name) *name = l.has_name ? b->text.data() + l.name_off : nullptr;
+    if (name_len) *name_len = l.has_name ? l.name_len : 0;
+    if (line_no) *line_no = l.line_no;
+    return COV_OK;
+}
+
+int covh_bed_resolve(const covh_bed *b, const covh_header *h, cov_depth_region *out) {
+    if (!b || !h || (!out && !b->lines.empty())) { g_err = "covh_bed_resolve: no regions or no header"; return COV_ERR_INVALID_ARG; }
+    std::unordered_map<std::string_view, uint32_t> tid_of;
+    tid_of.reserve(h->n_targets);
+    for (uint32_t t = 0; t < h->n_targets; t++) tid_of.emplace(std::string_view(h->names + h->name_off[t], h->name_off[t + 1] - h->name_off[t]), t);      // (the first of equal names)
+    for (size_t i = 0; i < b->lines.size(); i++) {
+        const covh_bed::Line &l = b->lines[i];
+        const std::string_view chrom(b->text.data() + l.chrom_off, l.chrom_len);
+        const auto it = tid_of.find(chrom);
+        if (it == tid_of.end()) { g_err = bed_at(b, l.line_no) + "reference '" + std::string(chrom) + "' is not in the alignment file's header (a BED file for another assembly?)"; return COV_ERR_INVALID_ARG; }
+        if (l.end > h->target_len[it->second]) {
+            g_err = bed_at(b, l.line_no) + "end " + std::to_string(l.end) + " lies behind the length " + std::to_string(h->target_len[it->second]) + " of reference '" + std::string(chrom) + "'";
+            return COV_ERR_INVALID_ARG;
+        }
+        out[i].tid = it->second; out[i].start = l.start; out[i].end = l.end; out[i].reserved = 0;
+    }
+    return COV_OK;
+}
+
+int covh_depth_regions_format(const covh_bed *b, const cov_depth_bin *results, int value, int no_zeros, int threads, int out_fd) {
+    if (!b) { g_err = "covh_depth_regions_format: no regions"; return COV_ERR_INVALID_ARG; }
+    if (value < COVH_BIN_MEAN || value > COVH_BIN_COVERED) { g_err = "covh_depth_regions_format: an unknown value kind"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = b->lines.size();
+    if (n && !results) { g_err = "covh_depth_regions_format: no results"; return COV_ERR_INVALID_ARG; }
+    constexpr uint64_t PIECE = 1ull << 17;      // regions per piece: a few MB of text
+    const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
+    std::vector<std::string> text(T);
+    for (uint64_t base = 0; base < n; base += PIECE * T) {      // T pieces side by side, written in their order
+        const unsigned np = (unsigned)std::min<uint64_t>(T, (n - base + PIECE - 1) / PIECE);
+        auto piece = [&](unsigned i) { format_regions_piece(b, results, value, no_zeros != 0, base + i * PIECE, std::min(n, base + (i + 1) * PIECE), text[i]); };
+        std::vector<std::thread> th;
+        for (unsigned i = 1; i < np; i++) th.emplace_back(piece, i);
+        piece(0);
+        for (auto &t : th) t.join();
+        for (unsigned i = 0; i < np; i++)
+            if (!write_all(out_fd, text[i].data(), text[i].size())) { g_err = "covh_depth_regions_format: write failed"; return COV_ERR_INVALID_ARG; }
+    }
+    return COV_OK;
+}
+
+int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_bed *b, int value, int no_zeros, int threads, int out_fd, uint64_t *n_regions_out) {
+    if (!s || !h || !b) { g_err = "covh_depth_regions_write: no session, header or regions"; return COV_ERR_INVALID_ARG; }
+    if (n_regions_out) *n_regions_out = 0;
+    const uint64_t n = b->lines.size();
+    std::vector<cov_depth_region> regions(n);
+    int rc = covh_bed_resolve(b, h, regions.data());
+    if (rc != COV_OK) return rc;
+    if (n == 0) return COV_OK;
+    rc = (int)cov_depth_regions_set(s, regions.data(), n);
+    if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+    std::vector<uint8_t> has(h->n_targets, 0);
+    for (const cov_depth_region &r : regions) has[r.tid] = 1;
+    std::vector<cov_depth_bin> results(n);      // the sample's results in the file's order, 24 B per region
+    void *pinned = nullptr; size_t cap = 0;     // page-locked, grown to the largest chunk: the results, then their input indices
+    struct Free { void *&p; ~Free() { if (p) cov_host_free(p); } } free_pinned{pinned};
+    uint64_t total = 0;
+    uint32_t lo = 0;
+    while (lo < h->n_targets && !has[lo]) lo++;      // targets without a region are skipped: their depth is never materialised
+    while (lo < h->n_targets) {
+        uint32_t next = 0; uint64_t m = 0;
+        rc = (int)cov_depth_regions_compute(s, lo, h->n_targets, &next, &m);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        if (m > cap) {
+            if (pinned) { cov_host_free(pinned); pinned = nullptr; }
+            cap = (size_t)m;
+            pinned = cov_host_alloc(cap * (sizeof(cov_depth_bin) + sizeof(uint64_t)));
+            if (!pinned) { g_err = "covh_depth_regions_write: no page-locked memory for a chunk's results"; return COV_ERR_HIP; }
+        }
+        cov_depth_bin *res = static_cast<cov_depth_bin *>(pinned);
+        uint64_t *idx = reinterpret_cast<uint64_t *>(res + cap);
+        rc = (int)cov_depth_regions_fetch(s, idx, res);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        for (uint64_t i = 0; i < m; i++) results[idx[i]] = res[i];
+        total += m;
+        lo = next;
+        while (lo < h->n_targets && !has[lo]) lo++;
+    }
+    if (total != n) { g_err = "covh_depth_regions_write: the chunks returned " + std::to_string(total) + " of " + std::to_string(n) + " regions"; return COV_ERR_STATE; }
+    rc = covh_depth_regions_format(b, results.data(), value, no_zeros, threads, out_fd);
+    if (rc != COV_OK) return rc;
+    if (n_regions_out) *n_regions_out = total;
     return COV_OK;
 }

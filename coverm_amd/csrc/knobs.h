@@ -4,7 +4,7 @@
 //   store_cap_records, store_cap_cigar      cov_create: the bounded record store (covermhip.hip)
 //   pileup_chunk_tiles                      cov_create: consecutive tiles one wave of the pileup kernels walks (1 .. 64)
 //   ingest_round_blocks, ingest_carry_kb, ingest_cwin_kb      cov_ingest_begin: blocks per inflate window, carry buffer, compressed window
-//   depth_chunk_bases                       cov_create: arena entries of one chunk of cov_depth_runs_compute / cov_depth_bins_compute (default 2^28)
+//   depth_chunk_bases                       cov_create: arena entries of one chunk of cov_depth_runs_compute / cov_depth_bins_compute / cov_depth_regions_compute (default 2^28)
 //   pair_chunk                              cov_pair_filter: records per table chunk
 //   ingest_piece_kb                         covh_bam_ingest_device: bytes per staging piece
 //   stream_window_kb, filter_window_kb      the streamed CPU reader's and `coverm-amd filter`'s compressed windows

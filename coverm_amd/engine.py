@@ -132,6 +132,7 @@ class Session:
         self.n_targets = len(tl)
         self.target_len = tl
         self._runs = False                         # (cov_set_targets and cov_set_target_mask turn genomes and runs off)
+        self._n_regions, self._region_tids = 0, np.zeros(0, np.int64)      # (and cov_set_targets drops the depth regions)
         if mask is not None:
             m = np.ascontiguousarray(mask, dtype=np.uint8)
             assert len(m) == len(tl)
@@ -243,6 +244,62 @@ class Session:
         ms = C.c_double(0)
         n = C.c_uint32(0)
         self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_BINS, C.byref(ms), C.byref(n)))
+        return ms.value, n.value
+
+    def set_depth_regions(self, regions):
+        """cov_depth_regions_set: the regions Session.depth_regions reduces, in ANY order, overlaps and duplicates allowed.  `regions`: a
+        native.DEPTH_REGION_DTYPE array, or an iterable of (tid, start, end) with 0 <= start < end <= the target's length ([start, end),
+        0-based, half open); nothing (or an empty list) clears them.  Needs set_targets; a new set_targets drops them."""
+        if isinstance(regions, np.ndarray) and regions.dtype == native.DEPTH_REGION_DTYPE:
+            arr = np.ascontiguousarray(regions)
+        else:
+            rows = list(regions) if regions is not None else []
+            arr = np.zeros(len(rows), dtype=native.DEPTH_REGION_DTYPE)
+            if rows:
+                a = np.asarray(rows, dtype=np.int64).reshape(len(rows), 3)
+                if (a < 0).any() or (a > 0xffffffff).any():
+                    raise ValueError("a region's tid, start or end is outside 0 .. 2^32 - 1")
+                arr["tid"], arr["start"], arr["end"] = a[:, 0], a[:, 1], a[:, 2]
+        self._check(self._lib.cov_depth_regions_set(self._h, arr.ctypes.data if arr.size else None, C.c_uint64(arr.size)))
+        self._region_tids = np.unique(arr["tid"]).astype(np.int64)
+        self._n_regions = int(arr.size)
+
+    def depth_regions(self, chunks=None):
+        """cov_depth_regions_compute / cov_depth_regions_fetch over the regions of set_depth_regions, chunk by chunk: per region the sum,
+        min, max and covered bases of its per-base depth, reduced on the device.  Returns a native.DEPTH_BIN_DTYPE array IN THE ORDER THE
+        REGIONS WERE GIVEN.  Targets without a region are skipped: a chunk begins at the first target at or behind the last chunk's
+        tid_next that has a region, so only those chunks' depth is materialised.  `chunks`: a list that receives one dict per chunk
+        actually computed (cov_depth_regions_info: tid_lo, tid_next, arena_bases, n_regions, n_pieces, arena_ms, regions_ms)."""
+        n = getattr(self, "_n_regions", 0)
+        tids = getattr(self, "_region_tids", np.zeros(0, np.int64))
+        out = np.zeros(n, dtype=native.DEPTH_BIN_DTYPE)
+        hi = self.n_targets
+        if n == 0:      # nothing set: the call refuses with its own words
+            nxt, m = C.c_uint32(0), C.c_uint64(0)
+            self._check(self._lib.cov_depth_regions_compute(self._h, C.c_uint32(0), C.c_uint32(hi), C.byref(nxt), C.byref(m)))
+            return out
+        at = 0
+        while at < len(tids):
+            lo = int(tids[at])
+            nxt, m = C.c_uint32(0), C.c_uint64(0)
+            self._check(self._lib.cov_depth_regions_compute(self._h, C.c_uint32(lo), C.c_uint32(hi), C.byref(nxt), C.byref(m)))
+            idx = np.zeros(int(m.value), dtype=np.uint64)
+            res = np.zeros(int(m.value), dtype=native.DEPTH_BIN_DTYPE)
+            self._check(self._lib.cov_depth_regions_fetch(self._h, idx.ctypes.data if idx.size else None, res.ctypes.data if res.size else None))
+            out[idx.astype(np.int64)] = res
+            if chunks is not None:
+                info = native.CovDepthRegionsInfo()
+                self._check(self._lib.cov_depth_regions_last(self._h, C.byref(info)))
+                chunks.append({k: getattr(info, k) for k, _ in info._fields_})
+            at = int(np.searchsorted(tids, nxt.value, side="left"))
+        return out
+
+    def depth_regions_kernel_ms(self):
+        """(ms, launches) of the region kernels of the last chunk of depth_regions (COV_K_DEPTH_REGIONS): six launches, k_depth_marks, the
+        rank scan's three, k_bins_init and k_depth_regions (four for a chunk without a region)."""
+        ms = C.c_double(0)
+        n = C.c_uint32(0)
+        self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_REGIONS, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
     def set_estimators(self, estimators):

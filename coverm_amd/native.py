@@ -16,13 +16,14 @@ ERR_UNSORTED, ERR_NM_MISSING, ERR_NM_BADTYPE, ERR_POS_OOB, ERR_BAD_CIGAR, ERR_BA
 ERR_INVALID_ARG, ERR_HIP, ERR_STATE = 16, 17, 18
 WANT_HIST, WANT_IDENTITY = 1, 2
 WANT_IDENTITY_PRIMARY_ONLY, WANT_IDENTITY_NONSUPP_ONLY = 4, 8
-K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 14
+K_PREP, K_RANGES, K_PILEUP, K_IDENTITY, K_HIST, K_HIST_COMPACT, K_ESTIMATE, K_COUNT = 0, 1, 2, 3, 4, 5, 6, 15
 K_GENOME = 7      # cov_set_genomes: reduce + histogram merge + estimate over genomes (Session.genome_kernel_ms)
 K_GROUP = 8       # cov_group_records: order check + sort passes + gather of the last call (Session.group_kernel_ms)
 K_SEP = 10        # cov_set_genome_runs: the entry table of the finish, in front of K_GENOME (Session.sep_kernel_ms)
 K_GENE_READS = 11 # cov_interval_reads_compute: the kernels of the last call (Session.gene_reads_kernel_ms)
 K_DEPTH_RUNS = 12 # cov_depth_runs_compute: the run kernels of the last chunk (Session.depth_runs_kernel_ms)
 K_DEPTH_BINS = 13 # cov_depth_bins_compute: the bin kernels of the last chunk (Session.depth_bins_kernel_ms)
+K_DEPTH_REGIONS = 14 # cov_depth_regions_compute: the region kernels of the last chunk (Session.depth_regions_kernel_ms)
 K_SAM = 9         # cov_sam_*: the decode kernels of the last SAM text ingest (Session.sam_kernel_ms)
 KERNEL_NAMES = {K_PREP: "k_prep", K_RANGES: "k_ranges", K_PILEUP: "k_pileup", K_IDENTITY: "k_identity",
                 K_HIST: "k_hist", K_HIST_COMPACT: "k_hist_compact", K_ESTIMATE: "k_estimate"}
@@ -88,6 +89,16 @@ class CovDepthBinsInfo(C.Structure):
                 ("tid_lo", C.c_uint32), ("tid_next", C.c_uint32), ("bin_size", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+# numpy mirror of cov_depth_region (16 bytes): [start, end) of target tid, 0-based, half open
+DEPTH_REGION_DTYPE = np.dtype([("tid", "<u4"), ("start", "<u4"), ("end", "<u4"), ("reserved", "<u4")])
+assert DEPTH_REGION_DTYPE.itemsize == 16
+
+
+class CovDepthRegionsInfo(C.Structure):
+    _fields_ = [("arena_bases", C.c_uint64), ("n_regions", C.c_uint64), ("n_pieces", C.c_uint64), ("arena_ms", C.c_double), ("regions_ms", C.c_double),
+                ("tid_lo", C.c_uint32), ("tid_next", C.c_uint32)]
+
+
 EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "cov_set_targets",
            "cov_set_target_mask", "cov_push_batch", "cov_push_batch_device", "cov_finish", "cov_fetch_hist",
            "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths", "cov_copy_run_words",
@@ -95,7 +106,8 @@ EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "co
            "cov_set_genome_runs", "cov_genome_entry_count", "cov_fetch_genome_entries",
            "cov_sam_begin", "cov_sam_window_bytes", "cov_sam_slot_wait", "cov_sam_feed", "cov_sam_end", "cov_ingest_last_stats",
            "cov_interval_reads_compute", "cov_depth_runs_compute", "cov_depth_runs_fetch", "cov_depth_runs_last",
-           "cov_depth_bins_compute", "cov_depth_bins_fetch", "cov_depth_bins_last"]
+           "cov_depth_bins_compute", "cov_depth_bins_fetch", "cov_depth_bins_last",
+           "cov_depth_regions_set", "cov_depth_regions_compute", "cov_depth_regions_fetch", "cov_depth_regions_last"]
 
 _lib = None
 
@@ -169,6 +181,10 @@ def lib():
     L.cov_depth_bins_compute.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.cov_depth_bins_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cov_depth_bins_last.argtypes = [C.c_void_p, C.POINTER(CovDepthBinsInfo)]
+    L.cov_depth_regions_set.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    L.cov_depth_regions_compute.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.cov_depth_regions_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cov_depth_regions_last.argtypes = [C.c_void_p, C.POINTER(CovDepthRegionsInfo)]
     _lib = L
     return L
 

@@ -377,6 +377,31 @@ int covh_depth_bins_format(const covh_header *h, uint32_t tid_lo, uint32_t n_tar
 int covh_depth_bins_write(cov_session *s, const covh_header *h, uint32_t bin_size, int value, int no_zeros, int threads, int out_fd,
                           uint64_t *n_bins_out);
 
+/* ---- depth regions of a BED file (`coverm-amd depth --regions r.bed`): per region the value cov_depth_regions_compute leaves on the device.
+ * covh_bed_read needs no device.  It reads lines  chrom \t start \t end [\t name [\t ...]]  (0-based, half open); a trailing \r is stripped;
+ * empty lines and lines beginning with '#', "track" or "browser" are skipped; start and end are decimal integers <= 2^31 - 1; field 4, if
+ * present, is the region's name, verbatim.  A syntax error or start >= end returns NULL with "<path>:<line>: <what>" in covh_last_error.
+ * covh_bed_line returns region i as the file gave it (chrom and name are NOT NUL terminated; name == NULL for a line without one).
+ * covh_bed_resolve fills out[covh_bed_count] against a header: chrom must equal a reference name exactly; an unknown name and an end beyond
+ * the reference's length are errors with the same "<path>:<line>: " prefix (a BED file for another assembly is a mistake worth hearing about).
+ * covh_depth_regions_format needs no device: one line per region IN THE FILE'S ORDER from results[covh_bed_count] in that order,
+ *   chrom \t start \t end \t value \n     or     chrom \t start \t end \t name \t value \n     when the line had a name;
+ * `value` is a covh_bin_value, printed exactly as the bins print it (mean = (double)sum / (double)(end - start) with "%.3f"); no_zeros drops
+ * the regions whose max is 0; formatted on up to `threads` threads in ordered pieces, the same text for every thread count.
+ * covh_depth_regions_write resolves, calls cov_depth_regions_set and walks the chunks of a finished session, SKIPPING targets without a
+ * region (the next chunk begins at the first target at or behind tid_next that has one), fetches through page-locked memory, scatters by
+ * input_index into one array of 24 B per region and formats once, at the end.  *n_regions_out (may be NULL) = the regions computed. */
+typedef struct covh_bed covh_bed;
+covh_bed *covh_bed_read(const char *path);
+void covh_bed_free(covh_bed *b);
+uint64_t covh_bed_count(const covh_bed *b);
+int covh_bed_line(const covh_bed *b, uint64_t i, const char **chrom, uint32_t *chrom_len, uint32_t *start, uint32_t *end, const char **name,
+                  uint32_t *name_len, uint64_t *line_no);
+int covh_bed_resolve(const covh_bed *b, const covh_header *h, cov_depth_region *out);
+int covh_depth_regions_format(const covh_bed *b, const cov_depth_bin *results, int value, int no_zeros, int threads, int out_fd);
+int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_bed *b, int value, int no_zeros, int threads, int out_fd,
+                             uint64_t *n_regions_out);
+
 /* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
  * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.
  * covh_genome_fasta_paths resolves a directory (directory != NULL: regular files, symlinks followed, whose name ends in

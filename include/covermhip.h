@@ -156,7 +156,8 @@ typedef enum {
     COV_K_GENE_READS = 11, /* cov_interval_reads_compute: the kernels of the last call, summed (not part of a finish) */
     COV_K_DEPTH_RUNS = 12, /* cov_depth_runs_compute: the run kernels of the last chunk (marks, the two scans, emit), summed (not part of a finish) */
     COV_K_DEPTH_BINS = 13, /* cov_depth_bins_compute: the bin kernels of the last chunk (marks, the rank scan, init, reduce), summed (not part of a finish) */
-    COV_K_COUNT = 14
+    COV_K_DEPTH_REGIONS = 14, /* cov_depth_regions_compute: the region kernels of the last chunk (marks, the rank scan, init, reduce), summed (not part of a finish) */
+    COV_K_COUNT = 15
 } cov_kernel_id;
 
 /* --- lifecycle ------------------------------------------------------------------------------- */
@@ -448,7 +449,7 @@ cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
  * the host, the records from the first considered record of the contig in flight onwards move to the front of the store and the call
  * goes on ("a spill"); cov_finish / cov_fetch_hist / cov_gather then return the whole sample (record indices count from the sample's first
  * record).  What remains: ONE reference's records must fit (2^32 - 16 records and CIGAR words); after a spill cov_copy_depth,
- * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_depth_bins_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
+ * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_depth_bins_compute, cov_depth_regions_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
  * that has to hand its file to the CPU reader fails with COV_ERR_STATE instead of COV_ERR_INGEST_FALLBACK; a store that carries mate
  * columns (cov_ingest_want_mates) or an adopted device batch is never spilled.  cov_store_spills: spills since the last cov_reset. */
 uint32_t cov_store_spills(const cov_session *s);
@@ -531,7 +532,7 @@ cov_status cov_depth_runs_last(const cov_session *s, cov_depth_runs_info *out);
  *   cov_depth_bins_fetch(s, bin_off, bins)
  *         bin_off: tid_next - tid_lo + 1 entries relative to the chunk, the bins of target tid_lo + k are bins[bin_off[k] .. bin_off[k + 1])
  *         (an empty target repeats its neighbour's offset); bins: n_bins entries in target order, then position order.
- * The states are those of the depth runs.  The runs and the bins of a session share the chunk's arena: a cov_depth_runs_compute makes
+ * The states are those of the depth runs.  The runs and the bins of a session share the chunk's arena (with the regions below): a cov_depth_runs_compute makes
  * cov_depth_bins_fetch return COV_ERR_STATE until the next cov_depth_bins_compute, and the reverse.  cov_kernel_ms(COV_K_DEPTH_BINS) and
  * cov_depth_bins_last describe the last chunk. */
 typedef struct { uint64_t sum; int32_t min; int32_t max; uint32_t covered; uint32_t reserved; } cov_depth_bin; /* 24 B */
@@ -546,6 +547,39 @@ typedef struct {
 cov_status cov_depth_bins_compute(cov_session *s, uint32_t bin_size, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_bins);
 cov_status cov_depth_bins_fetch(cov_session *s, uint64_t *bin_off, cov_depth_bin *bins);
 cov_status cov_depth_bins_last(const cov_session *s, cov_depth_bins_info *out);
+
+/* ---- depth regions: the same per-base depth reduced over arbitrary intervals on the device (the regions of a BED file: exome or amplicon
+ * targets, genes, prophage or plasmid intervals, windows around a breakpoint).  A region is [start, end) of target tid, 0-based and half
+ * open, with start < end <= the target's length; regions may overlap, repeat and come in any order, and range from one base to a whole
+ * target.  Per region the fields of cov_depth_bin: the sum, the smallest and the largest depth of its bases and the number of bases with
+ * depth > 0 (no end exclusion: every base of the region counts).
+ *   cov_depth_regions_set(s, regions, n)
+ *         validates the regions against the session's targets and keeps a copy in a stable order by tid (the input order inside a target
+ *         is kept).  n == 0 clears them.  COV_ERR_STATE before cov_set_targets; COV_ERR_INVALID_ARG, with the first offending index in
+ *         cov_last_error, for tid >= n_targets, start >= end, end > length, reserved != 0 or n >= 2^32 (the regions set before stay).
+ *         cov_set_targets drops the regions; cov_reset and cov_finish keep them.
+ *   cov_depth_regions_compute(s, tid_lo, tid_hi, &tid_next, &n_regions)
+ *         chunks as cov_depth_runs_compute does (the same planner, budget and arena), and reduces the regions whose target lies in
+ *         [tid_lo, tid_next): a wave per piece of 4096 bases of a region (csrc/depth_regions_kernels.hip.h).  A chunk without a region is
+ *         legal (n_regions = 0); a chunk of 2^32 pieces or more is refused (COV_ERR_STATE); without regions set: COV_ERR_STATE.
+ *   cov_depth_regions_fetch(s, input_index, out)
+ *         the chunk's n_regions results; input_index[i] is the position of result i in the array given to cov_depth_regions_set.
+ * The states are those of the depth runs and bins.  Runs, bins and regions share the chunk's arena: a compute of one makes the fetch of the
+ * other two return COV_ERR_STATE until their own next compute.  cov_kernel_ms(COV_K_DEPTH_REGIONS) and cov_depth_regions_last describe the
+ * last chunk. */
+typedef struct { uint32_t tid, start, end, reserved; } cov_depth_region; /* 16 B, [start, end) */
+typedef struct {
+    uint64_t arena_bases; /* entries of the chunk's arena (padding included) */
+    uint64_t n_regions;   /* regions of the chunk */
+    uint64_t n_pieces;    /* waves of the reduction */
+    double arena_ms;      /* the pileup into the arena (with its zero fill), HIP-event time */
+    double regions_ms;    /* the region kernels = cov_kernel_ms(COV_K_DEPTH_REGIONS) */
+    uint32_t tid_lo, tid_next;
+} cov_depth_regions_info;
+cov_status cov_depth_regions_set(cov_session *s, const cov_depth_region *regions, uint64_t n);
+cov_status cov_depth_regions_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_regions);
+cov_status cov_depth_regions_fetch(cov_session *s, uint64_t *input_index, cov_depth_bin *out);
+cov_status cov_depth_regions_last(const cov_session *s, cov_depth_regions_info *out);
 
 /* Page-locked host memory for record batches, pooled: a freed block is kept for the next request of similar size
  * (a decoder filling one batch per BAM file gets its arrays back without re-pinning).  cov_host_alloc returns NULL
