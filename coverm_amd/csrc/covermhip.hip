@@ -259,9 +259,9 @@ struct cov_session {
     std::string err;
     int tile = 1024;  // bases per tile (one wave per tile: STREAM_TW)
     bool use_fast = true;  // k_pileup_fast + k_pileup_stream on the slow-tile list (default); COVERM_PILEUP=stream: k_pileup_stream alone
-    int chunk_tiles = 4;   // consecutive tiles walked by one wave.  (Round 4, when every chunk end paid the statistics' reductions and atomics: 4 -> 0.627 ms, 8 -> 0.596,
-                           // 16 -> 0.642, 32 -> 0.866.  With the statistics derived from the histogram a chunk end only moves bins and the better balance of short
-                           // chunks wins: profiles/hist_derived_stats_ab.json.)  COVERM_KNOBS pileup_chunk_tiles overrides it.
+    int chunk_tiles = (int)psched::CHUNK_TILES;   // consecutive tiles walked by one wave; COVERM_KNOBS pileup_chunk_tiles overrides both.  A chunk end only moves the wave's bins,
+    int chunk_tiles_listed = (int)psched::CHUNK_TILES_LISTED;      // so what decides is balance: without the deep-tile list 4 tiles (0.385 ms; 8: 0.456), with the deep tiles out
+                           // of the chunks 8 (0.363; 4: 0.372, 16: 0.378): profiles/pileup_schedule_ab.json
     int prep_kernel = 0;   // 0 = k_prep_lean (prep_lean.hip.h); COVERM_PREP_KERNEL=7 forces k_prep7s, the second implementation (tests)
     int est_lanes = -1;        // k_estimate_lanes / k_genome_estimate_lanes (a lane per contig / genome) from 65 536 of them on; COVERM_EST_LANES=1 | 0 forces it on / off (tests)
     int fast_tables = 1;       // k_pileup_fast (one table of biased deltas: the default) or k_pileup_fast2t (two count tables; COVERM_FAST_TABLES=2)
@@ -275,6 +275,9 @@ struct cov_session {
     DevBuf<u32> d_tlen, d_tile_contig, d_tile_start;
     DevBuf<u32> d_tile_first, d_tcnt, d_fov, d_tscan, d_ttop;   // TileIdx (pileup_kernels.hip.h)
     DevBuf<u32> d_slow_list;                                    // tiles k_ranges leaves to k_pileup_stream
+    DevBuf<u32> d_deep_list;                                    // tiles of deep_min candidate runs or more: k_pileup_fast visits them first, one per wave (pileup_schedule_core.h)
+    uint32_t deep_min = psched::DEEP_MIN;                                    // COVERM_KNOBS pileup_deep_min: 0 = no list, flagged tiles do not exist and every tile is walked in its chunk
+    uint32_t last_pileup_waves = 0, last_pileup_chunk = 0;      // waves and tiles per chunk of the last k_pileup_fast launch (cov_pileup_schedule)
     uint32_t tile_shift = 10;
     DevBuf<u32> d_cx_list, d_cx_cnt, d_cx_cur, d_cx_scan, d_cx_top;   // CxIdx: long-CIGAR buckets
     DevBuf<uint2> d_cx_runs;
@@ -590,14 +593,13 @@ int pileup_occupancy(const cov_session *s, std::atomic<int> (&occ_dev)[64], cons
     }
     return occ;
 }
-// Grid = 8x the resident workgroups (registers, not LDS, bound residency): each wave still walks several chunks
-// and keeps its sums in registers across them, but the hardware dispatcher hands out the 8 successive "rounds",
-// which evens out the heavy-tailed per-chunk cost far better than a purely persistent grid (measured, 50 M reads:
-// 1.06 ms at 1x, 0.905 ms at 8x, 0.956 ms at one chunk per wave).
-u32 pileup_grid(const cov_session *s, int occ, u32 n_tiles) {
-    const u32 n_chunks = (n_tiles + (u32)s->chunk_tiles - 1) / (u32)s->chunk_tiles, wg_per_cu = 8u * (u32)occ;
-    return std::max(1u, std::min((n_chunks + 3) / 4, (u32)s->n_cus * wg_per_cu));
+// Grid = psched::PILEUP_ROUNDS x the resident workgroups (registers, not LDS, bound residency), at most a wave per chunk
+// (pileup_schedule_core.h): each wave still walks several chunks, and the hardware dispatcher hands out the successive "rounds".
+u32 pileup_grid(const cov_session *s, int occ, u32 n_tiles) {      // (k_pileup_stream; occ = resident workgroups of 256 threads per CU)
+    return psched::grid_of(n_tiles, (u32)s->chunk_tiles, (u32)s->n_cus, (u32)occ * 4u, psched::STREAM_WG_WAVES);
 }
+// the deep-tile list of the last k_ranges, for a k_pileup_fast launch over every tile (nullptr: none was written)
+const u32 *pileup_deep_list(const cov_session *s) { return s->use_fast && s->deep_min != 0u ? s->d_deep_list.p : nullptr; }
 
 // k_pileup_fast over every tile (it skips the ones k_ranges flagged TILE_F_SLOW)
 template <bool H, int TABLES>
@@ -606,7 +608,13 @@ void launch_fast_v(cov_session *s, const PileupArgs &a, u32 n_tiles) {
     const size_t smem = pileup_fast_smem_bytes(H, TABLES == 1 ? FAST_HB : FAST_HB7, TABLES);
     static std::atomic<int> occ_dev[64];
     const int occ = pileup_occupancy(s, occ_dev, reinterpret_cast<const void *>(kern), smem);
-    hipLaunchKernelGGL(kern, dim3(pileup_grid(s, occ, n_tiles)), dim3(256), smem, s->stream, a, n_tiles, (u32)s->chunk_tiles);
+    // the list holds tile numbers of the whole sample: only a launch over all of it, from tile 0, may take it
+    const u32 *deep_list = a.tile_base == 0u && n_tiles == s->n_tiles ? pileup_deep_list(s) : nullptr;
+    const u32 chunk = (u32)(deep_list != nullptr ? s->chunk_tiles_listed : s->chunk_tiles);
+    constexpr u32 WGW = psched::FAST_WG_WAVES;      // (occ = resident workgroups of 256 threads per CU: registers bound residency, so 4 x occ waves)
+    const u32 grid = psched::grid_of(n_tiles, chunk, (u32)s->n_cus, (u32)occ * 4u, WGW);
+    s->last_pileup_waves = grid * WGW; s->last_pileup_chunk = chunk;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(64u * WGW), smem / 4u * WGW, s->stream, a, n_tiles, chunk, deep_list, (const u32 *)&s->d_glob.p->n_deep);
 }
 template <bool H>
 void launch_fast_t(cov_session *s, const PileupArgs &a, u32 n_tiles) {
@@ -757,7 +765,8 @@ cov_status cov_create(const cov_config *cfg, cov_session **out) {
     if (const char *im = getenv("COVERM_IDENTITY")) s->id_mode = strcmp(im, "serial") ? 1 : 0;
     { long long v; if (covknob::get("store_cap_records", v) && v >= 1) s->cap_records = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
     { long long v; if (covknob::get("store_cap_cigar", v) && v >= 1) s->cap_cigar = std::min<uint64_t>((uint64_t)v, 0xfffffff0ull); }
-    { long long v; if (covknob::get("pileup_chunk_tiles", v) && v >= 1 && v <= 64) s->chunk_tiles = (int)v; }
+    { long long v; if (covknob::get("pileup_chunk_tiles", v) && v >= 1 && v <= 64) s->chunk_tiles = s->chunk_tiles_listed = (int)v; }
+    { long long v; if (covknob::get("pileup_deep_min", v) && v >= 0 && v <= 0x7fffffffll) s->deep_min = (uint32_t)v; }
     { long long v; if (covknob::get("depth_chunk_bases", v) && v >= 4) s->dr.chunk_bases = (uint64_t)v; }
     // (every stream costs ~6 ms to create and as much again when the process ends, tools/ubench/exit_probe: the side stream of the
     // identity kernels is created by the first cov_finish that wants it, and borrows the ingest's second stream when there is one)
@@ -789,7 +798,7 @@ void cov_destroy(cov_session *s) {
     s->d_sgid.release(); s->d_sblk.release(); s->d_sent_pos.release(); s->d_stop_last1.release(); s->d_stop_first.release(); s->d_scounts.release(); s->d_scode.release();
     s->d_stop_cnt.release(); s->d_stop_seg.release(); s->d_sent.release();
     s->d_gout.release(); if (s->h_gout) (void)hipHostFree(s->h_gout); s->h_gout = nullptr;
-    s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release();
+    s->d_tile_first.release(); s->d_tcnt.release(); s->d_fov.release(); s->d_tscan.release(); s->d_ttop.release(); s->d_slow_list.release(); s->d_deep_list.release();
     s->dr.release(); s->d_ctg_scratch.release(); s->d_depth_all.release(); s->d_depth_off.release(); s->d_iv.release(); s->d_ivst.release(); s->d_ivhist.release();
     s->gr_code.release(); s->gr_mism.release(); s->gr_trec.release(); s->gr_pprim.release(); s->gr_tids.release(); s->gr_ttid.release(); s->gr_tpos.release(); s->gr_ident.release();
     s->gr_tident.release(); s->gr_ck.release(); s->gr_bcnt.release(); s->gr_bmism.release(); s->gr_pmism.release(); s->gr_glob.release(); s->gr_iv.release(); s->gr_out.release(); s->gr_bounds.release();
@@ -860,6 +869,7 @@ cov_status cov_set_targets(cov_session *s, uint32_t n_targets, const uint64_t *t
     HIPCHK(s->d_tcnt.reserve(std::max<size_t>(1, nt), s->stream)); HIPCHK(s->d_fov.reserve(std::max<size_t>(1, nt), s->stream));
     HIPCHK(s->d_tscan.reserve(std::max<size_t>(1, nt), s->stream)); HIPCHK(s->d_ttop.reserve(nt / 1024 + 2, s->stream));
     HIPCHK(s->d_slow_list.reserve(std::max<size_t>(1, nt), s->stream));
+    HIPCHK(s->d_deep_list.reserve(std::max<size_t>(1, nt), s->stream));
     HIPCHK(s->d_cx_cnt.reserve(std::max<size_t>(1, nt), s->stream)); HIPCHK(s->d_cx_cur.reserve(std::max<size_t>(1, nt), s->stream));
     HIPCHK(s->d_cx_scan.reserve(std::max<size_t>(1, nt), s->stream)); HIPCHK(s->d_cx_top.reserve(nt / 1024 + 2, s->stream));
     HIPCHK(hipMemcpyAsync(s->d_tile_first.p, s->h_tile_first.data(), ((size_t)n_targets + 1) * 4, hipMemcpyHostToDevice, s->stream));
@@ -1353,9 +1363,10 @@ static cov_status stage_ranges(cov_session *s, const FinishPlan &p, const PassVi
     hipLaunchKernelGGL(k_tile_scan2, dim3(2), dim3(1024), 0, v.st, sp, n_blocks);
     hipLaunchKernelGGL((k_cx_expand<true>), dim3(cx_grid), dim3(256), 0, v.st, v.r, s->d_tlen.p, s->d_glob.p, v.cx, v.ti);
     u32 *slow_list = s->use_fast ? s->d_slow_list.p : nullptr;
+    u32 *deep_list = const_cast<u32 *>(pileup_deep_list(s));
     const auto ranges = p.want_hist ? &k_ranges<true> : &k_ranges<false>;
     hipLaunchKernelGGL(ranges, dim3((s->n_tiles + 255) / 256), dim3(256), 0, v.st, s->d_tile_contig.p, s->d_tile_start.p, s->n_tiles, s->d_tlen.p,
-                       v.mask, s->d_ctg.p, s->d_desc.p, v.ti, s->d_tscan.p, s->d_ttop.p, v.cx, s->d_glob.p, slow_list);
+                       v.mask, s->d_ctg.p, s->d_desc.p, v.ti, s->d_tscan.p, s->d_ttop.p, v.cx, s->d_glob.p, slow_list, deep_list, s->deep_min);
     time_end(s, COV_K_RANGES);
     HIPCHK(hipGetLastError());
     return COV_OK;
@@ -3401,6 +3412,12 @@ cov_status cov_last_paths(const cov_session *s, cov_path_counts *out) {
     out->listed_steps = s->h_glob.n_gen; out->generic_only = s->last_gen_all ? 1u : 0u;
     out->slow_tiles = s->h_glob.n_slow; out->bucket_records = s->h_glob.n_cx;
     out->bucket_entries = (uint32_t)std::min<uint64_t>(s->h_glob.cx_total, 0xffffffffull); out->passes = s->last_passes;
+    return COV_OK;
+}
+
+cov_status cov_pileup_schedule(const cov_session *s, uint32_t out[4]) {
+    if (!s || !out) return COV_ERR_INVALID_ARG;
+    out[0] = s->h_glob.n_deep; out[1] = s->last_pileup_waves; out[2] = s->last_pileup_chunk; out[3] = s->deep_min;
     return COV_OK;
 }
 

@@ -2,7 +2,9 @@
 // variable, COVERM_KNOBS="name=value,name=value" (e.g. "store_cap_records=50000,ingest_round_blocks=128"), looked up where a session, an
 // ingest or a reader is set up and never in a launch path.  A name that is absent leaves the built-in size in place.  The names:
 //   store_cap_records, store_cap_cigar      cov_create: the bounded record store (covermhip.hip)
-//   pileup_chunk_tiles                      cov_create: consecutive tiles one wave of the pileup kernels walks (1 .. 64)
+//   pileup_chunk_tiles                      cov_create: consecutive tiles one wave of the pileup kernels walks (1 .. 64; default 4, and 8 for k_pileup_fast with its deep-tile list)
+//   pileup_deep_min                         cov_create: tiles with this many candidate runs or more go on k_pileup_fast's deep-tile list and are visited
+//                                           first, one per wave (pileup_schedule_core.h); 0: no list, 1 upwards: the threshold (default 192)
 //   ingest_round_blocks, ingest_carry_kb, ingest_cwin_kb      cov_ingest_begin: blocks per inflate window, carry buffer, compressed window
 //   depth_chunk_bases                       cov_create: arena entries of one chunk of cov_depth_runs_compute / cov_depth_bins_compute / cov_depth_regions_compute (default 2^28)
 //   pair_chunk                              cov_pair_filter: records per table chunk

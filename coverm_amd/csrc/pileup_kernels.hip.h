@@ -22,6 +22,8 @@
 
 #define HSTC_FN __host__ __device__ __forceinline__
 #include "hist_stats_core.h"
+#define PSCHED_FN __host__ __device__ __forceinline__
+#include "pileup_schedule_core.h"
 #include "scan_ops.hip.h"
 
 namespace covk {
@@ -35,7 +37,7 @@ constexpr u32 F_POS_UNSORTED = 1u;
 // run-word types (top two bits of .y)
 constexpr u32 RW_SINGLE = 0u, RW_DOUBLE = 1u, RW_COMPLEX = 2u, RW_BUCKET = 3u;
 constexpr u32 FAST_MAX_CAND = 8191u;     // tiles with more candidate runs than this go to k_pileup_stream (k_pileup_fast's table holds 16-bit fields of 4 x the delta)
-constexpr u32 TILE_F_GENERIC = 1u, TILE_F_SLOW = 2u;   // tile descriptor flags (desc[2t].w)
+constexpr u32 TILE_F_GENERIC = 1u, TILE_F_SLOW = 2u, TILE_F_DEEP = 4u;   // tile descriptor flags (desc[2t].w); DEEP: on k_pileup_fast's deep-tile list (never together with SLOW)
 constexpr u32 CX_MIN_OPS = 16;   // RW_COMPLEX records with more CIGAR operations than this go through the per-tile buckets
 
 // Per-contig device accumulators (128 B).
@@ -70,7 +72,8 @@ struct DevGlobal {
     u64 pad2[2];
     u64 prim_slots[COUNTER_SLOTS * 8];  // sum = num_detected_primary_alignments (bam_generator.rs:114-118)
     u64 cons_slots[COUNTER_SLOTS * 8];  // sum = number of considered records
-    u32 pad_q[8 * 16];                  // (k_pileup_stream's work-queue counters until round 6; kept so that the block's size does not change)
+    u32 n_deep;          // tiles k_ranges flagged TILE_F_DEEP (k_pileup_fast visits them first, one per wave), listed in deep_list
+    u32 pad_q[8 * 16 - 1];              // (k_pileup_stream's work-queue counters until round 6; kept so that the block's size does not change)
 };
 
 struct FilterCfg {
@@ -166,7 +169,7 @@ __global__ void k_init(DevContig *ctg, u32 n_targets, DevGlobal *g, TileIdx ti, 
     if (c < ti.n_tiles) { ti.tcnt[c] = 0u; ti.fov[c] = 0xffffffffu; cx.cnt[c] = 0u; cx.cur[c] = 0u; }
     if (c == 0) {
         g->first_error = ~0ull; g->hist_cap_total = 0; g->chist_total = 0; g->internal_error = 0;
-        g->n_cx = 0; g->cx_total = 0; g->n_slow = 0; g->n_gen = 0;
+        g->n_cx = 0; g->cx_total = 0; g->n_slow = 0; g->n_gen = 0; g->n_deep = 0;
     }
     if (c < COUNTER_SLOTS * 8) { g->prim_slots[c] = 0; g->cons_slots[c] = 0; }
     if (c >= n_targets) return;
@@ -860,7 +863,7 @@ __global__ __launch_bounds__(256) void k_ranges(const u32 *__restrict__ tile_con
                                                 u32 n_tiles, const u32 *__restrict__ tlen, const uint8_t *__restrict__ mask,
                                                 DevContig *ctg, uint4 *__restrict__ desc, TileIdx ti,
                                                 const u32 *__restrict__ tscan, const u32 *__restrict__ ttop, CxIdx cx,
-                                                DevGlobal *__restrict__ g, u32 *__restrict__ slow_list) {
+                                                DevGlobal *__restrict__ g, u32 *__restrict__ slow_list, u32 *__restrict__ deep_list, u32 deep_min) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_tiles) return;
     const u32 c = tile_contig[t];
@@ -890,6 +893,23 @@ __global__ __launch_bounds__(256) void k_ranges(const u32 *__restrict__ tile_con
         if (out.w || out.y - out.x + cxn > FAST_MAX_CAND) {
             out.w |= TILE_F_SLOW;
             if (slow_list != nullptr) slow_list[atomicAdd(&g->n_slow, 1u)] = t;
+        }
+    }
+    // Tiles k_pileup_fast takes and that hold deep_min candidates or more go on its deep-tile list (pileup_schedule_core.h).  They are
+    // neighbours (the tiles of a few abundant contigs), so a wave appends its tiles with ONE atomic: ballot, popcount, lane rank (an
+    // atomic per tile serialises on the counter: DESIGN.md 3d).  The order of the list is arbitrary.
+    if (deep_list != nullptr) {
+        const bool deep = (out.x < out.y || cxn) && !(out.w & TILE_F_SLOW) && out.y - out.x + cxn >= deep_min;
+        const u64 dm = __ballot(deep);
+        if (dm != 0ull) {       // (wave-uniform)
+            const int lane = lane_id(), lead = __ffsll((long long)dm) - 1;
+            u32 base = 0;
+            if (lane == lead) base = atomicAdd(&g->n_deep, (u32)__popcll(dm));
+            base = (u32)__builtin_amdgcn_readlane((int)base, lead);
+            if (deep) {
+                out.w |= TILE_F_DEEP;
+                deep_list[base + (u32)__popcll(dm & (lane == 0 ? 0ull : (~0ull >> (64 - lane))))] = t;
+            }
         }
     }
     if (WANT_HIST) {   // one atomic per wave when all its tiles belong to one contig (the usual case)
@@ -1600,7 +1620,7 @@ __device__ __forceinline__ void lds_atomic_add(u32 addr, u32 x) { (void)__hip_at
 // to preset and to read back per tile (two ds_write_b128 + two ds_read_b128 instead of four each), an xor with 0x80008000 instead of the
 // packed subtraction of the two tables, the same events.
 template <bool WANT_HIST, int HB, int TABLES>
-__device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tiles, u32 chunk_tiles) {
+__device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tiles, u32 chunk_tiles, const u32 *__restrict__ deep_list, const u32 *__restrict__ n_deep_ptr) {
     constexpr int TW = FAST_TW, HBW = HB;
     constexpr int DS = TABLES == 1 ? 2 : 0;      // the one-table kernel counts in units of 1/4: an event adds or subtracts 4, so the running depth IS the byte offset of its bin
     constexpr size_t WB = (size_t)TW * 2 * TABLES + (WANT_HIST ? (size_t)HBW * 4 : 0);
@@ -1610,7 +1630,8 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
     u32 *E = TABLES == 2 ? S + TW / 2 : S;
     u32 *lhist = S + (TW / 2) * TABLES;
     uint4 *S4 = reinterpret_cast<uint4 *>(S), *E4 = reinterpret_cast<uint4 *>(E);
-    const u32 wave_id = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4u + (u32)w)), n_waves = gridDim.x * 4u;
+    const u32 wpb = blockDim.x >> 6;      // waves per workgroup: psched::FAST_WG_WAVES on the host's launches (there is no barrier in here, and the LDS is carved per wave)
+    const u32 wave_id = (u32)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (u32)w)), n_waves = gridDim.x * wpb;
     if (WANT_HIST) {
 #pragma unroll
         for (int b = lane; b < HBW; b += 64) lhist[b] = 0u;
@@ -1678,30 +1699,43 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
         r0 = i0 < d.y ? a.runs[i0] : make_uint2(0u, 0u);
         r1 = i1 < d.y ? a.runs[i1] : make_uint2(0u, 0u);
     };
-    // tile sequence of this wave: chunks wave_id, wave_id + n_waves, ... of chunk_tiles consecutive tiles each
-    const u32 n_chunks = (n_tiles + chunk_tiles - 1) / chunk_tiles;
-    if (wave_id >= n_chunks) return;
-    u32 ch = wave_id;
-    u32 t = ch * chunk_tiles, t_end = min(t + chunk_tiles, n_tiles);
+    // tile sequence of this wave (pileup_schedule_core.h): the deep-tile list's entries wave_id, wave_id + n_waves, ... one tile per visit,
+    // then the chunks wave_id, wave_id + n_waves, ... of chunk_tiles consecutive tiles each, without the tiles flagged for the list.
+    // deep_list == nullptr: no list, flagged tiles (if any) are walked in place.
+    const psched::Launch sched = psched::launch_of(n_tiles, chunk_tiles, n_waves, deep_list != nullptr ? *n_deep_ptr : 0u);
+    const u32 skip_flags = TILE_F_SLOW | (deep_list != nullptr ? TILE_F_DEEP : 0u);      // tiles a chunk visit leaves out
+    psched::Visit vis = psched::first(sched, wave_id);
+    if (vis.done) return;
+    // tile of the list visit after the current one: fetched a visit ahead, so that the next descriptor's address never waits for the list
+    u32 lt_next = 0;
+    u32 t, t_end;
+    if (vis.in_list) {
+        t = deep_list[vis.idx]; t_end = t + 1u;
+        if (vis.idx + n_waves < sched.n_deep) lt_next = deep_list[vis.idx + n_waves];
+    } else { t = psched::chunk_t0(sched, vis.idx); t_end = psched::chunk_t1(sched, vis.idx); }
     uint4 ds = a.desc[2 * (size_t)(a.tile_base + t)], dC1 = a.desc[2 * (size_t)(a.tile_base + t) + 1];
     uint2 rw0, rw1;
     load_runs(ds, rw0, rw1);
     for (;;) {
         // ---- next tile of the sequence (wave-uniform), its descriptor requested now
-        u32 tn = t + 1, tn_end = t_end, chn = ch;
-        bool chunk_end = false;
+        u32 tn = t + 1, tn_end = t_end;
+        psched::Visit visn = vis;
+        bool chunk_end = false;      // the visit ends with this tile: its bins move (neighbours in the list are unrelated, like two chunks)
         if (tn >= t_end) {
             chunk_end = true;
-            chn = ch + n_waves;
-            tn = chn < n_chunks ? chn * chunk_tiles : 0xffffffffu;
-            tn_end = chn < n_chunks ? min(tn + chunk_tiles, n_tiles) : 0u;
+            visn = psched::next(sched, wave_id, vis);
+            if (visn.done) { tn = 0xffffffffu; tn_end = 0u; }
+            else if (visn.in_list) {
+                tn = lt_next; tn_end = tn + 1u;
+                if (visn.idx + n_waves < sched.n_deep) lt_next = deep_list[visn.idx + n_waves];
+            } else { tn = psched::chunk_t0(sched, visn.idx); tn_end = psched::chunk_t1(sched, visn.idx); }
         }
         const bool have_next = tn != 0xffffffffu;
         uint4 nds = make_uint4(0u, 0u, 0u, 0u), ndC1 = make_uint4(0u, 0u, 0u, 0u);
         if (have_next) { nds = a.desc[2 * (size_t)(a.tile_base + tn)]; ndC1 = a.desc[2 * (size_t)(a.tile_base + tn) + 1]; }
 
         const u32 c = dC1.x, lo = dC1.y, L = ds.z, cxo = dC1.z, cxn = dC1.w;
-        const bool live = (ds.x < ds.y || cxn != 0u) && !(ds.w & TILE_F_SLOW);
+        const bool live = (ds.x < ds.y || cxn != 0u) && (vis.in_list || !(ds.w & skip_flags));
         uint4 sv0, sv1, ev0, ev1;
         if (live) {
             if ((int)c != cur_c) {
@@ -1882,21 +1916,22 @@ __device__ __forceinline__ void pileup_fast_body(const PileupArgs &a, u32 n_tile
         }
         if (chunk_end) { flush(); cur_c = -1; }
         if (!have_next) break;
-        t = tn; t_end = tn_end; ch = chn; ds = nds; dC1 = ndC1; rw0 = nrw0; rw1 = nrw1;
+        t = tn; t_end = tn_end; vis = visn; ds = nds; dC1 = ndC1; rw0 = nrw0; rw1 = nrw1;
     }
 }
 
-// The default (round 6): ONE table of biased deltas, 512 LDS bins (16 KiB of LDS per workgroup), seven waves per SIMD: 0.475 ms at BASELINE
-// config 2 against 0.531 for the two-table kernel below, alternating runs on one box (profiles/r06_lean_onetable_ab_5k.log; 384 bins 0.481,
-// eight waves with 28 bytes of scratch 0.521).
+// The default (round 6): ONE table of biased deltas, 512 LDS bins (4 KiB of LDS per wave): 0.475 ms at BASELINE config 2 against 0.531 for
+// the two-table kernel below, alternating runs on one box (profiles/r06_lean_onetable_ab_5k.log; 384 bins 0.481).  Eight waves per SIMD: the
+// body fits 64 registers WITHOUT scratch (63 / 64 with and without the histogram), 0.372 ms against 0.385 at seven
+// (profiles/pileup_schedule_ab.json; an eighth wave bought with scratch lost three times, DESIGN.md 3d: check the resource summary when the body changes).
 template <bool WANT_HIST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_pileup_fast(PileupArgs a, u32 n_tiles, u32 chunk_tiles) {
-    pileup_fast_body<WANT_HIST, FAST_HB, 1>(a, n_tiles, chunk_tiles);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_pileup_fast(PileupArgs a, u32 n_tiles, u32 chunk_tiles, const u32 *__restrict__ deep_list, const u32 *__restrict__ n_deep) {
+    pileup_fast_body<WANT_HIST, FAST_HB, 1>(a, n_tiles, chunk_tiles, deep_list, n_deep);
 }
 // The second implementation (COVERM_FAST_TABLES=2; rounds 4-5's default): two u16 count tables, 384 bins; six waves per SIMD (with the clipped loop for contig ends the body no longer fits 72 registers without scratch).
 template <bool WANT_HIST>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_pileup_fast2t(PileupArgs a, u32 n_tiles, u32 chunk_tiles) {
-    pileup_fast_body<WANT_HIST, FAST_HB7, 2>(a, n_tiles, chunk_tiles);
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_pileup_fast2t(PileupArgs a, u32 n_tiles, u32 chunk_tiles, const u32 *__restrict__ deep_list, const u32 *__restrict__ n_deep) {
+    pileup_fast_body<WANT_HIST, FAST_HB7, 2>(a, n_tiles, chunk_tiles, deep_list, n_deep);
 }
 
 // (The same step once more — 256 bins, 64 registers with 12 dwords of scratch, eight waves per SIMD — was measured in round 5: 0.816 ms

@@ -461,6 +461,13 @@ class Session:
         return dict(listed_steps=int(v[0]), generic_only=bool(v[1]), slow_tiles=int(v[2]), bucket_records=int(v[3]),
                     bucket_entries=int(v[4]), passes=int(v[5]))
 
+    def pileup_schedule(self):
+        """cov_pileup_schedule: how the last finish handed k_pileup_fast's tiles to its waves: tiles on the deep-tile list (0: none used),
+        waves launched, tiles per chunk, the list's threshold (COVERM_KNOBS pileup_deep_min)."""
+        v = (C.c_uint32 * 4)()
+        self._check(self._lib.cov_pileup_schedule(self._h, C.byref(v)))
+        return dict(deep_tiles=int(v[0]), waves=int(v[1]), chunk_tiles=int(v[2]), deep_min=int(v[3]))
+
     def run_words(self):
         """cov_copy_run_words: the run word k_prep left for every record of the store in the last finish, as uint64 (x | y << 32).  Raises
         CovError (COV_ERR_STATE) when there are none for the whole store: no records, an adopted device batch, a spilled store."""

@@ -101,7 +101,7 @@ class CovDepthRegionsInfo(C.Structure):
 
 EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "cov_set_targets",
            "cov_set_target_mask", "cov_push_batch", "cov_push_batch_device", "cov_finish", "cov_fetch_hist",
-           "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths", "cov_copy_run_words",
+           "cov_copy_depth", "cov_reset", "cov_kernel_ms", "cov_algorithmic_bytes", "cov_last_paths", "cov_pileup_schedule", "cov_copy_run_words",
            "cov_set_genomes", "cov_finish_genomes", "cov_fetch_genome_estimates", "cov_fetch_genome_stats",
            "cov_set_genome_runs", "cov_genome_entry_count", "cov_fetch_genome_entries",
            "cov_sam_begin", "cov_sam_window_bytes", "cov_sam_slot_wait", "cov_sam_feed", "cov_sam_end", "cov_ingest_last_stats",
@@ -159,6 +159,7 @@ def lib():
     L.cov_kernel_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint32)]
     L.cov_algorithmic_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
     L.cov_last_paths.argtypes = [C.c_void_p, C.POINTER(C.c_uint32 * 6)]
+    L.cov_pileup_schedule.argtypes = [C.c_void_p, C.POINTER(C.c_uint32 * 4)]
     L.cov_copy_run_words.argtypes = [C.c_void_p, C.c_void_p]
     L.cov_copy_records.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.cov_set_estimators.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]

@@ -344,6 +344,10 @@ cov_status cov_kernel_ms(const cov_session *s, cov_kernel_id k, double *ms_total
  * pipeline over the store (2: the bucket buffer was too small for bucket_entries, it was grown and the pass repeated). */
 typedef struct { uint32_t listed_steps, generic_only, slow_tiles, bucket_records, bucket_entries, passes; } cov_path_counts;
 cov_status cov_last_paths(const cov_session *s, cov_path_counts *out);
+/* How the last cov_finish handed k_pileup_fast's tiles to its waves (csrc/pileup_schedule_core.h): out[0] = tiles on the deep-tile list
+ * (0: no list was used), out[1] = waves launched, out[2] = tiles per chunk, out[3] = the list's threshold in candidate runs
+ * (COVERM_KNOBS pileup_deep_min; 0 = off). */
+cov_status cov_pileup_schedule(const cov_session *s, uint32_t out[4]);
 /* Test hook: the 8-byte run words k_prep left in the last cov_finish, one per record of the store in store order, as x | (uint64_t)y << 32
  * (x = start of the first merged M/=/X run, y = 0 or type << 30 | fields: SINGLE 0, DOUBLE 1 with len1 | gap << 10 | len2 << 18, COMPLEX 2,
  * BUCKET 3).  COV_ERR_STATE when the last finish did not leave run words for the whole store: no finish, no records, an adopted device
