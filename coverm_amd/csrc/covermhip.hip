@@ -29,6 +29,7 @@
 #include <string>
 #include <future>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/covermhip.h"
@@ -52,6 +53,7 @@ static_assert(sizeof(cov_contig_stats) == 128 && offsetof(cov_contig_stats, sum_
 static_assert(sizeof(cov_ingest_stats) == 56 && offsetof(cov_ingest_stats, max_hop_records) == 32 && offsetof(cov_ingest_stats, repaired_starts) == 48, "cov_ingest_stats layout");
 static_assert(sizeof(cov_summary) == 32 && offsetof(cov_summary, hist_total) == 24, "cov_summary layout");
 static_assert(sizeof(cov_interval) == 24 && sizeof(cov_interval_stats) == 56, "interval struct layout");
+static_assert(COV_DEPTH_MAX_CUTS == dclc::MAX_CUTS, "cut lists");
 static_assert(sizeof(cov_depth_run) == 8 && offsetof(cov_depth_run, depth) == 4 && sizeof(cov_depth_runs_info) == 40 && offsetof(cov_depth_runs_info, tid_lo) == 32, "depth run struct layout");
 static_assert(sizeof(cov_depth_bin) == 24 && sizeof(cov_depth_bin) == sizeof(dbnc::Bin) && offsetof(cov_depth_bin, min) == 8 && offsetof(dbnc::Bin, min) == 8 && offsetof(cov_depth_bin, max) == 12 &&
               offsetof(dbnc::Bin, max) == 12 && offsetof(cov_depth_bin, covered) == 16 && offsetof(dbnc::Bin, covered) == 16 && offsetof(cov_depth_bin, reserved) == 20 &&
@@ -331,13 +333,16 @@ struct cov_session {
         std::vector<drgc::Region> h_reg; std::vector<u32> h_reg_input, h_reg_first;
         bool have_regions = false;
         DevBuf<drgc::Desc> reg_desc; DevBuf<u32> reg_piece_off; DevBuf<dbnc::Bin> regs;
+        // the thresholds of cov_depth_thresholds_set (thr.n == 0: none; kept over set_targets, reset and finish) and, of the last chunk computed
+        // with them, its counts: n_regs x g_thr, row-major in the result order
+        dclc::Cuts thr = {}; DevBuf<u32> reg_counts; u32 g_thr = 0;
         std::vector<drgc::Desc> h_reg_desc; std::vector<u32> h_reg_piece_off;
         bool regs_valid = false;
         u32 g_lo = 0, g_next = 0, g_launches = 0, g_first = 0;      // g_first: the chunk's first region in h_reg
         u64 n_regs = 0, n_pieces = 0, g_arena_bases = 0;
         float g_arena_ms = 0.f, regs_ms = 0.f;            // of the last chunk of regions (COV_K_DEPTH_REGIONS)
         void drop() { valid = false; bins_valid = false; regs_valid = false; taker[0] = taker[1] = taker[2] = 0; }      // push / reset / finish: none is there
-        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); bins.release(); bin_off.release(); reg_desc.release(); reg_piece_off.release(); regs.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
+        void release() { arena.release(); woff.release(); mask.release(); rank.release(); sums.release(); run_off.release(); doff.release(); total.release(); runs.release(); bins.release(); bin_off.release(); reg_desc.release(); reg_piece_off.release(); regs.release(); reg_counts.release(); if (ev_mid) (void)hipEventDestroy(ev_mid); ev_mid = nullptr; }
     } dr;
     DevBuf<uint8_t> d_mask;
     std::vector<uint8_t> h_mask;       // host copy (convert_results lays the compact histogram out itself)
@@ -3091,13 +3096,15 @@ static cov_status depth_arena_stage(cov_session *s, const char *who, int party, 
     return COV_OK;
 }
 
-cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
-    if (!s) return COV_ERR_INVALID_ARG;
-    if (s->ing.active) { s->err = "cov_depth_runs_compute: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
-    if (!s->finished) { s->err = "cov_depth_runs_compute: needs a cov_finish over the records"; return COV_ERR_STATE; }
-    if (s->spill.active) { s->err = "cov_depth_runs_compute: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+// `view`: dprc::Identity (cov_depth_runs_compute: runs of equal depth) or dclc::ClassView (cov_depth_class_runs_compute: runs of equal depth
+// class); the chunk, the launches and what the fetch finds are the same.
+extern "C++" template <class View>
+static cov_status depth_runs_compute(cov_session *s, const char *who, const View &view, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
+    if (s->ing.active) { s->err = std::string(who) + ": a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (!s->finished) { s->err = std::string(who) + ": needs a cov_finish over the records"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = std::string(who) + ": part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
     if (!tid_next || !n_runs || tid_lo >= tid_hi || tid_hi > s->n_targets) return COV_ERR_INVALID_ARG;
-    covr::Range rr("depth runs of one chunk (cov_depth_runs_compute)");
+    covr::Range rr(std::is_same<View, dprc::Identity>::value ? "depth runs of one chunk (cov_depth_runs_compute)" : "depth class runs of one chunk (cov_depth_class_runs_compute)");
     cov_session::DepthRuns &D = s->dr;
     HIPCHK(hipSetDevice(s->cfg.device));
     timing_events(s);
@@ -3106,21 +3113,21 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     if (!D.ev_mid) HIPCHK(hipEventCreate(&D.ev_mid));
     // ---- the arena and scan #1 (the rank of every mask word)
     DepthChunk ck;
-    if (const cov_status rc = depth_arena_stage(s, "cov_depth_runs_compute", cov_session::DepthRuns::RUNS, tid_lo, tid_hi, ev, ck)) return rc;
+    if (const cov_status rc = depth_arena_stage(s, who, cov_session::DepthRuns::RUNS, tid_lo, tid_hi, ev, ck)) return rc;
     const u32 t1 = ck.t1, nT = ck.nT, words = ck.words;
     HIPCHK(D.run_off.reserve((size_t)nT + 1, st));
     // ---- scan #2, first half: the words' run starts counted, the block offsets and the total
-    const covdr::WordCount wc{D.arena.p, D.mask.p};
+    const covdr::WordCountT<View> wc{view, D.arena.p, D.mask.p};
     scan_offsets(st, wc, words, D.sums.p, D.total.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(D.ev_mid, st));
     u64 total = 0;
     HIPCHK(hipMemcpyAsync(&total, D.total.p, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
-    if (total > 0xffffffffull) { s->err = "cov_depth_runs_compute: more than 2^32 runs in one chunk"; return COV_ERR_STATE; }      // (at most one run per entry: only a chunk of exactly 2^32 entries, every one a run, gets here)
+    if (total > 0xffffffffull) { s->err = std::string(who) + ": more than 2^32 runs in one chunk"; return COV_ERR_STATE; }      // (at most one run per entry: only a chunk of exactly 2^32 entries, every one a run, gets here)
     HIPCHK(D.runs.reserve(std::max<u64>(total, 1), st));
     // ---- scan #2, second half: every word's runs written at its exclusive prefix, a target's first word leaves its run offset
-    const covdr::WordEmit we{D.arena.p, D.mask.p, D.rank.p, D.woff.p, D.runs.p, D.run_off.p};
+    const covdr::WordEmitT<View> we{view, D.arena.p, D.mask.p, D.rank.p, D.woff.p, D.runs.p, D.run_off.p};
     float ms_arena = 0.f, ms_a = 0.f, ms_b = 0.f;
     (void)hipEventElapsedTime(&ms_arena, ev[0], ev[1]);
     (void)hipEventElapsedTime(&ms_a, ev[1], D.ev_mid);
@@ -3135,9 +3142,29 @@ cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_
     D.lo = tid_lo; D.next = t1; D.n_runs = total; D.arena_bases = 4ull * words; D.valid = true;
     *tid_next = t1; *n_runs = total;
     if (cov_timing_on())
-        fprintf(stderr, "[covermhip] depth runs: targets [%u, %u), %llu arena entries, %llu runs; arena %.3f ms, run kernels %.3f ms\n", tid_lo, t1,
-                (unsigned long long)D.arena_bases, (unsigned long long)total, D.arena_ms, D.runs_ms);
+        fprintf(stderr, "[covermhip] %s: targets [%u, %u), %llu arena entries, %llu runs; arena %.3f ms, run kernels %.3f ms\n",
+                std::is_same<View, dprc::Identity>::value ? "depth runs" : "depth class runs", tid_lo, t1, (unsigned long long)D.arena_bases, (unsigned long long)total,
+                D.arena_ms, D.runs_ms);
     return COV_OK;
+}
+
+cov_status cov_depth_runs_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    return depth_runs_compute(s, "cov_depth_runs_compute", dprc::Identity{}, tid_lo, tid_hi, tid_next, n_runs);
+}
+
+// The cut list of the quantised runs and the thresholds of the regions: one validator (csrc/depth_class_core.h), the first offending index named.
+static cov_status depth_cuts_check(cov_session *s, const char *who, const int32_t *cuts, uint32_t n) {
+    if (n && !cuts) return COV_ERR_INVALID_ARG;
+    u32 at = 0;
+    if (const char *what = dclc::validate(cuts, n, &at)) { s->err = std::string(who) + ": value " + std::to_string(at) + ": " + what; return COV_ERR_INVALID_ARG; }
+    return COV_OK;
+}
+
+cov_status cov_depth_class_runs_compute(cov_session *s, const int32_t *cuts, uint32_t n_cuts, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (const cov_status rc = depth_cuts_check(s, "cov_depth_class_runs_compute", cuts, n_cuts)) return rc;
+    return depth_runs_compute(s, "cov_depth_class_runs_compute", dclc::ClassView{dclc::make(cuts, n_cuts)}, tid_lo, tid_hi, tid_next, n_runs);
 }
 
 cov_status cov_depth_runs_fetch(cov_session *s, uint64_t *run_off, cov_depth_run *runs) {
@@ -3315,8 +3342,14 @@ cov_status cov_depth_regions_compute(cov_session *s, uint32_t tid_lo, uint32_t t
         HIPCHK(hipMemcpyAsync(D.reg_desc.p, D.h_reg_desc.data(), (size_t)n * sizeof(drgc::Desc), hipMemcpyHostToDevice, st));
         HIPCHK(hipMemcpyAsync(D.reg_piece_off.p, D.h_reg_piece_off.data(), ((size_t)n + 1) * 4, hipMemcpyHostToDevice, st));
         hipLaunchKernelGGL(covdb::k_bins_init, dim3((n + 255u) / 256u), dim3(256), 0, st, D.regs.p, (u64)n);
-        hipLaunchKernelGGL(covrg::k_depth_regions, dim3((u32)((pieces + 3ull) / 4ull)), dim3(256), 0, st, (const int32_t *)D.arena.p, (const drgc::Desc *)D.reg_desc.p,
-                           (const u32 *)D.reg_piece_off.p, n, (u32)pieces, D.regs.p);
+        if (D.thr.n) {      // the threshold variant: the same launch, the counts beside the results (zeroed by a fill, which is no launch)
+            HIPCHK(D.reg_counts.reserve((size_t)n * D.thr.n, st));
+            HIPCHK(hipMemsetAsync(D.reg_counts.p, 0, (size_t)n * D.thr.n * 4, st));
+            hipLaunchKernelGGL(covrg::k_depth_regions_thr, dim3((u32)((pieces + 3ull) / 4ull)), dim3(256), 0, st, (const int32_t *)D.arena.p, (const drgc::Desc *)D.reg_desc.p,
+                               (const u32 *)D.reg_piece_off.p, n, (u32)pieces, D.regs.p, D.thr, D.reg_counts.p);
+        } else
+            hipLaunchKernelGGL(covrg::k_depth_regions, dim3((u32)((pieces + 3ull) / 4ull)), dim3(256), 0, st, (const int32_t *)D.arena.p, (const drgc::Desc *)D.reg_desc.p,
+                               (const u32 *)D.reg_piece_off.p, n, (u32)pieces, D.regs.p);
         launches += 2;
     }
     HIPCHK(hipGetLastError());
@@ -3327,7 +3360,7 @@ cov_status cov_depth_regions_compute(cov_session *s, uint32_t tid_lo, uint32_t t
     (void)hipEventElapsedTime(&ms_regs, ev[1], D.ev_mid);
     s->ev_fresh = -1;
     D.g_arena_ms = ms_arena; D.regs_ms = ms_regs; D.g_launches = launches;
-    D.g_lo = tid_lo; D.g_next = t1; D.g_first = r0; D.n_regs = n; D.n_pieces = pieces; D.g_arena_bases = 4ull * ck.words; D.regs_valid = true;
+    D.g_lo = tid_lo; D.g_next = t1; D.g_first = r0; D.n_regs = n; D.n_pieces = pieces; D.g_arena_bases = 4ull * ck.words; D.g_thr = D.thr.n; D.regs_valid = true;
     *tid_next = t1; *n_regions = n;
     if (cov_timing_on())
         fprintf(stderr, "[covermhip] depth regions: targets [%u, %u), %llu arena entries, %u regions in %llu pieces; arena %.3f ms, region kernels %.3f ms\n", tid_lo, t1,
@@ -3349,6 +3382,35 @@ cov_status cov_depth_regions_fetch(cov_session *s, uint64_t *input_index, cov_de
         HIPCHK(hipStreamSynchronize(s->stream));
     }
     for (u64 i = 0; i < D.n_regs; i++) input_index[i] = D.h_reg_input[D.g_first + i];
+    return COV_OK;
+}
+
+cov_status cov_depth_thresholds_set(cov_session *s, const int32_t *thr, uint32_t n) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    cov_session::DepthRuns &D = s->dr;
+    if (n) {
+        if (const cov_status rc = depth_cuts_check(s, "cov_depth_thresholds_set", thr, n)) return rc;      // (the thresholds set before stay)
+        D.thr = dclc::make(thr, n);
+    } else
+        D.thr = dclc::Cuts{};
+    if (D.regs_valid) { D.regs_valid = false; D.taker[cov_session::DepthRuns::REGIONS] = 0; }      // the chunk computed under the thresholds before is not theirs
+    return COV_OK;
+}
+
+cov_status cov_depth_regions_counts_fetch(cov_session *s, uint32_t *counts) {
+    if (!s) return COV_ERR_INVALID_ARG;
+    if (s->ing.active) { s->err = "cov_depth_regions_counts_fetch: a device ingest is still open (cov_ingest_end first)"; return COV_ERR_STATE; }
+    if (s->spill.active) { s->err = "cov_depth_regions_counts_fetch: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    if (!s->dr.thr.n) { s->err = "cov_depth_regions_counts_fetch: no thresholds set (cov_depth_thresholds_set)"; return COV_ERR_STATE; }
+    if (s->finished && !s->dr.regs_valid && s->dr.taker[cov_session::DepthRuns::REGIONS]) { s->err = s->dr.lost(cov_session::DepthRuns::REGIONS); return COV_ERR_STATE; }
+    if (!s->finished || !s->dr.regs_valid) { s->err = "cov_depth_regions_counts_fetch: no chunk computed since the last finish (cov_depth_regions_compute)"; return COV_ERR_STATE; }
+    cov_session::DepthRuns &D = s->dr;      // (a valid chunk was computed under the thresholds now set: setting them drops it)
+    if (D.n_regs && !counts) return COV_ERR_INVALID_ARG;
+    HIPCHK(hipSetDevice(s->cfg.device));
+    if (D.n_regs) {
+        HIPCHK(hipMemcpyAsync(counts, D.reg_counts.p, (size_t)D.n_regs * D.g_thr * 4, hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
     return COV_OK;
 }
 

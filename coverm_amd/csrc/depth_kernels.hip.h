@@ -10,13 +10,18 @@
 //                     bases on, not the one in front; the extra entry lies in the cache line the lane has just read); the functor counts
 //                     the word's run starts, the sink writes them at the word's exclusive prefix.  The output order is the scan's: target
 //                     order, then position order; no atomic takes part in it.
+//   ClassWordCount / ClassWordEmit      the same pair behind a view that maps every entry to its depth class (csrc/depth_class_core.h):
+//                     cov_depth_class_runs_compute.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "scan_ops.hip.h"
 
 #define DPRC_FN __host__ __device__ __forceinline__
-#include "depth_runs_core.h"
+#define DBNC_FN __host__ __device__ __forceinline__      // (depth_class_core.h brings the bins' and regions' cores with it)
+#define DRGC_FN __host__ __device__ __forceinline__
+#define DCLC_FN __host__ __device__ __forceinline__
+#include "depth_class_core.h"
 
 namespace covdr {
 
@@ -45,27 +50,36 @@ __device__ __forceinline__ Word load_word(const int32_t *__restrict__ arena, con
     return x;
 }
 
-struct WordCount {
+// The functors take what they compare and emit through a VIEW of the arena's entries (depth_runs_core.h): dprc::Identity for the runs of equal
+// depth, dclc::ClassView (the cut list by value: scalar registers) for the runs of equal depth class.  The view is an (empty, for Identity)
+// base, so the plain pair's kernel arguments are the pointers alone.
+template <class View> struct WordCountT : View {
     const int32_t *arena; const u32 *mask;
     __device__ u32 operator()(u32 w) const {
+        const View &q = *this;
         const Word x = load_word(arena, mask, w);
-        return dprc::popc32(dprc::run_starts(x.d.x, x.d.y, x.d.z, x.d.w, x.prev, x.ts));
+        return dprc::popc32(dprc::run_starts(q(x.d.x), q(x.d.y), q(x.d.z), q(x.d.w), q(x.prev), x.ts));      // (a view keeps PAD)
     }
 };
-struct WordEmit {      // dprc::emit_word over registers
+template <class View> struct WordEmitT : View {      // dprc::emit_word over registers
     const int32_t *arena; const u32 *mask, *rank, *woff; dprc::Run *runs; u32 *run_off;
     __device__ void operator()(u32 w, u32 p) const {
+        const View &q = *this;
         const Word x = load_word(arena, mask, w);
-        const u32 m = dprc::run_starts(x.d.x, x.d.y, x.d.z, x.d.w, x.prev, x.ts);
+        const int32_t d[4] = {q(x.d.x), q(x.d.y), q(x.d.z), q(x.d.w)};
+        const u32 m = dprc::run_starts(d[0], d[1], d[2], d[3], q(x.prev), x.ts);
         if (!x.ts && !m) return;
         const u32 k = dprc::target_of(mask, rank, w);
         if (x.ts) run_off[k] = p;
         const u32 base = 4u * (w - woff[k]);
-        const int32_t d[4] = {x.d.x, x.d.y, x.d.z, x.d.w};
 #pragma unroll
         for (u32 j = 0; j < 4u; j++)
             if (m >> j & 1u) { dprc::Run r; r.start = base + j; r.depth = d[j]; runs[p++] = r; }
     }
 };
+typedef WordCountT<dprc::Identity> WordCount;
+typedef WordEmitT<dprc::Identity> WordEmit;
+typedef WordCountT<dclc::ClassView> ClassWordCount;
+typedef WordEmitT<dclc::ClassView> ClassWordEmit;
 
 }  // namespace covdr

@@ -9,6 +9,8 @@
 //                 word's bit in the start mask (one bit per word) is set.
 //   plan_chunk    the targets one chunk takes under a budget of arena entries: at least one, then as many as still fit.
 //   run_starts    the bases of one word that start a run: not PAD, and the first of its target or different from the base in front.
+//   view          what the run arithmetic sees of an arena entry: the entry itself (Identity: runs of equal depth), or a function of it that
+//                 keeps PAD (dclc::ClassView of csrc/depth_class_core.h: runs of equal depth class).  The start mask, rank and order are the same.
 //   target_of     the chunk's target a word belongs to, from the start mask and the exclusive prefix of its popcounts (`rank`, one per
 //                 32 words): the number of target starts at or in front of the word, less one.  No search over the offsets.
 #pragma once
@@ -56,6 +58,8 @@ DPRC_FN u32 run_starts(int32_t d0, int32_t d1, int32_t d2, int32_t d3, int32_t p
            (u32)(d3 != PAD && d3 != d2) << 3;
 }
 
+struct Identity { DPRC_FN int32_t operator()(int32_t d) const { return d; } };
+
 DPRC_FN bool word_starts_target(const u32 *mask, u32 w) { return (mask[w >> 5] >> (w & 31u)) & 1u; }
 
 DPRC_FN u32 target_of(const u32 *mask, const u32 *rank, u32 w) {
@@ -63,15 +67,17 @@ DPRC_FN u32 target_of(const u32 *mask, const u32 *rank, u32 w) {
 }
 
 // What the scan's functor returns for word w ...
-DPRC_FN u32 count_word(const int32_t *arena, const u32 *mask, u32 w) {
+template <class View = Identity>
+DPRC_FN u32 count_word(const int32_t *arena, const u32 *mask, u32 w, const View &q = View()) {
     const int32_t *d = arena + 4ull * w;
-    return popc32(run_starts(d[0], d[1], d[2], d[3], w ? d[-1] : PAD, word_starts_target(mask, w)));
+    return popc32(run_starts(q(d[0]), q(d[1]), q(d[2]), q(d[3]), w ? q(d[-1]) : PAD, word_starts_target(mask, w)));
 }
 // ... and what its sink does with the word's exclusive prefix p: the word's runs go to runs[p ..], a target's first word leaves p in run_off.
-DPRC_FN void emit_word(const int32_t *arena, const u32 *mask, const u32 *rank, const u32 *woff, u32 w, u32 p, Run *runs, u32 *run_off) {
-    const int32_t *d = arena + 4ull * w;
+template <class View = Identity>
+DPRC_FN void emit_word(const int32_t *arena, const u32 *mask, const u32 *rank, const u32 *woff, u32 w, u32 p, Run *runs, u32 *run_off, const View &q = View()) {
+    const int32_t d[4] = {q(arena[4ull * w]), q(arena[4ull * w + 1ull]), q(arena[4ull * w + 2ull]), q(arena[4ull * w + 3ull])};
     const bool ts = word_starts_target(mask, w);
-    const u32 m = run_starts(d[0], d[1], d[2], d[3], w ? d[-1] : PAD, ts);
+    const u32 m = run_starts(d[0], d[1], d[2], d[3], w ? q(arena[4ull * w - 1ull]) : PAD, ts);
     if (!ts && !m) return;
     const u32 k = target_of(mask, rank, w);
     if (ts) run_off[k] = p;
@@ -95,8 +101,9 @@ DPRC_FN void mark_pads(int32_t *arena, const u32 *woff, const u32 *tlen, u32 k) 
 
 // The whole chunk serially, in the order of the device's launches: marks, rank scan, count, exclusive scan, emit.  arena: 4 * woff[n]
 // entries holding the targets' depths at 4 * woff[k]; mask / rank: (words + 31) / 32 entries; run_off: n + 1; runs: as many as counted
-// (runs == nullptr: only the count).  Returns the number of runs.
-DPRC_FN u64 runs_cpu(int32_t *arena, const u32 *tlen, u32 n, const u32 *woff, u32 *mask, u32 *rank, Run *runs, u32 *run_off) {
+// (runs == nullptr: only the count).  Returns the number of runs; a run's `depth` is the view's value.
+template <class View = Identity>
+DPRC_FN u64 runs_cpu(int32_t *arena, const u32 *tlen, u32 n, const u32 *woff, u32 *mask, u32 *rank, Run *runs, u32 *run_off, const View &q = View()) {
     const u32 words = woff[n], mw = (words + 31u) >> 5;
     for (u32 i = 0; i < mw; i++) mask[i] = 0u;
     for (u32 k = 0; k < n; k++) { mask[woff[k] >> 5] |= 1u << (woff[k] & 31u); mark_pads(arena, woff, tlen, k); }
@@ -104,8 +111,8 @@ DPRC_FN u64 runs_cpu(int32_t *arena, const u32 *tlen, u32 n, const u32 *woff, u3
     for (u32 i = 0; i < mw; i++) { rank[i] = r; r += popc32(mask[i]); }
     u64 total = 0;
     for (u32 w = 0; w < words; w++) {
-        const u32 c = count_word(arena, mask, w);
-        if (runs) emit_word(arena, mask, rank, woff, w, (u32)total, runs, run_off);
+        const u32 c = count_word(arena, mask, w, q);
+        if (runs) emit_word(arena, mask, rank, woff, w, (u32)total, runs, run_off, q);
         total += c;
     }
     if (runs) run_off[n] = (u32)total;

@@ -879,6 +879,10 @@ int run_depth(int argc, char **argv) {
     int bin_value = COVH_BIN_MEAN;
     bool have_bin_value = false;
     std::string regions_path;      // --regions: one line per region of a BED file (covh_depth_regions_write)
+    std::string quantize, thresholds;      // --quantize: one line per stretch of one depth class; --thresholds: per region or window, the bases at or above each
+    int32_t cuts[COV_DEPTH_MAX_CUTS] = {0}, thr[COV_DEPTH_MAX_CUTS] = {0};
+    uint32_t n_cuts = 0, n_thr = 0;
+    int open_end = 0;
     auto collect = [&](int &i, std::vector<std::string> &dst) { while (i + 1 < argc && (argv[i + 1][0] != '-' || !argv[i + 1][1])) dst.push_back(argv[++i]); };
     static const char *const REFUSED[] = {"-m", "--methods", "--gff", "--gff-feature-type", "--devices", "--contig-end-exclusion", "--min-covered-fraction", "--trim-min", "--trim-max",
                                           "--output-format", "-s", "--separator", "--single-genome", "--genome-definition", "-f", "--genome-fasta-files", "-d",
@@ -901,6 +905,13 @@ int run_depth(int argc, char **argv) {
             bin_size = (uint32_t)parse_uint(k, val(), 0x7fffffffull);
             if (bin_size == 0) die("invalid value '0' for '" + k + "'");
         } else if (k == "--regions") regions_path = val();
+        else if (k == "--quantize") {
+            quantize = val();
+            if (covh_depth_quantize_parse(quantize.c_str(), cuts, &n_cuts, &open_end) != COV_OK) die("invalid value for '--quantize': " + std::string(covh_last_error()));
+        } else if (k == "--thresholds") {
+            thresholds = val();
+            if (covh_depth_thresholds_parse(thresholds.c_str(), thr, &n_thr) != COV_OK) die("invalid value for '--thresholds': " + std::string(covh_last_error()));
+        }
         else if (k == "--bin-value") {
             const std::string v = val();
             static const char *const KINDS[] = {"mean", "sum", "min", "max", "covered"};      // covh_bin_value
@@ -919,6 +930,16 @@ int run_depth(int argc, char **argv) {
         else die("unknown argument " + k);
     }
     if (!regions_path.empty() && bin_size) die("the argument '--regions' cannot be used with '--bin-size': a line per region of the BED file, or a line per fixed window");
+    if (n_cuts) {
+        if (!regions_path.empty()) die("the argument '--quantize' cannot be used with '--regions': a line per stretch of one depth class, or a line per region of the BED file");
+        if (bin_size) die("the argument '--quantize' cannot be used with '--bin-size': a line per stretch of one depth class, or a line per fixed window");
+        if (have_bin_value) die("the argument '--quantize' cannot be used with '--bin-value': the track prints the class of a stretch, not a value of a window or region");
+        if (n_thr) die("the argument '--quantize' cannot be used with '--thresholds': the thresholds count the bases of a region or window (--regions, --bin-size)");
+        if (a.no_zeros) die("the argument '--quantize' cannot be used with '--no-zeros': leave the zero class out of the spec instead (--quantize 1:... prints no line for depth 0)");
+    }
+    if (n_thr && !bin_size && regions_path.empty())
+        die("the argument '--thresholds' needs '--regions' or '--bin-size': it counts, per region or window, the bases at or above each threshold");
+    if (n_thr && have_bin_value) die("the argument '--thresholds' cannot be used with '--bin-value': the counts are the value columns");
     if (have_bin_value && !bin_size && regions_path.empty())
         die("the argument '--bin-value' needs '--bin-size' or '--regions': it picks what is printed per bin or region (coverm-amd depth --bin-size N --bin-value ...)");
     if (a.bams.empty()) die("--bam-files is required (read mapping is out of scope for this engine)");
@@ -976,9 +997,34 @@ int run_depth(int argc, char **argv) {
         Sample S; S.path = b;
         ingest(R, s, S, std::max(1, a.threads), 0, 1);
         const double t_runs0 = now();
-        fprintf(out, "track type=bedGraph name=\"%s\"\n", S.stoit.c_str());
+        if (n_cuts) fprintf(out, "track name=\"%s\" description=\"depth classes %s\"\n", S.stoit.c_str(), quantize.c_str());      // (the label column is not numeric: no bedGraph)
+        else fprintf(out, "track type=bedGraph name=\"%s\"\n", S.stoit.c_str());
+        if (n_thr) {
+            fputs("#thresholds", out);
+            for (uint32_t j = 0; j < n_thr; j++) fprintf(out, "\t%d", thr[j]);
+            fputc('\n', out);
+        }
         fflush(out);
         const covh_header hdr = S.header();
+        if (n_cuts) {
+            uint64_t n_runs = 0;
+            if (covh_depth_class_runs_write(s, &hdr, cuts, n_cuts, open_end, std::max(1, a.threads), fileno(out), &n_runs) != COV_OK) die(covh_last_error());
+            if (timing_on())
+                fprintf(stderr, "[coverm-amd] sample %s: open %.3fs, ingest (decode+push) %.3fs, finish %.3fs, %llu records; depth classes %s: %llu runs computed, fetched and written in %.3fs\n",
+                        S.stoit.c_str(), S.t_open, S.t_ingest, S.t_finish, (unsigned long long)S.n_records, quantize.c_str(), (unsigned long long)n_runs, now() - t_runs0);
+            continue;
+        }
+        if (n_thr) {
+            uint64_t n_lines = 0;
+            const int rc = bed ? covh_depth_regions_counts_write(s, &hdr, bed, thr, n_thr, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_lines)
+                               : covh_depth_bins_counts_write(s, &hdr, bin_size, thr, n_thr, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_lines);
+            if (rc != COV_OK) die(covh_last_error());
+            if (timing_on())
+                fprintf(stderr, "[coverm-amd] sample %s: open %.3fs, ingest (decode+push) %.3fs, finish %.3fs, %llu records; depth thresholds %s: %llu %s computed, fetched and written in %.3fs\n",
+                        S.stoit.c_str(), S.t_open, S.t_ingest, S.t_finish, (unsigned long long)S.n_records, thresholds.c_str(), (unsigned long long)n_lines, bed ? "regions" : "windows",
+                        now() - t_runs0);
+            continue;
+        }
         if (bed) {
             uint64_t n_regions = 0;
             if (covh_depth_regions_write(s, &hdr, bed, bin_value, a.no_zeros ? 1 : 0, std::max(1, a.threads), fileno(out), &n_regions) != COV_OK) die(covh_last_error());
@@ -1027,7 +1073,7 @@ int run_cli(int argc, char **argv) {
                         "       genome mode takes its genomes from -s, --single-genome, --genome-definition, -f <fasta>..., -d <dir> [-x fna]\n"
                         "       (a directory's files in bytewise name order) or --genome-fasta-list <file>; --use-full-contig-names\n"
                         "       coverm-amd filter -b <bam>... -o <bam>... [thresholds] [--inverse]\n"
-                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--bin-size N | --regions BED [--bin-value V]] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
+                        "       coverm-amd depth -b <bam|sam|->... [-o FILE] [--no-zeros] [--bin-size N | --regions BED [--bin-value V | --thresholds T,..]] [--quantize SPEC] [--unsorted] [--device N] [-t N] [--no-stream] [flag and read filters]\n"
                         "       the per-base depth of every reference, under contig's filters, as a bedGraph: one `track` line per sample, then\n"
                         "       name<TAB>start<TAB>end<TAB>depth (0-based, half open) per stretch of equal depth; --no-zeros drops the stretches of depth 0\n"
                         "       --bin-size N [--bin-value mean|sum|min|max|covered]: one line per window of N bases instead (the last window of a reference\n"
@@ -1035,7 +1081,12 @@ int run_cli(int argc, char **argv) {
                         "       others as integers; --no-zeros then drops the windows without a covered base\n"
                         "       --regions BED [--bin-value ...]: one line per region of a BED file instead (chrom<TAB>start<TAB>end[<TAB>name], 0-based, half\n"
                         "       open; regions may overlap and come in any order), in the file's order, reduced on the device: chrom, start, end, the name when\n"
-                        "       the line had one, then the value; a reference the sample's header does not have, or an end behind its length, is an error\n");
+                        "       the line had one, then the value; a reference the sample's header does not have, or an end behind its length, is an error\n"
+                        "       --thresholds T1,T2,.. (with --regions or --bin-size; 1 to 16 ascending depths): per region or window, the number of its bases\n"
+                        "       with depth >= each threshold instead of a value, counted on the device; a line `#thresholds<TAB>T1<TAB>T2..` follows the track line\n"
+                        "       --quantize C0:C1:..[:] (1 to 16 ascending cuts): one line per stretch of one depth CLASS instead, name<TAB>start<TAB>end<TAB>lo:hi for\n"
+                        "       the classes [C0,C1), [C1,C2) .. and, when the spec ends in ':', lo:inf for [Clast,inf); an empty first field means 0; depths below C0\n"
+                        "       (and at or above the last cut of a spec without the final ':') print no line; merged on the device, e.g. --quantize 0:1:5:150:\n");
         return 2;
     }
     a.mode = argv[1];

@@ -4,6 +4,7 @@
 #include "../../include/coverm_host.h"
 #include "knobs.h"
 #include "sep_entry_core.h"
+#include "depth_class_core.h"
 
 #include <algorithm>
 #include <cerrno>
@@ -1916,20 +1917,19 @@ int covh_depth_regions_format(const covh_bed *b, const cov_depth_bin *results, i
     return COV_OK;
 }
 
-int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_bed *b, int value, int no_zeros, int threads, int out_fd, uint64_t *n_regions_out) {
-    if (!s || !h || !b) { g_err = "covh_depth_regions_write: no session, header or regions"; return COV_ERR_INVALID_ARG; }
-    if (n_regions_out) *n_regions_out = 0;
-    const uint64_t n = b->lines.size();
-    std::vector<cov_depth_region> regions(n);
-    int rc = covh_bed_resolve(b, h, regions.data());
-    if (rc != COV_OK) return rc;
-    if (n == 0) return COV_OK;
-    rc = (int)cov_depth_regions_set(s, regions.data(), n);
+namespace {
+
+// The chunks of a finished session that hold a region: cov_depth_regions_set, then compute / fetch chunk by chunk through page-locked
+// memory, SKIPPING targets without a region, scattered by input_index into results[n] (and, with thresholds set on the session, their
+// counts into counts[n x n_thr]).
+int collect_regions(cov_session *s, const covh_header *h, const char *who, const cov_depth_region *regions, uint64_t n, cov_depth_bin *results, uint32_t *counts,
+                    uint32_t n_thr) {
+    int rc = (int)cov_depth_regions_set(s, regions, n);
     if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
     std::vector<uint8_t> has(h->n_targets, 0);
-    for (const cov_depth_region &r : regions) has[r.tid] = 1;
-    std::vector<cov_depth_bin> results(n);      // the sample's results in the file's order, 24 B per region
-    void *pinned = nullptr; size_t cap = 0;     // page-locked, grown to the largest chunk: the results, then their input indices
+    for (uint64_t i = 0; i < n; i++) has[regions[i].tid] = 1;
+    const size_t per = sizeof(cov_depth_bin) + sizeof(uint64_t) + (counts ? (size_t)n_thr * 4 : 0);
+    void *pinned = nullptr; size_t cap = 0;     // page-locked, grown to the largest chunk: the results, their input indices, their counts
     struct Free { void *&p; ~Free() { if (p) cov_host_free(p); } } free_pinned{pinned};
     uint64_t total = 0;
     uint32_t lo = 0;
@@ -1941,21 +1941,291 @@ int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_be
         if (m > cap) {
             if (pinned) { cov_host_free(pinned); pinned = nullptr; }
             cap = (size_t)m;
-            pinned = cov_host_alloc(cap * (sizeof(cov_depth_bin) + sizeof(uint64_t)));
-            if (!pinned) { g_err = "covh_depth_regions_write: no page-locked memory for a chunk's results"; return COV_ERR_HIP; }
+            pinned = cov_host_alloc(cap * per);
+            if (!pinned) { g_err = std::string(who) + ": no page-locked memory for a chunk's results"; return COV_ERR_HIP; }
         }
         cov_depth_bin *res = static_cast<cov_depth_bin *>(pinned);
         uint64_t *idx = reinterpret_cast<uint64_t *>(res + cap);
+        uint32_t *cnt = reinterpret_cast<uint32_t *>(idx + cap);
         rc = (int)cov_depth_regions_fetch(s, idx, res);
+        if (rc == COV_OK && counts) rc = (int)cov_depth_regions_counts_fetch(s, cnt);
         if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
         for (uint64_t i = 0; i < m; i++) results[idx[i]] = res[i];
+        if (counts)
+            for (uint64_t i = 0; i < m; i++) memcpy(counts + idx[i] * n_thr, cnt + i * n_thr, (size_t)n_thr * 4);
         total += m;
         lo = next;
         while (lo < h->n_targets && !has[lo]) lo++;
     }
-    if (total != n) { g_err = "covh_depth_regions_write: the chunks returned " + std::to_string(total) + " of " + std::to_string(n) + " regions"; return COV_ERR_STATE; }
+    if (total != n) { g_err = std::string(who) + ": the chunks returned " + std::to_string(total) + " of " + std::to_string(n) + " regions"; return COV_ERR_STATE; }
+    return COV_OK;
+}
+
+}  // namespace
+
+int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_bed *b, int value, int no_zeros, int threads, int out_fd, uint64_t *n_regions_out) {
+    if (!s || !h || !b) { g_err = "covh_depth_regions_write: no session, header or regions"; return COV_ERR_INVALID_ARG; }
+    if (n_regions_out) *n_regions_out = 0;
+    const uint64_t n = b->lines.size();
+    std::vector<cov_depth_region> regions(n);
+    int rc = covh_bed_resolve(b, h, regions.data());
+    if (rc != COV_OK) return rc;
+    if (n == 0) return COV_OK;
+    std::vector<cov_depth_bin> results(n);      // the sample's results in the file's order, 24 B per region
+    rc = collect_regions(s, h, "covh_depth_regions_write", regions.data(), n, results.data(), nullptr, 0);
+    if (rc != COV_OK) return rc;
     rc = covh_depth_regions_format(b, results.data(), value, no_zeros, threads, out_fd);
     if (rc != COV_OK) return rc;
-    if (n_regions_out) *n_regions_out = total;
+    if (n_regions_out) *n_regions_out = n;
+    return COV_OK;
+}
+
+// ---------------------------------------------------------------------------------------------- depth classes (`coverm-amd depth --quantize`, `--thresholds`)
+namespace {
+
+// decimal fields separated by `sep` into v[0 .. n); an empty field is -1
+bool class_fields(const char *text, char sep, std::vector<int64_t> &v, std::string &why) {
+    v.clear();
+    const std::string_view t(text);
+    for (size_t at = 0;;) {
+        const size_t e = t.find(sep, at);
+        const std::string_view f = t.substr(at, e == std::string_view::npos ? std::string_view::npos : e - at);
+        uint32_t x = 0;
+        if (f.empty()) v.push_back(-1);
+        else if (bed_number(f, x)) v.push_back(x);
+        else { why = "'" + std::string(f) + "' is not a decimal integer of at most 2147483647"; return false; }
+        if (v.size() > 64) { why = "more than 16 values"; return false; }
+        if (e == std::string_view::npos) return true;
+        at = e + 1;
+    }
+}
+
+int class_list(const char *who, const char *text, const std::vector<int64_t> &v, int32_t *out, uint32_t *n_out) {
+    std::vector<int32_t> c(v.begin(), v.end());
+    uint32_t at = 0;
+    if (const char *what = dclc::validate(c.data(), (uint32_t)c.size(), &at)) { g_err = std::string(who) + ": '" + text + "': value " + std::to_string(at) + ": " + what; return COV_ERR_INVALID_ARG; }
+    for (size_t i = 0; i < c.size(); i++) out[i] = c[i];
+    *n_out = (uint32_t)c.size();
+    return COV_OK;
+}
+
+// The label of class c under (cuts, open_end): empty when the class is not printed.
+void class_labels(const int32_t *cuts, uint32_t n, bool open_end, std::vector<std::string> &lab) {
+    lab.assign((size_t)n + 1, std::string());
+    for (uint32_t c = 1; c < n; c++) lab[c] = std::to_string(cuts[c - 1]) + ":" + std::to_string(cuts[c]);
+    if (open_end) lab[n] = std::to_string(cuts[n - 1]) + ":inf";
+}
+
+// n items as text on up to `threads` threads in ordered pieces of 2^17, written in their order: the same text for every thread count.
+template <class Piece>
+int write_in_pieces(const char *who, uint64_t n, int threads, int out_fd, Piece piece_text) {
+    constexpr uint64_t PIECE = 1ull << 17;
+    const unsigned T = (unsigned)std::max(1, std::min(threads, 64));
+    std::vector<std::string> text(T);
+    for (uint64_t base = 0; base < n; base += PIECE * T) {
+        const unsigned np = (unsigned)std::min<uint64_t>(T, (n - base + PIECE - 1) / PIECE);
+        auto piece = [&](unsigned i) { text[i].clear(); piece_text(base + i * PIECE, std::min(n, base + (i + 1) * PIECE), text[i]); };
+        std::vector<std::thread> th;
+        for (unsigned i = 1; i < np; i++) th.emplace_back(piece, i);
+        piece(0);
+        for (auto &t : th) t.join();
+        for (unsigned i = 0; i < np; i++)
+            if (!write_all(out_fd, text[i].data(), text[i].size())) { g_err = std::string(who) + ": write failed"; return COV_ERR_INVALID_ARG; }
+    }
+    return COV_OK;
+}
+
+struct PutNumber {
+    std::string &out; char num[24];
+    void operator()(uint64_t v) { const auto r = std::to_chars(num, num + sizeof num, v); out.append(num, (size_t)(r.ptr - num)); }
+};
+
+// The thresholds of a session while a _write function runs: set, and cleared again behind it.
+struct SessionThresholds {
+    cov_session *s; int rc;
+    SessionThresholds(cov_session *s_, const int32_t *thr, uint32_t n) : s(s_), rc((int)cov_depth_thresholds_set(s_, thr, n)) { if (rc != COV_OK) g_err = cov_last_error(s); }
+    ~SessionThresholds() { (void)cov_depth_thresholds_set(s, nullptr, 0); }
+};
+
+}  // namespace
+
+int covh_depth_quantize_parse(const char *spec, int32_t *cuts, uint32_t *n_cuts, int *open_end) {
+    if (!spec || !cuts || !n_cuts || !open_end) { g_err = "covh_depth_quantize_parse: no spec"; return COV_ERR_INVALID_ARG; }
+    std::vector<int64_t> v;
+    std::string why;
+    const std::string at = std::string("covh_depth_quantize_parse: '") + spec + "': ";
+    if (!class_fields(spec, ':', v, why)) { g_err = at + why; return COV_ERR_INVALID_ARG; }
+    if (v.size() < 2) { g_err = at + "no class: at least two cuts, or one and an open end (0:1:5: gives [0,1), [1,5) and [5,inf))"; return COV_ERR_INVALID_ARG; }
+    const bool open = v.back() < 0;
+    if (open) v.pop_back();
+    if (!v.empty() && v[0] < 0) v[0] = 0;      // an empty first field means 0
+    for (size_t i = 0; i < v.size(); i++)
+        if (v[i] < 0) { g_err = at + "value " + std::to_string(i) + ": an empty field (only the first and the last may be empty)"; return COV_ERR_INVALID_ARG; }
+    if (v.empty() || (v.size() < 2 && !open)) { g_err = at + "no class: at least two cuts, or one and an open end"; return COV_ERR_INVALID_ARG; }
+    const int rc = class_list("covh_depth_quantize_parse", spec, v, cuts, n_cuts);
+    if (rc == COV_OK) *open_end = open ? 1 : 0;
+    return rc;
+}
+
+int covh_depth_thresholds_parse(const char *list, int32_t *thr, uint32_t *n_thr) {
+    if (!list || !thr || !n_thr) { g_err = "covh_depth_thresholds_parse: no list"; return COV_ERR_INVALID_ARG; }
+    std::vector<int64_t> v;
+    std::string why;
+    const std::string at = std::string("covh_depth_thresholds_parse: '") + list + "': ";
+    if (!class_fields(list, ',', v, why)) { g_err = at + why; return COV_ERR_INVALID_ARG; }
+    for (size_t i = 0; i < v.size(); i++)
+        if (v[i] < 0) { g_err = at + "value " + std::to_string(i) + ": an empty field"; return COV_ERR_INVALID_ARG; }
+    return class_list("covh_depth_thresholds_parse", list, v, thr, n_thr);
+}
+
+int covh_depth_class_runs_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, const uint64_t *run_off, const cov_depth_run *runs, const int32_t *cuts,
+                                 uint32_t n_cuts, int open_end, int threads, int out_fd) {
+    if (!h || !run_off || (uint64_t)tid_lo + n_targets > h->n_targets) { g_err = "covh_depth_class_runs_format: targets outside the header"; return COV_ERR_INVALID_ARG; }
+    uint32_t bad = 0;
+    if (!cuts || dclc::validate(cuts, n_cuts, &bad)) { g_err = "covh_depth_class_runs_format: a bad cut list"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = run_off[n_targets];
+    if (n && !runs) { g_err = "covh_depth_class_runs_format: no runs"; return COV_ERR_INVALID_ARG; }
+    std::vector<std::string> lab;
+    class_labels(cuts, n_cuts, open_end != 0, lab);
+    return write_in_pieces("covh_depth_class_runs_format", n, threads, out_fd, [&](uint64_t j0, uint64_t j1, std::string &out) {
+        uint32_t k = (uint32_t)(std::upper_bound(run_off, run_off + n_targets + 1, j0) - run_off) - 1u;      // last target whose offset is <= j0
+        PutNumber put{out, {}};
+        for (uint64_t j = j0; j < j1; j++) {
+            while (j >= run_off[k + 1]) k++;
+            const cov_depth_run r = runs[j];
+            if (r.depth < 0 || (uint32_t)r.depth > n_cuts || lab[(size_t)r.depth].empty()) continue;      // class 0, a closed spec's class n
+            const uint32_t t = tid_lo + k;
+            const uint64_t end = j + 1 < run_off[k + 1] ? runs[j + 1].start : h->target_len[t];      // the next run's start, printed or not
+            out.append(h->names + h->name_off[t], h->name_off[t + 1] - h->name_off[t]);
+            out.push_back('\t'); put(r.start); out.push_back('\t'); put(end); out.push_back('\t');
+            out.append(lab[(size_t)r.depth]);
+            out.push_back('\n');
+        }
+    });
+}
+
+int covh_depth_class_runs_write(cov_session *s, const covh_header *h, const int32_t *cuts, uint32_t n_cuts, int open_end, int threads, int out_fd, uint64_t *n_runs_out) {
+    if (!s || !h) { g_err = "covh_depth_class_runs_write: no session"; return COV_ERR_INVALID_ARG; }
+    uint64_t total = 0;
+    if (n_runs_out) *n_runs_out = 0;
+    cov_depth_run *runs = nullptr; size_t cap = 0;      // page-locked, grown to the largest chunk
+    struct Free { cov_depth_run *&p; ~Free() { if (p) cov_host_free(p); } } free_runs{runs};
+    std::vector<uint64_t> run_off;
+    for (uint32_t lo = 0; lo < h->n_targets;) {
+        uint32_t next = 0; uint64_t n = 0;
+        int rc = (int)cov_depth_class_runs_compute(s, cuts, n_cuts, lo, h->n_targets, &next, &n);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        if (n > cap) {
+            if (runs) { cov_host_free(runs); runs = nullptr; }
+            cap = (size_t)n;
+            runs = static_cast<cov_depth_run *>(cov_host_alloc(cap * sizeof(cov_depth_run)));
+            if (!runs) { g_err = "covh_depth_class_runs_write: no page-locked memory for a chunk's runs"; return COV_ERR_HIP; }
+        }
+        run_off.resize((size_t)(next - lo) + 1);
+        rc = (int)cov_depth_runs_fetch(s, run_off.data(), runs);
+        if (rc != COV_OK) { g_err = cov_last_error(s); return rc; }
+        rc = covh_depth_class_runs_format(h, lo, next - lo, run_off.data(), runs, cuts, n_cuts, open_end, threads, out_fd);
+        if (rc != COV_OK) return rc;
+        total += n; lo = next;
+    }
+    if (n_runs_out) *n_runs_out = total;
+    return COV_OK;
+}
+
+int covh_depth_regions_counts_format(const covh_bed *b, const cov_depth_bin *results, const uint32_t *counts, uint32_t n_thr, int no_zeros, int threads, int out_fd) {
+    if (!b) { g_err = "covh_depth_regions_counts_format: no regions"; return COV_ERR_INVALID_ARG; }
+    if (n_thr == 0 || n_thr > COV_DEPTH_MAX_CUTS) { g_err = "covh_depth_regions_counts_format: 1 .. 16 thresholds"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = b->lines.size();
+    if (n && (!counts || (no_zeros && !results))) { g_err = "covh_depth_regions_counts_format: no counts or no results"; return COV_ERR_INVALID_ARG; }
+    return write_in_pieces("covh_depth_regions_counts_format", n, threads, out_fd, [&](uint64_t j0, uint64_t j1, std::string &out) {
+        PutNumber put{out, {}};
+        for (uint64_t j = j0; j < j1; j++) {
+            const covh_bed::Line &l = b->lines[j];
+            if (no_zeros && results[j].max == 0) continue;
+            out.append(b->text, l.chrom_off, l.chrom_len);
+            out.push_back('\t'); put(l.start); out.push_back('\t'); put(l.end);
+            if (l.has_name) { out.push_back('\t'); out.append(b->text, l.name_off, l.name_len); }
+            for (uint32_t t = 0; t < n_thr; t++) { out.push_back('\t'); put(counts[j * n_thr + t]); }
+            out.push_back('\n');
+        }
+    });
+}
+
+int covh_depth_regions_counts_write(cov_session *s, const covh_header *h, const covh_bed *b, const int32_t *thr, uint32_t n_thr, int no_zeros, int threads, int out_fd,
+                                    uint64_t *n_regions_out) {
+    if (!s || !h || !b) { g_err = "covh_depth_regions_counts_write: no session, header or regions"; return COV_ERR_INVALID_ARG; }
+    if (n_regions_out) *n_regions_out = 0;
+    if (n_thr == 0) { g_err = "covh_depth_regions_counts_write: no thresholds"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = b->lines.size();
+    std::vector<cov_depth_region> regions(n);
+    int rc = covh_bed_resolve(b, h, regions.data());
+    if (rc != COV_OK) return rc;
+    SessionThresholds set(s, thr, n_thr);
+    if (set.rc != COV_OK) return set.rc;
+    if (n == 0) return COV_OK;
+    std::vector<cov_depth_bin> results(n);
+    std::vector<uint32_t> counts((size_t)n * n_thr);
+    rc = collect_regions(s, h, "covh_depth_regions_counts_write", regions.data(), n, results.data(), counts.data(), n_thr);
+    if (rc != COV_OK) return rc;
+    rc = covh_depth_regions_counts_format(b, results.data(), counts.data(), n_thr, no_zeros, threads, out_fd);
+    if (rc != COV_OK) return rc;
+    if (n_regions_out) *n_regions_out = n;
+    return COV_OK;
+}
+
+int covh_depth_bins_counts_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, uint32_t bin_size, const uint64_t *bin_off, const cov_depth_bin *bins,
+                                  const uint32_t *counts, uint32_t n_thr, int no_zeros, int threads, int out_fd) {
+    if (!h || !bin_off || (uint64_t)tid_lo + n_targets > h->n_targets) { g_err = "covh_depth_bins_counts_format: targets outside the header"; return COV_ERR_INVALID_ARG; }
+    if (bin_size == 0 || n_thr == 0 || n_thr > COV_DEPTH_MAX_CUTS) { g_err = "covh_depth_bins_counts_format: bin size 0, or not 1 .. 16 thresholds"; return COV_ERR_INVALID_ARG; }
+    const uint64_t n = bin_off[n_targets];
+    if (n && (!counts || (no_zeros && !bins))) { g_err = "covh_depth_bins_counts_format: no counts or no bins"; return COV_ERR_INVALID_ARG; }
+    return write_in_pieces("covh_depth_bins_counts_format", n, threads, out_fd, [&](uint64_t j0, uint64_t j1, std::string &out) {
+        uint32_t k = (uint32_t)(std::upper_bound(bin_off, bin_off + n_targets + 1, j0) - bin_off) - 1u;      // last target whose offset is <= j0
+        PutNumber put{out, {}};
+        for (uint64_t j = j0; j < j1; j++) {
+            while (j >= bin_off[k + 1]) k++;
+            if (no_zeros && bins[j].max == 0) continue;
+            const uint32_t t = tid_lo + k;
+            const uint64_t start = (j - bin_off[k]) * bin_size, end = std::min<uint64_t>(start + bin_size, h->target_len[t]);
+            out.append(h->names + h->name_off[t], h->name_off[t + 1] - h->name_off[t]);
+            out.push_back('\t'); put(start); out.push_back('\t'); put(end);
+            for (uint32_t c = 0; c < n_thr; c++) { out.push_back('\t'); put(counts[j * n_thr + c]); }
+            out.push_back('\n');
+        }
+    });
+}
+
+int covh_depth_bins_counts_write(cov_session *s, const covh_header *h, uint32_t bin_size, const int32_t *thr, uint32_t n_thr, int no_zeros, int threads, int out_fd,
+                                 uint64_t *n_bins_out) {
+    if (!s || !h) { g_err = "covh_depth_bins_counts_write: no session"; return COV_ERR_INVALID_ARG; }
+    if (n_bins_out) *n_bins_out = 0;
+    if (bin_size == 0 || bin_size > 0x7fffffffu || n_thr == 0) { g_err = "covh_depth_bins_counts_write: the bin size is 1 .. 2^31 - 1 bases, with at least one threshold"; return COV_ERR_INVALID_ARG; }
+    // the windows of every reference, tiled into regions in target order, then position order: result i is window i
+    std::vector<uint64_t> bin_off((size_t)h->n_targets + 1);
+    uint64_t n = 0;
+    for (uint32_t t = 0; t < h->n_targets; t++) { bin_off[t] = n; n += h->target_len[t] ? (h->target_len[t] - 1) / bin_size + 1 : 0; }
+    bin_off[h->n_targets] = n;
+    if (n >= (1ull << 32)) {      // refused in cov_depth_regions_set's words (which reads no region before it refuses)
+        const cov_depth_region none{};
+        const int rc = (int)cov_depth_regions_set(s, &none, n);
+        g_err = cov_last_error(s);
+        return rc != COV_OK ? rc : COV_ERR_INVALID_ARG;
+    }
+    SessionThresholds set(s, thr, n_thr);
+    if (set.rc != COV_OK) return set.rc;
+    if (n == 0) return COV_OK;
+    std::vector<cov_depth_region> regions((size_t)n);
+    for (uint32_t t = 0; t < h->n_targets; t++)
+        for (uint64_t j = bin_off[t]; j < bin_off[t + 1]; j++) {
+            const uint64_t start = (j - bin_off[t]) * bin_size;
+            regions[j] = cov_depth_region{t, (uint32_t)start, (uint32_t)std::min<uint64_t>(start + bin_size, h->target_len[t]), 0u};
+        }
+    std::vector<cov_depth_bin> results((size_t)n);
+    std::vector<uint32_t> counts((size_t)n * n_thr);
+    int rc = collect_regions(s, h, "covh_depth_bins_counts_write", regions.data(), n, results.data(), counts.data(), n_thr);
+    if (rc != COV_OK) return rc;
+    rc = covh_depth_bins_counts_format(h, 0, h->n_targets, bin_size, bin_off.data(), results.data(), counts.data(), n_thr, no_zeros, threads, out_fd);
+    if (rc != COV_OK) return rc;
+    if (n_bins_out) *n_bins_out = n;
     return COV_OK;
 }

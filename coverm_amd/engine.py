@@ -178,7 +178,7 @@ class Session:
         self._check(self._lib.cov_copy_depth(self._h, tid, d.ctypes.data if d.size else None))
         return d
 
-    def depth_runs(self, tid_lo: int = 0, tid_hi: Optional[int] = None, chunks=None):
+    def depth_runs(self, tid_lo: int = 0, tid_hi: Optional[int] = None, chunks=None, _cuts=None):
         """cov_depth_runs_compute / cov_depth_runs_fetch over targets [tid_lo, tid_hi) (default: all), chunk by chunk: the per-base depth
         run-length encoded on the device.  Returns (run_off, start, depth): the runs of target tid_lo + k are entries
         run_off[k] .. run_off[k + 1] (uint64, tid_hi - tid_lo + 1 entries), start[j] the run's first base (uint32, 0-based, inside its
@@ -189,7 +189,11 @@ class Session:
         offs, parts, base = [np.zeros(1, dtype=np.uint64)], [], 0
         while lo < hi:
             nxt, n = C.c_uint32(0), C.c_uint64(0)
-            self._check(self._lib.cov_depth_runs_compute(self._h, C.c_uint32(lo), C.c_uint32(hi), C.byref(nxt), C.byref(n)))
+            if _cuts is None:
+                self._check(self._lib.cov_depth_runs_compute(self._h, C.c_uint32(lo), C.c_uint32(hi), C.byref(nxt), C.byref(n)))
+            else:      # (depth_class_runs: the same chunks, fetch and info)
+                self._check(self._lib.cov_depth_class_runs_compute(self._h, _cuts.ctypes.data if _cuts.size else None, C.c_uint32(_cuts.size), C.c_uint32(lo),
+                                                                   C.c_uint32(hi), C.byref(nxt), C.byref(n)))
             ro = np.zeros(nxt.value - lo + 1, dtype=np.uint64)
             runs = np.zeros(int(n.value), dtype=native.DEPTH_RUN_DTYPE)
             self._check(self._lib.cov_depth_runs_fetch(self._h, ro.ctypes.data, runs.ctypes.data if runs.size else None))
@@ -204,8 +208,23 @@ class Session:
         runs = np.concatenate(parts) if parts else np.zeros(0, dtype=native.DEPTH_RUN_DTYPE)
         return np.concatenate(offs), np.ascontiguousarray(runs["start"]), np.ascontiguousarray(runs["depth"])
 
+    @staticmethod
+    def _cut_list(values):
+        """A cut list as the int32 array the library validates (a value outside int32 cannot be one: refused here)."""
+        a = np.asarray(list(values), dtype=np.int64).reshape(-1)
+        if ((a < -2 ** 31) | (a > 2 ** 31 - 1)).any():
+            raise ValueError("a cut is outside the 32-bit range")
+        return np.ascontiguousarray(a.astype(np.int32))
+
+    def depth_class_runs(self, cuts, tid_lo: int = 0, tid_hi: Optional[int] = None, chunks=None):
+        """cov_depth_class_runs_compute / cov_depth_runs_fetch over targets [tid_lo, tid_hi) (default: all), chunk by chunk: the per-base
+        depth classified against `cuts` (1 .. 16 ascending values in 0 .. 2^31 - 1; the class of a depth d is the number of cuts <= d) and
+        run-length encoded by class on the device.  Returns (run_off, start, cls), the shape depth_runs returns: every class is there,
+        0 and len(cuts) included.  `chunks` as for depth_runs."""
+        return self.depth_runs(tid_lo, tid_hi, chunks, _cuts=self._cut_list(cuts))
+
     def depth_runs_kernel_ms(self):
-        """(ms, launches) of the run kernels of the last chunk of depth_runs (COV_K_DEPTH_RUNS)."""
+        """(ms, launches) of the run kernels of the last chunk of depth_runs or depth_class_runs (COV_K_DEPTH_RUNS)."""
         ms = C.c_double(0)
         n = C.c_uint32(0)
         self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_RUNS, C.byref(ms), C.byref(n)))
@@ -264,7 +283,7 @@ class Session:
         self._region_tids = np.unique(arr["tid"]).astype(np.int64)
         self._n_regions = int(arr.size)
 
-    def depth_regions(self, chunks=None):
+    def depth_regions(self, chunks=None, _each=None):
         """cov_depth_regions_compute / cov_depth_regions_fetch over the regions of set_depth_regions, chunk by chunk: per region the sum,
         min, max and covered bases of its per-base depth, reduced on the device.  Returns a native.DEPTH_BIN_DTYPE array IN THE ORDER THE
         REGIONS WERE GIVEN.  Targets without a region are skipped: a chunk begins at the first target at or behind the last chunk's
@@ -287,6 +306,8 @@ class Session:
             res = np.zeros(int(m.value), dtype=native.DEPTH_BIN_DTYPE)
             self._check(self._lib.cov_depth_regions_fetch(self._h, idx.ctypes.data if idx.size else None, res.ctypes.data if res.size else None))
             out[idx.astype(np.int64)] = res
+            if _each is not None:      # (depth_region_counts: the chunk's counts, while the chunk is there)
+                _each(idx)
             if chunks is not None:
                 info = native.CovDepthRegionsInfo()
                 self._check(self._lib.cov_depth_regions_last(self._h, C.byref(info)))
@@ -294,9 +315,32 @@ class Session:
             at = int(np.searchsorted(tids, nxt.value, side="left"))
         return out
 
+    def set_depth_thresholds(self, thr):
+        """cov_depth_thresholds_set: the thresholds depth_region_counts counts (1 .. 16 ascending values in 0 .. 2^31 - 1); nothing (or an
+        empty list) clears them.  Valid any time; kept over set_targets, reset and finish."""
+        arr = self._cut_list(thr if thr is not None else [])
+        self._check(self._lib.cov_depth_thresholds_set(self._h, arr.ctypes.data if arr.size else None, C.c_uint32(arr.size)))
+        self._n_thr = int(arr.size)
+
+    def depth_region_counts(self, chunks=None):
+        """depth_regions with the thresholds of set_depth_thresholds: returns (bins, counts), both IN THE ORDER THE REGIONS WERE GIVEN;
+        bins is what depth_regions returns, counts[i, j] (uint32, shape (n_regions, K)) the bases of region i with depth >= threshold j."""
+        k = getattr(self, "_n_thr", 0)
+        counts = np.zeros((getattr(self, "_n_regions", 0), k), dtype=np.uint32)
+
+        def take(idx):
+            part = np.zeros((len(idx), k), dtype=np.uint32)
+            self._check(self._lib.cov_depth_regions_counts_fetch(self._h, part.ctypes.data if part.size else None))
+            counts[idx.astype(np.int64)] = part
+        bins = self.depth_regions(chunks=chunks, _each=take)
+        if counts.shape[0] == 0:      # (no chunk ran: the fetch refuses with its own words when no thresholds are set)
+            self._check(self._lib.cov_depth_regions_counts_fetch(self._h, None))
+        return bins, counts
+
     def depth_regions_kernel_ms(self):
         """(ms, launches) of the region kernels of the last chunk of depth_regions (COV_K_DEPTH_REGIONS): six launches, k_depth_marks, the
-        rank scan's three, k_bins_init and k_depth_regions (four for a chunk without a region)."""
+        rank scan's three, k_bins_init and k_depth_regions (four for a chunk without a region).  With thresholds set the launches are the
+        same six (or four): k_depth_regions_thr takes k_depth_regions' place, and the counts are zeroed by a fill, which is no launch."""
         ms = C.c_double(0)
         n = C.c_uint32(0)
         self._check(self._lib.cov_kernel_ms(self._h, native.K_DEPTH_REGIONS, C.byref(ms), C.byref(n)))

@@ -79,6 +79,8 @@ class CovDepthRunsInfo(C.Structure):
                 ("tid_lo", C.c_uint32), ("tid_next", C.c_uint32)]
 
 
+DEPTH_MAX_CUTS = 16      # COV_DEPTH_MAX_CUTS: values of a cut list (cov_depth_class_runs_compute, cov_depth_thresholds_set)
+
 # numpy mirror of cov_depth_bin (24 bytes)
 DEPTH_BIN_DTYPE = np.dtype([("sum", "<u8"), ("min", "<i4"), ("max", "<i4"), ("covered", "<u4"), ("reserved", "<u4")])
 assert DEPTH_BIN_DTYPE.itemsize == 24
@@ -107,7 +109,8 @@ EXPORTS = ["cov_abi_version", "cov_create", "cov_destroy", "cov_last_error", "co
            "cov_sam_begin", "cov_sam_window_bytes", "cov_sam_slot_wait", "cov_sam_feed", "cov_sam_end", "cov_ingest_last_stats",
            "cov_interval_reads_compute", "cov_depth_runs_compute", "cov_depth_runs_fetch", "cov_depth_runs_last",
            "cov_depth_bins_compute", "cov_depth_bins_fetch", "cov_depth_bins_last",
-           "cov_depth_regions_set", "cov_depth_regions_compute", "cov_depth_regions_fetch", "cov_depth_regions_last"]
+           "cov_depth_regions_set", "cov_depth_regions_compute", "cov_depth_regions_fetch", "cov_depth_regions_last",
+           "cov_depth_class_runs_compute", "cov_depth_thresholds_set", "cov_depth_regions_counts_fetch"]
 
 _lib = None
 
@@ -186,6 +189,9 @@ def lib():
     L.cov_depth_regions_compute.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     L.cov_depth_regions_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.cov_depth_regions_last.argtypes = [C.c_void_p, C.POINTER(CovDepthRegionsInfo)]
+    L.cov_depth_class_runs_compute.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    L.cov_depth_thresholds_set.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+    L.cov_depth_regions_counts_fetch.argtypes = [C.c_void_p, C.c_void_p]
     _lib = L
     return L
 

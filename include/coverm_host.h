@@ -402,6 +402,40 @@ int covh_depth_regions_format(const covh_bed *b, const cov_depth_bin *results, i
 int covh_depth_regions_write(cov_session *s, const covh_header *h, const covh_bed *b, int value, int no_zeros, int threads, int out_fd,
                              uint64_t *n_regions_out);
 
+/* ---- depth classes (`coverm-amd depth --quantize SPEC`, `--thresholds LIST`): the text of cov_depth_class_runs_compute's runs and of the
+ * threshold counts cov_depth_regions_compute leaves beside its results.
+ * covh_depth_quantize_parse reads a --quantize spec: decimal non-negative integers separated by ':'; an empty first field means 0, an empty
+ * last field means that the last class is open-ended; at least one class must result ("0:1:" gives [0,1) and [1,inf), "5" alone is an
+ * error).  cuts: COV_DEPTH_MAX_CUTS entries.  covh_depth_thresholds_parse reads a --thresholds list: decimal non-negative integers
+ * separated by ','.  Both apply the cut list's rules (1 .. 16 values in 0 .. 2^31 - 1, strictly ascending); COV_ERR_INVALID_ARG with the
+ * reason in covh_last_error.  Neither needs a device.
+ * The classes a quantised track prints: [cuts[i-1], cuts[i]) for i = 1 .. n-1 with the label "lo:hi", and [cuts[n-1], inf) with the label
+ * "lo:inf" when the spec is open-ended.  Class 0 (below the first cut) is never printed, and neither is class n of a closed spec.  A line is
+ *   name \t start \t end \t label \n      end = the start of the target's next run, printed or not, or the target's length.
+ * covh_depth_class_runs_format needs no device, works in ordered pieces like covh_depth_runs_format and gives the same text for every
+ * thread count; covh_depth_class_runs_write walks a finished session chunk by chunk through page-locked memory.
+ * The threshold counts print one line per region,
+ *   chrom \t start \t end [\t name] \t c_1 .. \t c_K \n      c_j = the region's bases with depth >= threshold j,
+ * in the file's order (covh_depth_regions_counts_format: results[] as for covh_depth_regions_format, used by no_zeros, which drops the
+ * regions whose max is 0; counts: n x n_thr, row-major), or one line per window of bin_size bases, name \t start \t end \t c_1 .. c_K, in
+ * target order, then position order (covh_depth_bins_counts_format: bin_off as for covh_depth_bins_format).  The two _write functions set
+ * the thresholds on the session (cov_depth_thresholds_set), go the regions' way (the windows are tiled into regions on the host; 2^32
+ * windows or more are refused with cov_depth_regions_set's message) and clear the thresholds again. */
+int covh_depth_quantize_parse(const char *spec, int32_t *cuts, uint32_t *n_cuts, int *open_end);
+int covh_depth_thresholds_parse(const char *list, int32_t *thr, uint32_t *n_thr);
+int covh_depth_class_runs_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, const uint64_t *run_off, const cov_depth_run *runs,
+                                 const int32_t *cuts, uint32_t n_cuts, int open_end, int threads, int out_fd);
+int covh_depth_class_runs_write(cov_session *s, const covh_header *h, const int32_t *cuts, uint32_t n_cuts, int open_end, int threads, int out_fd,
+                                uint64_t *n_runs_out);
+int covh_depth_regions_counts_format(const covh_bed *b, const cov_depth_bin *results, const uint32_t *counts, uint32_t n_thr, int no_zeros,
+                                     int threads, int out_fd);
+int covh_depth_regions_counts_write(cov_session *s, const covh_header *h, const covh_bed *b, const int32_t *thr, uint32_t n_thr, int no_zeros,
+                                    int threads, int out_fd, uint64_t *n_regions_out);
+int covh_depth_bins_counts_format(const covh_header *h, uint32_t tid_lo, uint32_t n_targets, uint32_t bin_size, const uint64_t *bin_off,
+                                  const cov_depth_bin *bins, const uint32_t *counts, uint32_t n_thr, int no_zeros, int threads, int out_fd);
+int covh_depth_bins_counts_write(cov_session *s, const covh_header *h, uint32_t bin_size, const int32_t *thr, uint32_t n_thr, int no_zeros,
+                                 int threads, int out_fd, uint64_t *n_bins_out);
+
 /* ---- genomes defined by FASTA files (`coverm genome -f / -d -x / --genome-fasta-list`; src/genome_parsing.rs:10-70,
  * src/genomes_and_contigs.rs:25-40).  Host code only: nothing here touches the GPU.
  * covh_genome_fasta_paths resolves a directory (directory != NULL: regular files, symlinks followed, whose name ends in

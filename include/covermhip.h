@@ -453,7 +453,7 @@ cov_status cov_fetch_genome_entries(cov_session *s, cov_genome_entry *out);
  * the host, the records from the first considered record of the contig in flight onwards move to the front of the store and the call
  * goes on ("a spill"); cov_finish / cov_fetch_hist / cov_gather then return the whole sample (record indices count from the sample's first
  * record).  What remains: ONE reference's records must fit (2^32 - 16 records and CIGAR words); after a spill cov_copy_depth,
- * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_depth_bins_compute, cov_depth_regions_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
+ * cov_interval_stats_compute, cov_interval_reads_compute, cov_depth_runs_compute, cov_depth_class_runs_compute, cov_depth_bins_compute, cov_depth_regions_compute, cov_copy_records and cov_pair_filter_apply return COV_ERR_STATE (they need every record) and a device ingest
  * that has to hand its file to the CPU reader fails with COV_ERR_STATE instead of COV_ERR_INGEST_FALLBACK; a store that carries mate
  * columns (cov_ingest_want_mates) or an adopted device batch is never spilled.  cov_store_spills: spills since the last cov_reset. */
 uint32_t cov_store_spills(const cov_session *s);
@@ -584,6 +584,30 @@ cov_status cov_depth_regions_set(cov_session *s, const cov_depth_region *regions
 cov_status cov_depth_regions_compute(cov_session *s, uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_regions);
 cov_status cov_depth_regions_fetch(cov_session *s, uint64_t *input_index, cov_depth_bin *out);
 cov_status cov_depth_regions_last(const cov_session *s, cov_depth_regions_info *out);
+
+/* ---- depth classes: a depth classified against a short ascending list of cut points (csrc/depth_class_core.h).  A cut list holds n values,
+ * 1 <= n <= COV_DEPTH_MAX_CUTS, each in [0, 2^31 - 1], strictly ascending; the class of a depth d is the number of cuts c with c <= d:
+ * class 0 lies below the first cut, class n at or above the last.  A bad list is COV_ERR_INVALID_ARG with the first offending index in
+ * cov_last_error ("value <index>: ...").
+ *   cov_depth_class_runs_compute(s, cuts, n_cuts, tid_lo, tid_hi, &tid_next, &n_runs)
+ *         cov_depth_runs_compute over the depth CLASSES: the maximal stretches of equal class inside each target, every class included
+ *         (0 and n too), in target order, then position order.  States, chunking, knob and refusals are those of cov_depth_runs_compute.
+ *         The chunk belongs to the runs: cov_depth_runs_fetch fetches it (the `depth` field of a run holds its class),
+ *         cov_depth_runs_last and cov_kernel_ms(COV_K_DEPTH_RUNS) describe it (seven launches, as for the plain runs).
+ *   cov_depth_thresholds_set(s, thr, n)
+ *         the thresholds (a cut list) cov_depth_regions_compute counts from now on; n == 0 clears them.  Valid any time after cov_create;
+ *         kept over cov_set_targets, cov_reset and cov_finish.  Setting them drops a regions chunk that awaits its fetch.
+ *         With thresholds set, cov_depth_regions_compute also leaves, per region and threshold t, the number of the region's bases with
+ *         depth >= t (the threshold variant of the region kernel: the same six launches, or four for a chunk without a region; the
+ *         results of cov_depth_regions_fetch are the bytes they are without thresholds).
+ *   cov_depth_regions_counts_fetch(s, counts)
+ *         n_regions * n thresholds values, row-major: row i belongs to result i of cov_depth_regions_fetch.  The states are those of
+ *         cov_depth_regions_fetch, its arena-was-taken sentence included; COV_ERR_STATE when no thresholds are set. */
+#define COV_DEPTH_MAX_CUTS 16
+cov_status cov_depth_class_runs_compute(cov_session *s, const int32_t *cuts, uint32_t n_cuts,
+                                        uint32_t tid_lo, uint32_t tid_hi, uint32_t *tid_next, uint64_t *n_runs);
+cov_status cov_depth_thresholds_set(cov_session *s, const int32_t *thr, uint32_t n);   /* n == 0 clears */
+cov_status cov_depth_regions_counts_fetch(cov_session *s, uint32_t *counts);
 
 /* Page-locked host memory for record batches, pooled: a freed block is kept for the next request of similar size
  * (a decoder filling one batch per BAM file gets its arrays back without re-pinning).  cov_host_alloc returns NULL
