@@ -359,6 +359,23 @@ def session_mates(session, n_records: int):
     return mtid, qh1, qh2
 
 
+def set_mates(session, mtid, qh1, qh2):
+    """Test hook (cov_set_mates): overwrites the mate columns an ingest with want_mates left in the session's store (one entry per record)."""
+    L = _lib()
+    L.cov_set_mates.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cov_last_error.restype = C.c_char_p
+    L.cov_last_error.argtypes = [C.c_void_p]
+    mtid, qh1, qh2 = np.ascontiguousarray(mtid, np.int32), np.ascontiguousarray(qh1, np.uint64), np.ascontiguousarray(qh2, np.uint32)
+    n = C.c_uint64(0)
+    L.cov_copy_records.argtypes = [C.c_void_p, C.POINTER(CovBatch), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    assert L.cov_copy_records(session._h, None, C.byref(n), None) == 0
+    if not (len(mtid) == len(qh1) == len(qh2) == int(n.value)):
+        raise ValueError("set_mates: %d / %d / %d entries for a store of %d records" % (len(mtid), len(qh1), len(qh2), int(n.value)))
+    rc = L.cov_set_mates(session._h, mtid.ctypes.data, qh1.ctypes.data, qh2.ctypes.data)
+    if rc != 0:
+        raise RuntimeError("cov_set_mates: %d: %s" % (rc, (L.cov_last_error(session._h) or b"").decode()))
+
+
 def write_bam(path: str, names, lens, batch: RecordBatch, with_seq=True, level: int = 1, threads: int = None):
     """Threaded BGZF/BAM writer (covh_bam_write) for synthetic inputs.  with_seq: False / 0 = SEQ '*', True / 1 = constant
     SEQ and QUAL, 2 = realistic entropy (random bases, Phred-like qualities, Illumina-style names)."""

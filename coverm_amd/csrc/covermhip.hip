@@ -39,6 +39,7 @@
 #include "store_plan_core.h"
 #include "finish_plan_core.h"
 #include "ingest_plan_core.h"
+#include "pair_key_core.h"
 
 using namespace covk;
 
@@ -2591,8 +2592,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     HIPCHK(hipStreamSynchronize(st));
     u32 biggest = 0;
     for (u32 c = 0; c < n_chunks; c++) biggest = std::max(biggest, cuts[c + 1] > cuts[c] ? cuts[c + 1] - cuts[c] : 0u);
-    u64 cap = 1024;
-    while (cap < 2ull * biggest) cap <<= 1;
+    const u64 cap = pkey::table_size(biggest);
     // (the kernels carry the table size as 32 bits: a table of 2^32 entries would read as 0.)  A reference with that many records, or a
     // table that does not fit the device beside the store, goes to the host's pair filter: the store is still untouched here.
     auto too_big = [&](const char *what) {
@@ -2603,8 +2603,7 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
     if (cap > (1ull << 31)) return too_big("more than 2^30 records of one reference");
     if (d_tab.reserve((size_t)cap, st) != hipSuccess) return too_big("the join table of the largest reference does not fit the device's memory");
     auto chunk_table = [&](u32 r0, u32 r1) -> u64 {        // this chunk's table (a prefix of the buffer) built: its size
-        u64 cc = 1024;
-        while (cc < 2ull * (r1 - r0)) cc <<= 1;
+        const u64 cc = pkey::table_size(r1 - r0);
         (void)hipMemsetAsync(d_tab.p, 0, (size_t)cc * sizeof(covp::PairEntry), st);
         hipLaunchKernelGGL(covp::k_pair_insert, dim3((r1 - r0 + 255u) / 256u), dim3(256), 0, st, C, r0, r1, d_tab.p, (u32)(cc - 1), d_cnt.p);
         return cc;
@@ -2622,7 +2621,8 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
         HIPCHK(hipMemcpyAsync(hcnt.data(), d_cnt.p, hcnt.size() * sizeof(u32), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         if (hcnt[1]) { s->err = "cov_pair_filter_apply: internal error, hash table overflow"; return COV_ERR_STATE; }
-        constexpr u32 CAP = 1u << 20;
+        u32 CAP = 1u << 20;        // listed records of one chunk; knob pair_multi_cap (tests reach the decline without a million records)
+        { long long v; if (covknob::get("pair_multi_cap", v)) CAP = (u32)std::min<long long>(std::max<long long>(v, 16), 1ll << 20); }      // a value below 16 is 16
         DevBuf<covp::MultiRec> d_list; DevBuf<uint2> d_pairs;
         struct Rel2 { DevBuf<covp::MultiRec> &a; DevBuf<uint2> &b; ~Rel2() { a.release(); b.release(); } } rel2{d_list, d_pairs};
         for (u32 c = 0; c < n_chunks; c++) {
@@ -2637,7 +2637,8 @@ cov_status cov_pair_filter_apply(cov_session *s, const cov_pair_filter *f, uint6
             HIPCHK(hipMemcpyAsync(&n_list, d_cnt.p, sizeof n_list, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             if (n_list > CAP) {
-                s->err = "pair filter: more than 2^20 records carry a read name that occurs more than twice among the primary proper-pair records of one reference "
+                s->err = "pair filter: more than " + (CAP == 1u << 20 ? std::string("2^20") : std::to_string(CAP)) +
+                         " records carry a read name that occurs more than twice among the primary proper-pair records of one reference "
                          "(handing the file to the CPU reader)";
                 return COV_ERR_INGEST_FALLBACK;
             }
@@ -2802,6 +2803,20 @@ cov_status cov_copy_mates(cov_session *s, int32_t *mtid, uint64_t *qh1, uint32_t
     if (!s->want_mates || (n && !s->store.mtid.p)) { s->err = "cov_copy_mates: the records were not ingested with cov_ingest_want_mates"; return COV_ERR_STATE; }
     HIPCHK(hipSetDevice(s->cfg.device));
     HIPCHK(s->store.copy_mates_out(mtid, qh1, qh2, s->stream));
+    HIPCHK(hipStreamSynchronize(s->stream));
+    return COV_OK;
+}
+
+// Test hook, the counterpart of cov_copy_mates: the mate columns of a store that has them, overwritten (n_records each).  Read names cannot
+// be made to collide in 64 or 96 bits of their hash; keys written here can.
+cov_status cov_set_mates(cov_session *s, const int32_t *mtid, const uint64_t *qh1, const uint32_t *qh2) {
+    if (!s || s->adopted || !mtid || !qh1 || !qh2) return COV_ERR_STATE;
+    if (s->spill.active) { s->err = "cov_set_mates: part of the sample's records already left the bounded record store"; return COV_ERR_STATE; }
+    const uint64_t n = s->store.n_records;
+    if (!s->want_mates || (n && !s->store.mtid.p)) { s->err = "cov_set_mates: the records were not ingested with cov_ingest_want_mates"; return COV_ERR_STATE; }
+    if (s->store.mates_valid != n) { s->err = "cov_set_mates: the store holds records without mate columns"; return COV_ERR_STATE; }
+    HIPCHK(hipSetDevice(s->cfg.device));
+    HIPCHK(s->store.copy_mates_in(mtid, qh1, qh2, s->stream));
     HIPCHK(hipStreamSynchronize(s->stream));
     return COV_OK;
 }

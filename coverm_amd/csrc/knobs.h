@@ -8,6 +8,8 @@
 //   ingest_round_blocks, ingest_carry_kb, ingest_cwin_kb      cov_ingest_begin: blocks per inflate window, carry buffer, compressed window
 //   depth_chunk_bases                       cov_create: arena entries of one chunk of cov_depth_runs_compute / cov_depth_bins_compute / cov_depth_regions_compute (default 2^28)
 //   pair_chunk                              cov_pair_filter: records per table chunk
+//   pair_multi_cap                          cov_pair_filter: records of read names used more than twice that one chunk may list before the file is handed to
+//                                           the CPU reader (default 2^20; a value below 16 is taken as 16, one above 2^20 as 2^20)
 //   ingest_piece_kb                         covh_bam_ingest_device: bytes per staging piece
 //   stream_window_kb, filter_window_kb      the streamed CPU reader's and `coverm-amd filter`'s compressed windows
 //   finalise_threads                        the host estimators' thread count

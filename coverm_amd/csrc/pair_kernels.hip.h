@@ -30,6 +30,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "name_hash_core.h"
+#include "pair_key_core.h"
 
 namespace covp {
 
@@ -85,18 +86,14 @@ __global__ void k_pair_cuts(const int32_t *__restrict__ tid, u32 n, u32 T, u32 n
     cuts[c] = lo;
 }
 
-__device__ __forceinline__ u32 table_slot(u64 k1, u64 k2t, u32 mask) {
-    u64 x = k1 ^ (k2t * 0x9e3779b97f4a7c15ull);
-    x ^= x >> 29;
-    return (u32)x & mask;
-}
+// The key of a record and the slot its probe run starts at: csrc/pair_key_core.h (one statement for the kernels, the driver and the CPU test)
+using pkey::key_k1; using pkey::key_k2t; using pkey::table_slot;
 
 __global__ __launch_bounds__(256) void k_pair_insert(PairCols C, u32 r0, u32 r1, PairEntry *__restrict__ T, u32 mask, u32 *__restrict__ counters) {
     const u32 i = r0 + blockIdx.x * 256u + threadIdx.x;
     if (i >= r1) return;
     if (!eligible(C.flag[i])) return;
-    u64 k1 = C.qh1[i]; if (!k1) k1 = 1;
-    const u64 k2t = (u64)C.qh2[i] | ((u64)((u32)C.tid[i] + 2u) << 32);
+    const u64 k1 = key_k1(C.qh1[i]), k2t = key_k2t(C.qh2[i], C.tid[i]);
     u32 h = table_slot(k1, k2t, mask);
     for (u32 probe = 0; probe <= mask; probe++, h = (h + 1u) & mask) {
         PairEntry *e = T + h;
@@ -181,8 +178,7 @@ __global__ __launch_bounds__(256) void k_pair_collect(PairCols C, u32 r0, u32 r1
     const u32 i = r0 + blockIdx.x * 256u + threadIdx.x;
     if (i >= r1) return;
     if (!eligible(C.flag[i])) return;
-    u64 k1 = C.qh1[i]; if (!k1) k1 = 1;
-    const u64 k2t = (u64)C.qh2[i] | ((u64)((u32)C.tid[i] + 2u) << 32);
+    const u64 k1 = key_k1(C.qh1[i]), k2t = key_k2t(C.qh2[i], C.tid[i]);
     u32 h = table_slot(k1, k2t, mask);
     for (u32 probe = 0; probe <= mask; probe++, h = (h + 1u) & mask) {
         const PairEntry e = T[h];

@@ -99,6 +99,12 @@ struct RecordStore {
         RS_TRY(hipMemcpyAsync(h_mtid, mtid.p, n * 4, hipMemcpyDeviceToHost, st)); RS_TRY(hipMemcpyAsync(h_qh1, qh1.p, n * 8, hipMemcpyDeviceToHost, st));
         return hipMemcpyAsync(h_qh2, qh2.p, n * 4, hipMemcpyDeviceToHost, st);
     }
+    hipError_t copy_mates_in(const int32_t *h_mtid, const uint64_t *h_qh1, const uint32_t *h_qh2, hipStream_t st) {
+        const uint64_t n = n_records;
+        if (!n) return hipSuccess;
+        RS_TRY(hipMemcpyAsync(mtid.p, h_mtid, n * 4, hipMemcpyHostToDevice, st)); RS_TRY(hipMemcpyAsync(qh1.p, h_qh1, n * 8, hipMemcpyHostToDevice, st));
+        return hipMemcpyAsync(qh2.p, h_qh2, n * 4, hipMemcpyHostToDevice, st);
+    }
     template <typename T>
     hipError_t front_(T *p, size_t from, size_t n, hipStream_t st) {
         if (!n || !from) return hipSuccess;

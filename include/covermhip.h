@@ -292,7 +292,7 @@ cov_status cov_sam_end(cov_session *s, uint64_t *n_records);
  * runs with cov_config.filter_single = 0.  COV_ERR_NM_MISSING / COV_ERR_NM_BADTYPE where the reference's nm() would have panicked;
  * COV_ERR_INGEST_FALLBACK (store untouched) when more than 2^20 records carry a read name that occurs more than twice among the
  * primary proper-pair records of one reference (fewer are replayed exactly): run the host filter (covh_pair_mode_order) on the CPU
- * reader's records then.  Same layout as covh_pair_filter. */
+ * reader's records then.  (Tests lower the 2^20 with the knob pair_multi_cap, csrc/knobs.h.)  Same layout as covh_pair_filter. */
 typedef struct {
     int32_t filter_single;     /* single-read thresholds apply to both mates as well (filter.rs:48-55) */
     uint8_t min_mapq;          /* 255 = off */
@@ -324,6 +324,11 @@ cov_status cov_copy_records(cov_session *s, const cov_batch *host, uint64_t *n_r
 /* Test hook: what an ingest with cov_ingest_want_mates kept beside the records — the mate's reference and the 96-bit read-name hash
  * (csrc/name_hash_core.h), n_records entries each.  COV_ERR_STATE without want_mates. */
 cov_status cov_copy_mates(cov_session *s, int32_t *mtid, uint64_t *qh1, uint32_t *qh2);
+/* Test hook, the counterpart of cov_copy_mates: overwrites the three mate columns of a store that already has them (n_records entries
+ * each, host arrays), before cov_pair_filter_apply.  The filter then joins records by the keys given here: two records with equal
+ * (qh1 with 0 read as 1, qh2) on one reference are one read name to it, whatever their names were, which is how tests reach key
+ * collisions that no pair of names produces.  COV_ERR_STATE as cov_copy_mates, and when the columns do not cover the whole store. */
+cov_status cov_set_mates(cov_session *s, const int32_t *mtid, const uint64_t *qh1, const uint32_t *qh2);
 
 /* Multi-GPU, one process: after cov_finish on every session (one per device, same targets), ONE RCCL gather moves each
  * rank's per-contig result block (fixed size: 160 B per contig + counters) to the device of sessions[root] over xGMI and
